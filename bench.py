@@ -7,7 +7,11 @@ primitive applied to every state -- the loop body of ManipLattice::GetSuccs (smp
 for every (state, primitive), including the state-table lookup of every valid successor and the ballot compaction
 of the valid ones (K5) -- inputs and outputs resident in HBM.  value = successor evaluations / s, whole job.
 
-That figure is a kernel-level rate.  What a caller of the plugin API gets is reported beside it, in the same line:
+A plain run does only what `value` needs: set-up, --warmup steps, --steps timed steps, the result line (and, with
+--dump-outputs DIR, the arrays the last timed step handed back, as DIR/<name>.npy).  Everything else is behind --full.
+
+That figure is a kernel-level rate.  What a caller of the plugin API gets is reported beside it, in the same line, with
+--full (which also adds the roofline of the step's collision kernel and secondary figures of the step itself):
   planner        one query through smplx_plan (the engine's own ARA*, frontier hints from its OPEN list)
   planner_plain  the same query driven by an SBPL-shaped ARA* that only knows GetSuccs / GetGoalHeuristic
                  (tests/cpp/sbpl_loop_driver.cpp over include/smpl_amd/plugin.hpp; no hints)
@@ -21,8 +25,9 @@ That figure is a kernel-level rate.  What a caller of the plugin API gets is rep
 N > 1 (driver: torch.distributed.run, one rank per GPU, RCCL): queries shard by rank -- rank r owns queries
 [128 r, 128 r + 128) of the seeded config-4 list on the replicated scene (its own goals, BFS grids, state tables), no
 collective on the data path; the per-query result records are all-gathered once at the end (smpl_amd/shard.py).  Every
-rank times the step on a frontier of its own first query and runs its shard; `value` = step evaluations of all ranks /
-max-over-ranks time (weak scaling), `shard` = whole-job figures of the config-4 run.
+rank times the step on a frontier of its own first query and (with --full) runs its shard; `value` = step evaluations
+of all ranks / max-over-ranks time (weak scaling), `shard` = whole-job figures of the config-4 run.  --dump-outputs
+writes rank 0's step.
 """
 from __future__ import annotations
 
@@ -62,6 +67,50 @@ def frontier_of(space, B, p, nwarm0):
     return np.stack([space.get_state(i)[0] for i in range(1, B + 1)])
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+
+
+def dump_step_outputs(dirname, B, M, N, d_flags, d_coord, d_sq, d_h, d_cost, d_lk, d_id, d_reca, d_recb, d_btab, rb):
+    """What a caller of the step receives (include/smpl_amd.h, smplx_expand_batch_k5_device), as float64 .npy files:
+    the dense outputs indexed [state][primitive], entries the header leaves undefined set to 0, and the compacted
+    successor stream in (state, primitive) order -- block_tab walked block by block, since where a block's records land
+    in their region depends on the order of its atomics.  Past DUMP_BUDGET_BYTES a fixed, seeded sample of the states is
+    written; state_index names the rows either way."""
+    flags = d_flags.cpu().numpy().reshape(B, M)
+    valid = (flags & 1) != 0
+    dense = {"flags": flags,
+             "coord": np.where(valid[:, :, None], d_coord.cpu().numpy().reshape(B, M, N), 0),
+             "succ_q": np.where(((flags & 0x10) == 0)[:, :, None], d_sq.cpu().numpy().reshape(B, M, N), 0.0),
+             "h": d_h.cpu().numpy().reshape(B, M), "cost": d_cost.cpu().numpy().reshape(B, M),
+             "lookups": np.where((flags & 0x40) == 0, d_lk.cpu().numpy().reshape(B, M), 0),
+             "succ_id": d_id.cpu().numpy().reshape(B, M)}
+    btab = d_btab.cpu().numpy().reshape(-1, 4)
+    ia = np.concatenate([np.arange(f, f + c) for f, c in btab[:, 0:2]] + [np.zeros(0, np.int64)])
+    ib = np.concatenate([np.arange(f, f + c) for f, c in btab[:, 2:4]] + [np.zeros(0, np.int64)])
+    rec_a = d_reca.cpu().numpy().reshape(-1, 2)[ia]
+    ints = (N + 2) // 2 * 2                      # int32 h, coord[N], padding to 8 bytes; then double q[N]
+    rec_t = np.dtype([("i", "<i4", (ints,)), ("q", "<f8", (N,))])
+    assert rec_t.itemsize == rb
+    rec_b = np.ascontiguousarray(d_recb.cpu().numpy().reshape(-1, rb)[ib]).view(rec_t).reshape(-1)
+    a_state = rec_a[:, 1] >> 9
+    a_needs_b = (rec_a[:, 0] < 0) | ((rec_a[:, 1] & 0x100) != 0)     # unknown coordinate, or a goal successor
+    assert int(a_needs_b.sum()) == rec_b.shape[0]
+    b_state = a_state[a_needs_b]
+    keep = np.arange(B)
+    total = 8 * (sum(a.size for a in dense.values()) + rec_a.size + rec_b.shape[0] * (1 + 2 * N))
+    if total > DUMP_BUDGET_BYTES:
+        per_state = 8 * M * (5 + 2 * N + 2 + 1 + 2 * N)   # dense + at most one record of each region per edge
+        keep = np.sort(np.random.default_rng(0).choice(B, DUMP_BUDGET_BYTES // per_state, replace=False))
+        dense = {k: a[keep] for k, a in dense.items()}
+        rec_a = rec_a[np.isin(a_state, keep)]
+        rec_b = rec_b[np.isin(b_state, keep)]
+    arrays = dict(dense, state_index=keep, compact_a=rec_a, compact_b_h=rec_b["i"][:, 0],
+                  compact_b_coord=rec_b["i"][:, 1:1 + N], compact_b_q=rec_b["q"])
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,6 +141,11 @@ def main():
     ap.add_argument("--no-k2", action="store_true")
     ap.add_argument("--setup-threads", type=int, default=8, help="host threads that set goals (BFS) and starts of the shard's queries")
     ap.add_argument("--generic-kernels", action="store_true", help="skip the per-robot hiprtc build (A/B runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the secondary figures of the step, the rates through the plugin API, the CPU "
+                         "baselines and the parity checks (the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     import torch
@@ -131,10 +185,13 @@ def main():
 
     space = new_space()
     spec_ok, spec_note = space.specialized()
-    # BASELINE config 4: the seeded list of (start, goal) pairs; validity of the candidates decided by the engine
-    cs, cg = scenes.config4_candidates()
-    S_all, G_all = scenes.config4_queries(cs, cg, space.state_valid_batch(cs)[0], space.state_valid_batch(cg)[0])
-    first, last, S_mine, G_mine = shard.rank_queries(S_all, G_all, rank, world, args.queries_per_gpu)
+    # BASELINE config 4: the seeded list of (start, goal) pairs; validity of the candidates decided by the engine.  A rank
+    # other than 0 steps on its own first query; the shard leg (--full) runs them all
+    first, last, S_mine, G_mine = 0, 0, [], []
+    if world > 1 or args.full:
+        cs, cg = scenes.config4_candidates()
+        S_all, G_all = scenes.config4_queries(cs, cg, space.state_valid_batch(cs)[0], space.state_valid_batch(cg)[0])
+        first, last, S_mine, G_mine = shard.rank_queries(S_all, G_all, rank, world, args.queries_per_gpu)
 
     # ---- the step: a frontier batch of this rank's own query (rank 0: the config-2 query itself) -------------------
     B = args.batch
@@ -182,7 +239,8 @@ def main():
         step()
     torch.cuda.synchronize()
     d_cnt.zero_()
-    space.profile_begin(min(args.steps, args.profile_steps if args.profile_steps > 0 else max(1, args.steps // 8)))
+    if args.full:   # the roofline's HIP events, inside the timed region
+        space.profile_begin(min(args.steps, args.profile_steps if args.profile_steps > 0 else max(1, args.steps // 8)))
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -193,7 +251,6 @@ def main():
     if dist is not None:
         dist.barrier()
     t1 = time.perf_counter()
-    prep_ms, expand_ms, launches = space.profile_end()
     evals, valid, lookups_ref, lookups_done, configs, state_lookups = space.counters_read(d_cnt.data_ptr(), B)
     elapsed = t1 - t0
     raw_k5 = d_tot.cpu().numpy()
@@ -202,36 +259,14 @@ def main():
     k5 = {"valid_successors_per_launch": int(tot_k5[0]), "full_records_per_launch": int(tot_k5[1]), "overflow": int(tot_k5[2]),
           "known_ids_per_launch": known, "table_states": space.num_states() - 1,
           "compact_bytes_per_launch": int(8 * tot_k5[0] + rb * tot_k5[1]), "dense_bytes_per_launch": int(B * M * (12 * N + 9))}
+    if args.dump_outputs and rank == 0:
+        # before any other leg reuses the step's buffers
+        dump_step_outputs(args.dump_outputs, B, M, N, d_flags, d_coord, d_sq, d_h, d_cost, d_lk, d_id, d_reca, d_recb,
+                          d_btab, rb)
 
     # whole-job aggregate: units of all ranks / max-over-ranks time (one all-gather of three doubles per rank)
     sc = shard.gather_scalars([float(evals), elapsed, float(valid)], dist, world, coll_dev)
     value, tmax, total_evals = shard.aggregate(sc[:, :2])
-
-    # ---- roofline of the dominant kernel (k_pipe_configs: the collision check), this rank ---------------------------
-    # SURVEY 8(d), collision kernel: algorithmic bytes = 4 B per distance-grid lookup + 8N B per configuration.
-    # HIP events on the launch stream bracket the kernel inside the timed region (smplx_profile_*).
-    L_ = max(args.steps, 1)        # the tallies cover every timed step
-    P_ = max(launches, 1)          # the events cover the first --profile-steps of them
-    cfg_per_launch = configs / L_
-    lk_per_launch = (lookups_done + state_lookups) / L_
-    alg_bytes = 4.0 * lk_per_launch + 8.0 * N * cfg_per_launch
-    k_ms = prep_ms / P_            # first event interval = k_pipe_configs
-    achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-    # HBM-side bytes of the same kernel from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate
-    # runs; gfx950 correction applied) -- kept in profiles/traffic.json, null when that file is absent
-    traffic = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-            traffic = json.load(f)["k_pipe_configs"]["bytes_per_launch"] if args.batch == 4096 and args.grid == 256 else None
-    except (OSError, KeyError, ValueError):
-        traffic = None
-    roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "kernel": "k_pipe_configs",
-                "kernel_ms": round(k_ms, 4), "finish_kernel_ms": round(expand_ms / P_, 4), "profiled_steps": int(launches),
-                "algorithmic_bytes_per_launch": int(alg_bytes), "configs_per_launch": int(cfg_per_launch),
-                "lookups_per_launch": int(lk_per_launch), "evals_per_launch": int(evals / L_),
-                "succ_eval_bytes_per_launch": int(evals / L_ * (20 * N + 8) + 4.0 * lookups_ref / L_),
-                "reference_lookups_per_launch": int(lookups_ref / L_)}
 
     out = {
         "metric": "successor evaluations/sec, ManipLattice GetSuccs loop body (7-DOF arm, 256^3 voxel grid)",
@@ -244,13 +279,41 @@ def main():
                    "batch_states": B, "primitives": M, "grid": args.grid, "queries": world,
                    "parallelism": f"query-shard x{world} (cfg 4 list, 128 queries per GPU)" if world > 1 else "single query"},
         "value_is": "kernel-level rate of the batched step (inputs resident in HBM); rates through the plugin API are in "
-                    "planner / planner_plain / shard",
+                    "planner / planner_plain / shard (--full)",
         "valid_fraction": round(valid / max(evals, 1), 4),
         "k5": k5,
         "kernels": ("per-robot hiprtc build, " + spec_note[:120]) if spec_ok else "generic (" + spec_note[:200] + ")",
-        "roofline": roofline,
     }
-    single = rank == 0 and world == 1
+
+    if args.full:
+        # ---- roofline of the dominant kernel (k_pipe_configs: the collision check), this rank -----------------------
+        # SURVEY 8(d), collision kernel: algorithmic bytes = 4 B per distance-grid lookup + 8N B per configuration.
+        # HIP events on the launch stream bracket the kernel inside the timed region (smplx_profile_*).
+        prep_ms, expand_ms, launches = space.profile_end()
+        L_ = max(args.steps, 1)        # the tallies cover every timed step
+        P_ = max(launches, 1)          # the events cover the first --profile-steps of them
+        cfg_per_launch = configs / L_
+        lk_per_launch = (lookups_done + state_lookups) / L_
+        alg_bytes = 4.0 * lk_per_launch + 8.0 * N * cfg_per_launch
+        k_ms = prep_ms / P_            # first event interval = k_pipe_configs
+        achieved = alg_bytes / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+        # HBM-side bytes of the same kernel from the PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate
+        # runs; gfx950 correction applied) -- kept in profiles/traffic.json, null when that file is absent
+        traffic = None
+        try:
+            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                traffic = json.load(f)["k_pipe_configs"]["bytes_per_launch"] if args.batch == 4096 and args.grid == 256 else None
+        except (OSError, KeyError, ValueError):
+            traffic = None
+        out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBPS, 6), "traffic": traffic, "kernel": "k_pipe_configs",
+                           "kernel_ms": round(k_ms, 4), "finish_kernel_ms": round(expand_ms / P_, 4), "profiled_steps": int(launches),
+                           "algorithmic_bytes_per_launch": int(alg_bytes), "configs_per_launch": int(cfg_per_launch),
+                           "lookups_per_launch": int(lk_per_launch), "evals_per_launch": int(evals / L_),
+                           "succ_eval_bytes_per_launch": int(evals / L_ * (20 * N + 8) + 4.0 * lookups_ref / L_),
+                           "reference_lookups_per_launch": int(lookups_ref / L_)}
+    # every leg below is --full only
+    single = args.full and rank == 0 and world == 1
 
     if single and args.overlap_streams > 1:
         # secondary figure: the same step with several independent frontier batches in flight (what a GPU that
@@ -623,7 +686,7 @@ def main():
         except Exception as e:   # the secondary leg must not take the bench line down
             out["planner_plain"] = {"error": repr(e)[:300]}
 
-    if not args.no_shard and not args.no_planner:
+    if args.full and not args.no_shard and not args.no_planner:
         # ---- BASELINE config 4: this rank's 128 queries through smplx_plan_multi: the device-resident search, one persistent
         # workgroup per query, all in one launch ------------------------------------------------------------------------
         nb = args.shard_expansions

@@ -1,6 +1,7 @@
 """The oracle's IntrusiveHeap against golden vectors produced by the REFERENCE's own header
 (smpl/include/smpl/intrusive_heap.h compiled in place: oracle/_ref/heap_ref, tests/golden/make_heap_golden.py).
 This is the one piece of the path the reference's code pins directly."""
+import hashlib
 import json
 import os
 import subprocess
@@ -11,6 +12,7 @@ import pytest
 from oracle_binding import ORACLE_DIR, Oracle
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "heap_ref.json")
+GOLD_LIVE = os.path.join(os.path.dirname(__file__), "golden", "heap_ref_live.json")
 
 
 @pytest.fixture(scope="module")
@@ -33,11 +35,8 @@ def test_survey_tie_order(oracle):
     assert got[4:] == [4, 1, 2, 0, 3, -1]
 
 
-def test_live_reference_binary_agrees_when_present(oracle):
-    """In the build container oracle/_ref/heap_ref exists: drive it live on a fresh random sequence."""
-    binp = os.path.join(ORACLE_DIR, "_ref", "heap_ref")
-    if not os.path.exists(binp):
-        pytest.skip("oracle/_ref/heap_ref not built here (reference absent)")
+def live_ops():
+    """The seeded sequence of the live test (tests/golden/make_live_golden.py stores the reference's answers to it)."""
     rng = np.random.default_rng(77)
     ops = []
     n = 0
@@ -49,6 +48,19 @@ def test_live_reference_binary_agrees_when_present(oracle):
             ops.append((1, 0))
         else:
             ops.append((3, int(rng.integers(0, n))))
-    text = f"{len(ops)}\n" + "\n".join(f"{c} {k}" for c, k in ops) + "\n"
-    ref = [int(x) for x in subprocess.run([binp], input=text.encode(), stdout=subprocess.PIPE, check=True).stdout.split()]
+    return ops, f"{len(ops)}\n" + "\n".join(f"{c} {k}" for c, k in ops) + "\n"
+
+
+def test_live_reference_binary_agrees_when_present(oracle):
+    """The reference heap on a seeded sequence of its own: its answers are stored in tests/golden/heap_ref_live.json, and
+    where oracle/_ref/heap_ref is built (the reference's header compiled in place) it is driven live as well."""
+    ops, text = live_ops()
+    with open(GOLD_LIVE) as f:
+        stored = json.load(f)
+    assert stored["input_sha256"] == hashlib.sha256(text.encode()).hexdigest(), "the seeded sequence is not the stored one"
+    ref = stored["top_after_each_op"]
+    binp = os.path.join(ORACLE_DIR, "_ref", "heap_ref")
+    if os.path.exists(binp):
+        live = subprocess.run([binp], input=text.encode(), stdout=subprocess.PIPE, check=True).stdout.split()
+        assert [int(x) for x in live] == ref
     assert oracle.heap_run(np.array(ops, np.int32)).tolist() == ref

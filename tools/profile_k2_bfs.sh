@@ -5,8 +5,8 @@ set -e
 OUT=gpurun_out/${1:-prof_k2}
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o k2 -- python3 bench.py --no-cpu --no-planner --no-shard --overlap-streams 1 --scaling-batches= --steps 10 > "$OUT/k2.log" 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT" -o k2fetch -- python3 bench.py --no-cpu --no-planner --no-shard --overlap-streams 1 --scaling-batches= --steps 10 > "$OUT/k2fetch.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o k2 -- python3 bench.py --full --no-cpu --no-planner --no-shard --overlap-streams 1 --scaling-batches= --steps 10 > "$OUT/k2.log" 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT" -o k2fetch -- python3 bench.py --full --no-cpu --no-planner --no-shard --overlap-streams 1 --scaling-batches= --steps 10 > "$OUT/k2fetch.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bfs256 -- python3 tools/bfs_time.py 256 > "$OUT/bfs256.log" 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o bfs512 -- python3 tools/bfs_time.py 512 > "$OUT/bfs512.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT" -o bfsfetch -- python3 tools/bfs_time.py 256 > "$OUT/bfsfetch.log" 2>&1

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/r03_prof
 mkdir -p "$OUT"
 tools/profile_round.sh r03_prof/round > "$OUT/round.log" 2>&1
-K2="bench.py --no-cpu --no-planner --overlap-streams 1 --scaling-batches= --steps 10"
+K2="bench.py --full --no-cpu --no-planner --overlap-streams 1 --scaling-batches= --steps 10"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -o k2 -- python3 $K2 > "$OUT/k2.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$OUT" -o k2fetch -- python3 $K2 > "$OUT/k2fetch.log" 2>&1
 tools/profile_bfs.sh r03_prof/bfs256 256 > "$OUT/bfs256.log" 2>&1
