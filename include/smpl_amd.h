@@ -339,6 +339,44 @@ int smplx_search_counters(const smplx_space* s, int64_t out[16]);
 int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p, int32_t* path_ids, int cap,
                      smplx_search_stats* stats, double* wall_seconds, int host_threads);
 
+/* ---- anytime ARA*: time budgets, resumable replans, partial solutions (ARAStar::replan(const TimeParameters&, ...),
+ * arastar.cpp:107-215 and 486-527; TimeParameters / timedOut: arastar.h:80-90, arastar.cpp:454-484) ----
+ * A call CONTINUES the previous search of the space (resumed = 1) when from_scratch == 0, the space has a search from an
+ * earlier smplx_plan / smplx_replan call that ran on the same side (device or host loop), the start id is the same, no
+ * smplx_set_goal_* (it renumbers the lattice) and no failed call on the space came since; otherwise it plans from scratch
+ * (the reference's "start changed -> reinitialise", arastar.cpp:128-162).  A resumed call keeps OPEN, INCONS, the search
+ * states, the iteration, curr_eps and satisfied_eps; its expansion count and budget clock start at 0; final_eps,
+ * delta_eps, improve and the budgets are this call's (the setters of arastar.h:96-123 between calls), initial_eps is
+ * used only from scratch.  The budget is checked where timedOut sits (after the goal test, before the pop): max_*_init
+ * while there is no solution, max_* once there is one; wall mode counts seconds since the call entered smplx_replan*,
+ * and a budget of 0 expands nothing.  With no solution, allow_partial and OPEN not empty, the call returns the bp chain
+ * from OPEN's minimum, its g as the cost, result SMPLX_ARA_PARTIAL and solved = 1 (arastar.cpp:204-209).  A call that
+ * times out while improving returns the goal's current chain (arastar.cpp:213).  smplx_expansion_log holds the pops of
+ * the whole search since it last started from scratch, across resumed calls. */
+enum { SMPLX_TIME_EXPANSIONS = 0, SMPLX_TIME_WALL = 1 };                /* ARAStar::TimeParameters::TimingType */
+enum { SMPLX_ARA_SUCCESS = 0, SMPLX_ARA_PARTIAL = 1,                     /* ReplanResultCode, arastar.cpp:97-105 */
+       SMPLX_ARA_TIMED_OUT = 4, SMPLX_ARA_EXHAUSTED = 5 };
+typedef struct smplx_time_params {
+    double initial_eps, final_eps, delta_eps;
+    int32_t improve, bounded, type;               /* type: SMPLX_TIME_* */
+    int32_t max_expansions_init, max_expansions;
+    double max_seconds_init, max_seconds;         /* max_allowed_time_init / max_allowed_time */
+    int32_t allow_partial;                        /* ARAStar::allowPartialSolutions */
+    int32_t from_scratch;                         /* force_planning_from_scratch before this call */
+} smplx_time_params;
+typedef struct smplx_replan_stats {
+    smplx_search_stats s;         /* expansions / expansions_init / satisfied_eps: since the search began (get_n_expands ...);
+                                     seconds, evaluations, lookups, batches: this call's */
+    int32_t result;               /* SMPLX_ARA_* of this call */
+    int32_t call_expansions;      /* expansions of this call */
+    int32_t resumed;              /* 1 = continued the previous search of this space */
+    int32_t pad;
+} smplx_replan_stats;
+/* smplx_plan / smplx_plan_multi are these with from_scratch = 1, SMPLX_TIME_EXPANSIONS and allow_partial = 0. */
+int smplx_replan(smplx_space* s, const smplx_time_params* p, int32_t* path_ids, int cap, smplx_replan_stats* st);
+int smplx_replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32_t* path_ids, int cap,
+                       smplx_replan_stats* st, double* wall_seconds, int host_threads);
+
 /* Query sharding over ranks, one process per GPU (independent queries partition over GPUs with no data-path
  * collective; the demo's outer loop over requests, smpl_test/src/call_planner.cpp): rank r of `world` owns queries
  * [*first, *first + *count) of a list of `total`, `per_rank` each (BASELINE config 4: 128), the last ranks possibly fewer or

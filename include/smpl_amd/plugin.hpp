@@ -8,11 +8,13 @@
 //   RobotPlanningSpace   smpl/include/smpl/graph/robot_planning_space.h:60-218
 //                        (+ SBPL DiscreteSpaceInformation::GetSuccs, Heuristic::GetGoalHeuristic)
 //   Extension            smpl/include/smpl/extension.h:40-60
+//   ARAStar              smpl/include/smpl/search/arastar.h:80-165 (GpuARAStar: the engine's own search)
 // In a real integration these classes derive from the reference's own bases; the bodies
 // stay as they are here.
 #pragma once
 
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
 #include <cstdint>
 #include <cstdio>
@@ -446,6 +448,109 @@ public:
 
 private:
     GpuPlanningContext* ctx_;
+};
+
+// sbpl::ARAStar (smpl/include/smpl/search/arastar.h:80-165, smpl/src/search/arastar.cpp) over the engine's own search
+// (smplx_replan): the same public interface, for a caller that wants the device-resident or host-driven ARA* instead of
+// an ARAStar that calls GetSuccs.  The search lives in the context's space; it continues between replan calls while the
+// start is unchanged (the reference's contract, arastar.h:55-78).  Return values follow the reference: replan returns 1
+// on success or partial success, 0 otherwise.  (The ReplanParams overloads are not mirrored.)
+class GpuARAStar {
+public:
+    typedef std::chrono::steady_clock clock;
+    struct TimeParameters {                        // arastar.h:84-92
+        bool bounded = true;
+        bool improve = true;
+        enum TimingType { EXPANSIONS, TIME } type = TIME;
+        int max_expansions_init = 0;
+        int max_expansions = 0;
+        clock::duration max_allowed_time_init = clock::duration::zero();
+        clock::duration max_allowed_time = clock::duration::zero();
+    };
+
+    explicit GpuARAStar(GpuPlanningContext* ctx) : ctx_(ctx) {}
+
+    void allowPartialSolutions(bool enabled) { allow_partial_ = enabled; }
+    bool allowPartialSolutions() const { return allow_partial_; }
+    void setAllowedRepairTime(double allowed_time_secs) { time_params_.max_allowed_time = to_duration(allowed_time_secs); }
+    double allowedRepairTime() const { return to_seconds(time_params_.max_allowed_time); }
+    void setTargetEpsilon(double target_eps) { final_eps_ = std::max(target_eps, 1.0); }
+    double targetEpsilon() const { return final_eps_; }
+    void setDeltaEpsilon(double delta_eps) { delta_eps_ = delta_eps; }
+    double deltaEpsilon() const { return delta_eps_; }
+    void setImproveSolution(bool improve) { time_params_.improve = improve; }
+    bool improveSolution() const { return time_params_.improve; }
+    void setBoundExpansions(bool bound) { time_params_.bounded = bound; }
+    bool boundExpansions() const { return time_params_.bounded; }
+
+    int replan(const TimeParameters& params, std::vector<int>* solution, int* cost)   // arastar.cpp:107-215
+    {
+        time_params_ = params;
+        smplx_time_params p;
+        p.initial_eps = initial_eps_; p.final_eps = final_eps_; p.delta_eps = delta_eps_;
+        p.improve = params.improve; p.bounded = params.bounded;
+        p.type = params.type == TimeParameters::TIME ? SMPLX_TIME_WALL : SMPLX_TIME_EXPANSIONS;
+        p.max_expansions_init = params.max_expansions_init; p.max_expansions = params.max_expansions;
+        p.max_seconds_init = std::max(0.0, to_seconds(params.max_allowed_time_init));
+        p.max_seconds = std::max(0.0, to_seconds(params.max_allowed_time));
+        p.allow_partial = allow_partial_;
+        p.from_scratch = from_scratch_;
+        ids_.resize(1 << 16);
+        smplx_replan_stats st;
+        if (smplx_replan(ctx_->space(), &p, ids_.data(), (int)ids_.size(), &st) != SMPLX_OK || st.s.path_len > (int)ids_.size()) {
+            from_scratch_ = 1;
+            return 0;
+        }
+        from_scratch_ = 0;
+        stats_ = st;
+        if (!st.s.solved) return 0;
+        if (solution) solution->assign(ids_.begin(), ids_.begin() + st.s.path_len);
+        if (cost) *cost = st.s.cost;
+        return 1;
+    }
+    int replan(double allowed_time_secs, std::vector<int>* solution)
+    {
+        int cost;
+        return replan(allowed_time_secs, solution, &cost);
+    }
+    int replan(double allowed_time_secs, std::vector<int>* solution, int* cost)      // arastar.cpp:245-265
+    {
+        TimeParameters tparams = time_params_;
+        if (tparams.max_allowed_time_init == tparams.max_allowed_time) {
+            tparams.max_allowed_time_init = to_duration(allowed_time_secs);
+            tparams.max_allowed_time = to_duration(allowed_time_secs);
+        } else {
+            tparams.max_allowed_time_init = to_duration(allowed_time_secs);   // the repair time stays
+        }
+        return replan(tparams, solution, cost);
+    }
+    int force_planning_from_scratch() { from_scratch_ = 1; return 0; }                 // arastar.cpp:380-385
+    int force_planning_from_scratch_and_free_memory() { return force_planning_from_scratch(); }
+    int set_search_mode(bool first_solution_unbounded) { time_params_.bounded = !first_solution_unbounded; return 0; }
+    void set_initialsolution_eps(double eps) { initial_eps_ = eps; }
+    double get_solution_eps() const { return stats_.s.satisfied_eps; }
+    int get_n_expands() const { return stats_.s.expansions; }
+    int get_n_expands_init_solution() const { return stats_.s.expansions_init; }
+    double get_initial_eps() const { return initial_eps_; }
+    double get_final_epsilon() const { return final_eps_; }
+    const TimeParameters& timeParameters() const { return time_params_; }
+    // what the last call did (SMPLX_ARA_* result, its own expansions, whether it continued the previous search)
+    const smplx_replan_stats& lastCallStats() const { return stats_; }
+
+private:
+    static clock::duration to_duration(double secs)
+    {
+        return std::chrono::duration_cast<clock::duration>(std::chrono::duration<double>(secs));
+    }
+    static double to_seconds(const clock::duration& d) { return std::chrono::duration<double>(d).count(); }
+
+    GpuPlanningContext* ctx_;
+    TimeParameters time_params_;
+    double initial_eps_ = 1.0, final_eps_ = 1.0, delta_eps_ = 1.0;   // arastar.cpp:58-73
+    bool allow_partial_ = false;
+    int from_scratch_ = 1;
+    smplx_replan_stats stats_ = smplx_replan_stats();
+    std::vector<int32_t> ids_;
 };
 
 // sbpl::motion::PlannerInterface::postProcessPath (smpl_ros/src/ros/planner_interface.cpp:2651-2697): ShortcutPath with

@@ -36,7 +36,12 @@ SYMBOLS = [
     "smplx_compact_totals_len", "smplx_compact_capacity",
     "smplx_grid_create_empty", "smplx_grid_add_boxes", "smplx_grid_add_points", "smplx_grid_remove_points", "smplx_grid_copy_d2",
     "smplx_search_counters", "smplx_grid_set_ref_counted", "smplx_grid_update_points", "smplx_grid_copy_counts", "smplx_grid_last_edit_cells",
+    "smplx_replan", "smplx_replan_multi",
 ]
+
+# smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
+TIME_EXPANSIONS, TIME_WALL = 0, 1
+ARA_SUCCESS, ARA_PARTIAL, ARA_TIMED_OUT, ARA_EXHAUSTED = 0, 1, 4, 5
 
 
 class Params(C.Structure):
@@ -58,6 +63,26 @@ class SearchStats(C.Structure):
                 ("expansions_init", C.c_int32), ("satisfied_eps", C.c_double), ("seconds", C.c_double),
                 ("gpu_succ_evals", C.c_int64), ("committed_succ_evals", C.c_int64), ("gpu_batches", C.c_int64),
                 ("cache_hits", C.c_int64), ("cache_misses", C.c_int64), ("grid_lookups", C.c_int64)]
+
+
+class TimeParams(C.Structure):
+    _fields_ = [("initial_eps", C.c_double), ("final_eps", C.c_double), ("delta_eps", C.c_double),
+                ("improve", C.c_int32), ("bounded", C.c_int32), ("type", C.c_int32),
+                ("max_expansions_init", C.c_int32), ("max_expansions", C.c_int32),
+                ("max_seconds_init", C.c_double), ("max_seconds", C.c_double),
+                ("allow_partial", C.c_int32), ("from_scratch", C.c_int32)]
+
+
+class ReplanStats(C.Structure):
+    _fields_ = [("s", SearchStats), ("result", C.c_int32), ("call_expansions", C.c_int32), ("resumed", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+def time_params(eps0, eps_final, eps_delta, improve=True, bounded=False, max_init=0, max_rep=0, wall=False,
+                seconds_init=0.0, seconds=0.0, allow_partial=False, from_scratch=False):
+    """smplx_time_params: expansion bounds (wall=False) or wall-clock budgets in seconds (wall=True)."""
+    return TimeParams(eps0, eps_final, eps_delta, int(improve), int(bounded), TIME_WALL if wall else TIME_EXPANSIONS,
+                      int(max_init), int(max_rep), float(seconds_init), float(seconds), int(allow_partial), int(from_scratch))
 
 
 _lib = None
@@ -520,6 +545,52 @@ class Space:
             d["expansion_log"] = log
             out.append(d)
         return out, wall.value
+
+    def _log(self):
+        n = lib().smplx_expansion_log_size(self.h)
+        log = np.zeros(n, np.int32)
+        if n:
+            _chk(lib().smplx_expansion_log(self.h, _p(log, _ip)))
+        return log
+
+    @staticmethod
+    def _replan_dict(S, ids):
+        d = {f: getattr(S.s, f) for f, _ in SearchStats._fields_}
+        d["path"] = ids[:S.s.path_len].copy()
+        d["result"], d["call_expansions"], d["resumed"] = S.result, S.call_expansions, S.resumed
+        return d
+
+    def replan(self, eps0, eps_final, eps_delta, improve=True, bounded=False, max_init=0, max_rep=0, wall=False,
+               seconds_init=0.0, seconds=0.0, allow_partial=False, from_scratch=False, cap=100000):
+        """Anytime ARA* (smplx_replan): continues the space's previous search where include/smpl_amd.h allows it.  The dict of
+        plan() plus result (ARA_*), call_expansions and resumed; expansion_log is the whole search's since it started."""
+        P = time_params(eps0, eps_final, eps_delta, improve, bounded, max_init, max_rep, wall, seconds_init, seconds,
+                        allow_partial, from_scratch)
+        S = ReplanStats()
+        ids = np.zeros(cap, np.int32)
+        _chk(lib().smplx_replan(self.h, C.byref(P), _p(ids, _ip), cap, C.byref(S)))
+        out = self._replan_dict(S, ids)
+        out["expansion_log"] = self._log()
+        return out
+
+    @staticmethod
+    def replan_multi(spaces, eps0, eps_final, eps_delta, improve=True, bounded=False, max_init=0, max_rep=0, wall=False,
+                     seconds_init=0.0, seconds=0.0, allow_partial=False, from_scratch=False, cap=4096, host_threads=1):
+        """smplx_replan_multi: replan() for independent queries on one GPU.  Returns (list of dicts, wall seconds)."""
+        nq = len(spaces)
+        P = time_params(eps0, eps_final, eps_delta, improve, bounded, max_init, max_rep, wall, seconds_init, seconds,
+                        allow_partial, from_scratch)
+        St = (ReplanStats * nq)()
+        H = (C.c_void_p * nq)(*[sp.h for sp in spaces])
+        ids = np.zeros((nq, cap), np.int32)
+        wall_s = C.c_double()
+        _chk(lib().smplx_replan_multi(H, nq, C.byref(P), _p(ids, _ip), cap, St, C.byref(wall_s), int(host_threads)))
+        out = []
+        for q, sp in enumerate(spaces):
+            d = Space._replan_dict(St[q], ids[q])
+            d["expansion_log"] = sp._log()
+            out.append(d)
+        return out, wall_s.value
 
     def post_process_path(self, path, shortcut=True, interpolate=True, upstream_limits=False):
         """PlannerInterface::postProcessPath (planner_interface.cpp:2651-2697).  Returns (path, stats)."""

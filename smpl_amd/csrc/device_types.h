@@ -216,7 +216,7 @@ struct SmplxSucc { int32_t id; int32_t cost_prim; };  // cost | primitive << 24 
 // why a launch of k_search came back
 enum { SMPLX_SS_RUNNING = 0,      // step budget of the launch used up: launch again
        SMPLX_SS_DONE = 1,         // replan finished (solved or not)
-       SMPLX_SS_GROW = 2,         // a buffer is too small for the next expansion: the host enlarges them and launches again
+       SMPLX_SS_GROW = 2,         // a buffer is too small for the next expansion or the path: the host enlarges them and launches again
        SMPLX_SS_ERROR = 3 };
 
 struct SmplxSearchDev {
@@ -245,6 +245,10 @@ struct SmplxSearchDev {
     uint32_t goal_f, pad1;
     int64_t committed_evals, gpu_evals, lookups;
     int64_t ticks[8];             // 100 MHz wall clock per phase of thread 0: select, pop, evaluate, commit, relax, reorder, idle
+    // ---- the call's budget and result form (smplx_time_params)
+    int32_t time_wall, allow_partial;   // time_wall: the budget counts wall-clock ticks, not expansions
+    int64_t t_start;              // wall clock of the call's start as the device sees it (0: not recorded yet)
+    int64_t budget_init, budget_rep;    // wall-clock ticks from t_start (max_seconds_init / max_seconds)
 };
 
 // hash of a discretised coordinate (host inserts and device lookups must agree; state ids never depend on it)

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <functional>
 #include <limits>
+#include <memory>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -191,6 +192,10 @@ struct smplx_model {
     smplx::HostModel hm;
 };
 
+namespace {
+struct Search;   // the host-driven ARA* (below)
+}
+
 struct DevSearch {
     unsigned char* arena = nullptr;      // one allocation carved into the buffers of SmplxSearchDev
     SmplxSearchDev* d_hdr = nullptr;
@@ -203,6 +208,7 @@ struct DevSearch {
     int call_number = 0, n_succ_kept = 0;
     int64_t grows = 0, searches = 0, ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int dup_pushes = 0;
+    int64_t evals_base[3] = {0, 0, 0};   // the header's committed / GPU evaluations and grid lookups when the call began
     int test_capacity = 0;               // test hook: first capacity in states
     bool test_no_helper = false;         // test hook: launch k_search without its helper wave
 };
@@ -314,6 +320,10 @@ struct smplx_space {
     PinBuf<unsigned short> p_stateq;
     std::vector<int32_t> eval_count;    // per id: evaluated (active) primitives, for committed_evals
     std::vector<int32_t> expansion_log;
+    // the search of the last smplx_plan / smplx_replan call, which a later smplx_replan may continue
+    int search_side = 0;                 // 0: none (or not resumable), 1: device-resident, 2: host-driven loop
+    int search_start = -1;               // its start id
+    std::shared_ptr<Search> host_search; // the host loop's search (OPEN, INCONS, search states) between calls
     // optional per-kernel timing of expand launches (bench.py roofline): 3 events per launch
     std::vector<hipEvent_t> prof_events;
     size_t prof_used = 0;
@@ -791,6 +801,7 @@ void reset_lattice(smplx_space* s)
     s->cache_off.clear(); s->cache_cnt.clear(); s->recs.clear(); s->rec_coord.clear(); s->rec_q.clear();
     s->done_off.clear(); s->done_cnt.clear(); s->done_succ.clear(); s->done_cost.clear(); s->done_prim.clear();
     s->ds.dev_states = 0; s->ds.host_behind = false; s->ds.log_on_device = false; s->ds.n_succ_kept = 0;
+    s->search_side = 0;                          // state ids are renumbered: no search continues across this
     s->ds.table_fresh = s->d_table != nullptr;   // (emptied below)
     s->eval_count.clear();
     s->hint.clear();
@@ -1970,6 +1981,9 @@ struct Search {
     int expand_count = 0, expand_count_init = 0;
     int start_id = -1, goal_id = 0;
     int error = SMPLX_OK;
+    bool wall = false, allow_partial = false;      // smplx_time_params: wall-clock budget, partial solutions
+    double max_sec_init = 0.0, max_sec_rep = 0.0;
+    std::chrono::steady_clock::time_point t_call;  // when the call began (the wall-clock budget's clock)
 
     bool less(int a, int b) const { return st[a].f < st[b].f; }
     bool heap_empty() const { return heap.size() == 1; }
@@ -2047,11 +2061,12 @@ struct Search {
         for (size_t i = 1; i < heap.size(); ++i) st[heap[i]].f = key(st[heap[i]]);
         make();
     }
-    bool timed_out(int elapsed) const
+    bool timed_out(int elapsed) const   // arastar.cpp:454-484
     {
         if (!bounded) return false;
-        if (satisfied_eps == std::numeric_limits<double>::infinity()) return elapsed >= max_init;
-        return elapsed >= max_rep;
+        const bool init = satisfied_eps == std::numeric_limits<double>::infinity();
+        if (wall) return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count() >= (init ? max_sec_init : max_sec_rep);
+        return elapsed >= (init ? max_init : max_rep);
     }
     void expand(int sid)   // arastar.cpp:531-568
     {
@@ -2131,10 +2146,18 @@ struct Search {
         return 5;
     }
 
-    // arastar.cpp:107-215 (always from scratch) as a resumable state machine: resume() runs until the search
-    // finishes (R_DONE) or a frontier batch is in flight (R_YIELD)
+    // arastar.cpp:107-215 as a resumable state machine: resume() runs until the search finishes (R_DONE) or a frontier
+    // batch is in flight (R_YIELD).  Phase 0 starts from scratch; continue_call() re-enters a finished search at phase 1
+    // for a later call (smplx_replan), which keeps OPEN, INCONS, the search states, iteration and epsilons
     int phase = 0, num = 0, err = 0, solved = 0, cost = 0;
     std::vector<int> solution;
+    void continue_call()
+    {
+        phase = 1; num = 0; err = 0; solved = 0; cost = 0;
+        solution.clear();
+        error = SMPLX_OK; miss_id = -1;
+        defer_issue = false; pause_after = 0;       // (set again by the multi-query drivers)
+    }
     int resume()
     {
         if (phase == 0) {
@@ -2181,10 +2204,14 @@ struct Search {
         }
         expand_count += num;
         phase = 3;
-        if (satisfied_eps == std::numeric_limits<double>::infinity()) { solved = 0; return R_DONE; }
-        for (int s = goal_id; s >= 0; s = st[s].bp) solution.push_back(s);
+        // arastar.cpp:199-214: the goal's chain once there is a solution, else with partial solutions the chain of OPEN's minimum
+        int from = -1;
+        if (satisfied_eps != std::numeric_limits<double>::infinity()) from = goal_id;
+        else if (allow_partial && !heap_empty()) from = heap[1];
+        if (from < 0) { solved = 0; return R_DONE; }
+        for (int s = from; s >= 0; s = st[s].bp) solution.push_back(s);
         std::reverse(solution.begin(), solution.end());
-        cost = (int)st[goal_id].g;
+        cost = (int)st[from].g;
         solved = 1;
         return R_DONE;
     }
@@ -2193,16 +2220,27 @@ struct Search {
     bool defer_issue = false;   // cross-query batching: the caller gathers the misses of many queries into one launch
 };
 
-void fill_search(Search& S, smplx_space* s, const smplx_search_params* p)
+// the parameters a call may change (a resumed call too: the reference's setters between calls)
+void set_call_params(Search& S, const smplx_time_params* p, std::chrono::steady_clock::time_point t_call)
 {
-    S.sp = s;
-    S.initial_eps = p->initial_eps;
     S.final_eps = std::max(p->final_eps, 1.0);   // ARAStar::setTargetEpsilon (arastar.h:112-114)
     S.delta_eps = p->delta_eps;
     S.improve = p->improve != 0;
     S.bounded = p->bounded != 0;
     S.max_init = p->max_expansions_init;
     S.max_rep = p->max_expansions;
+    S.wall = p->type == SMPLX_TIME_WALL;
+    S.max_sec_init = p->max_seconds_init;
+    S.max_sec_rep = p->max_seconds;
+    S.allow_partial = p->allow_partial != 0;
+    S.t_call = t_call;
+}
+
+void fill_search(Search& S, smplx_space* s, const smplx_time_params* p, std::chrono::steady_clock::time_point t_call)
+{
+    S.sp = s;
+    S.initial_eps = p->initial_eps;
+    set_call_params(S, p, t_call);
     S.start_id = s->start_id;
     S.goal_id = 0;
 }
@@ -2651,26 +2689,64 @@ static int read_counters(smplx_space* s, size_t cw, unsigned long long counters[
     return SMPLX_OK;
 }
 
-int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p, int32_t* path_ids, int cap,
-                     smplx_search_stats* stats, double* wall_seconds, int host_threads)
+// ARAStar::replan(const TimeParameters&, ...) for nq queries (smplx_replan_multi); t_call: when the call began
+static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32_t* path_ids, int cap,
+                        smplx_replan_stats* stats, double* wall_seconds, int host_threads, std::chrono::steady_clock::time_point t_call)
 {
-    if (!spaces || nq <= 0 || !p || !stats) return set_error(SMPLX_E_ARG, "bad argument");
-    std::vector<Search> S(nq);
-    std::vector<size_t> cw(nq);
-    struct Base { int64_t b, h, m, c, g; };
-    std::vector<Base> base(nq);
     for (int q = 0; q < nq; ++q) {
         smplx_space* s = spaces[q];
         if (!s) return set_error(SMPLX_E_ARG, "null space");
         if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
         if (s->start_id < 0) return set_error(SMPLX_E_STATE, "start not set");
         if (s->grid->epoch != s->grid_epoch) return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
-        if (int e = pull_lattice(s)) return e;
-        if (int e = pull_log(s)) return e;
-        fill_search(S[q], s, p);
+    }
+    // ---- the device-resident search (SURVEY row N2): one persistent workgroup per query, no host round trips.  Taken
+    // whenever the kernel fits the robot (search_host.h); SMPLX_SEARCH=host selects the host-driven loop below, which is
+    // also what serves an external SBPL planner through smplx_get_succs ----
+    bool device = true;
+    for (int q = 0; q < nq && device; ++q) device = search_on_device(spaces[q]);
+    {
+        const char* mode = getenv("SMPLX_SEARCH");
+        if (mode && !std::strcmp(mode, "device")) {
+            if (!device) return set_error(SMPLX_E_LIMIT, "SMPLX_SEARCH=device: the search kernel does not fit this robot / space");
+        } else if (nq == 1) {
+            // A lone query is a chain of dependent expansions: measured on MI355X (cfg 2) the host-driven loop with its
+            // speculative frontier batches expands 1.1e5 states/s, the single workgroup 3.9e4; the device-resident search
+            // wins where it has queries to run side by side (cfg 4: 4.5e6 against 1.5e6 states/s).
+            device = false;
+        }
+    }
+    // which queries continue the search their space holds (include/smpl_amd.h: same side, same start, no new goal, no
+    // failed call since)
+    const int side = device ? 1 : 2;
+    std::vector<char> resume(nq, 0);
+    for (int q = 0; q < nq; ++q) {
+        const smplx_space* s = spaces[q];
+        resume[q] = !p->from_scratch && s->search_side == side && s->search_start == s->start_id && (device || s->host_search);
+    }
+    std::vector<Search> S(device ? 0 : nq);
+    std::vector<size_t> cw(nq);
+    struct Base { int64_t b, h, m, c, g; };
+    std::vector<Base> base(nq);
+    for (int q = 0; q < nq; ++q) {
+        smplx_space* s = spaces[q];
+        s->search_side = 0;                      // until this call has succeeded
+        if (!resume[q]) {
+            if (int e = pull_lattice(s)) return e;
+            if (int e = pull_log(s)) return e;
+            s->expansion_log.clear();
+        }
+        if (!device) {
+            if (resume[q]) {
+                S[q] = std::move(*s->host_search);
+                set_call_params(S[q], p, t_call);
+                S[q].continue_call();
+            } else {
+                fill_search(S[q], s, p, t_call);
+            }
+        }
         s->adaptive_small = nq == 1;
         if (nq > 1) s->pipeline_left = 0;
-        s->expansion_log.clear();
         const int capB = s->params.batch_states > 0 ? s->params.batch_states : 4096;
         cw[q] = counter_words(capB, s->M);
         if (int e = s->b_counters.reserve(cw[q])) return e;
@@ -2692,31 +2768,17 @@ int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p,
                   std::memcmp(&a->hs.actions, &b->hs.actions, sizeof(SmplxActionsDev)) == 0 && a->fused_mode == b->fused_mode;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    // ---- the device-resident search (SURVEY row N2): one persistent workgroup per query, no host round trips.  Taken
-    // whenever the kernel fits the robot (search_host.h); SMPLX_SEARCH=host selects the host-driven loop below, which is
-    // also what serves an external SBPL planner through smplx_get_succs ----
-    {
-        bool device = true;
-        for (int q = 0; q < nq && device; ++q) device = search_on_device(spaces[q]);
-        const char* mode = getenv("SMPLX_SEARCH");
-        if (mode && !std::strcmp(mode, "device")) {
-            if (!device) return set_error(SMPLX_E_LIMIT, "SMPLX_SEARCH=device: the search kernel does not fit this robot / space");
-        } else if (nq == 1) {
-            // A lone query is a chain of dependent expansions: measured on MI355X (cfg 2) the host-driven loop with its
-            // speculative frontier batches expands 1.1e5 states/s, the single workgroup 3.9e4; the device-resident search
-            // wins where it has queries to run side by side (cfg 4: 4.5e6 against 1.5e6 states/s).
-            device = false;
+    if (device) {
+        if (grouped || nq == 1) {
+            if (int e = search_run(spaces, nq, p, resume.data(), path_ids, cap, stats, t_done.data(), t0, t_call)) return e;
+        } else {
+            for (int q = 0; q < nq; ++q)
+                if (int e = search_run(spaces + q, 1, p, resume.data() + q, path_ids ? path_ids + (size_t)q * cap : nullptr, cap, stats + q,
+                                       t_done.data() + q, t0, t_call)) return e;
         }
-        if (device) {
-            if (grouped || nq == 1) {
-                if (int e = search_run(spaces, nq, p, path_ids, cap, stats, t_done.data(), t0)) return e;
-            } else {
-                for (int q = 0; q < nq; ++q)
-                    if (int e = search_run(spaces + q, 1, p, path_ids ? path_ids + (size_t)q * cap : nullptr, cap, stats + q, t_done.data() + q, t0)) return e;
-            }
-            if (wall_seconds) *wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            return SMPLX_OK;
-        }
+        if (wall_seconds) *wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        for (int q = 0; q < nq; ++q) { spaces[q]->search_side = side; spaces[q]->search_start = spaces[q]->start_id; }
+        return SMPLX_OK;
     }
     if (grouped) {
         // host threads: each drives a contiguous slice of the queries with its own leading space / stream, so the
@@ -2787,8 +2849,9 @@ int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p,
         smplx_space* s = spaces[q];
         unsigned long long counters[4] = {0, 0, 0, 0};
         if (!grouped) { if (int e = read_counters(s, cw[q], counters)) return e; }
-        smplx_search_stats& st = stats[q];
-        std::memset(&st, 0, sizeof(st));
+        smplx_replan_stats& rs = stats[q];
+        std::memset(&rs, 0, sizeof(rs));
+        smplx_search_stats& st = rs.s;
         st.solved = S[q].solved;
         st.path_len = (int)S[q].solution.size();
         st.cost = S[q].cost;
@@ -2804,7 +2867,64 @@ int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p,
         st.cache_hits = (s->cache_hits - base[q].h) - st.cache_misses;   // expansions served without waiting for the GPU
         if (path_ids)
             for (int i = 0; i < (int)S[q].solution.size() && i < cap; ++i) path_ids[(size_t)q * cap + i] = S[q].solution[i];
+        rs.call_expansions = S[q].num;
+        rs.resumed = resume[q];
+        rs.result = S[q].err;
+        if (S[q].solved && S[q].satisfied_eps == std::numeric_limits<double>::infinity()) rs.result = SMPLX_ARA_PARTIAL;
+        else if (S[q].err == 0) rs.result = SMPLX_ARA_SUCCESS;
+        // the search stays with its space for a later call
+        if (!s->host_search) s->host_search = std::make_shared<Search>();
+        *s->host_search = std::move(S[q]);
+        s->search_side = side;
+        s->search_start = s->start_id;
     }
+    return SMPLX_OK;
+}
+
+int smplx_replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32_t* path_ids, int cap,
+                       smplx_replan_stats* stats, double* wall_seconds, int host_threads)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    if (!spaces || nq <= 0 || !p || !stats) return set_error(SMPLX_E_ARG, "bad argument");
+    if (path_ids && cap <= 0) return set_error(SMPLX_E_ARG, "path_ids needs cap > 0");
+    if (p->type != SMPLX_TIME_EXPANSIONS && p->type != SMPLX_TIME_WALL) return set_error(SMPLX_E_ARG, "unknown timing type");
+    if (!(p->max_seconds_init >= 0.0) || !(p->max_seconds >= 0.0)) return set_error(SMPLX_E_ARG, "time budgets must be >= 0");
+    if (!(p->initial_eps >= 1.0) || !(p->final_eps >= 0.0) || !(p->delta_eps > 0.0) || !std::isfinite(p->initial_eps))
+        return set_error(SMPLX_E_ARG, "epsilons: initial_eps >= 1 (finite), final_eps >= 0, delta_eps > 0");
+    for (int q = 0; q < nq; ++q)
+        for (int r = 0; r < q; ++r)
+            if (spaces[q] && spaces[q] == spaces[r]) return set_error(SMPLX_E_ARG, "a space appears twice");
+    const int e = replan_multi(spaces, nq, p, path_ids, cap, stats, wall_seconds, host_threads, t_call);
+    if (e != SMPLX_OK)
+        for (int q = 0; q < nq; ++q) if (spaces[q]) spaces[q]->search_side = 0;   // a failed call: the next one starts from scratch
+    return e;
+}
+
+int smplx_replan(smplx_space* s, const smplx_time_params* p, int32_t* path_ids, int cap, smplx_replan_stats* st)
+{
+    if (!s) return set_error(SMPLX_E_ARG, "null argument");
+    return smplx_replan_multi(&s, 1, p, path_ids, cap, st, nullptr, 1);
+}
+
+// ARAStar::replan from scratch under an expansion bound: smplx_replan_multi with from_scratch = 1
+int smplx_plan_multi(smplx_space** spaces, int nq, const smplx_search_params* p, int32_t* path_ids, int cap,
+                     smplx_search_stats* stats, double* wall_seconds, int host_threads)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    if (!spaces || nq <= 0 || !p || !stats) return set_error(SMPLX_E_ARG, "bad argument");
+    smplx_time_params tp;
+    std::memset(&tp, 0, sizeof(tp));
+    tp.initial_eps = p->initial_eps; tp.final_eps = p->final_eps; tp.delta_eps = p->delta_eps;
+    tp.improve = p->improve; tp.bounded = p->bounded; tp.type = SMPLX_TIME_EXPANSIONS;
+    tp.max_expansions_init = p->max_expansions_init; tp.max_expansions = p->max_expansions;
+    tp.from_scratch = 1;
+    std::vector<smplx_replan_stats> rs(nq);
+    const int e = replan_multi(spaces, nq, &tp, path_ids, cap, rs.data(), wall_seconds, host_threads, t_call);
+    if (e != SMPLX_OK) {
+        for (int q = 0; q < nq; ++q) if (spaces[q]) spaces[q]->search_side = 0;
+        return e;
+    }
+    for (int q = 0; q < nq; ++q) stats[q] = rs[q].s;
     return SMPLX_OK;
 }
 

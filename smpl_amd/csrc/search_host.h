@@ -240,16 +240,52 @@ int pull_log(smplx_space* s)
     return SMPLX_OK;
 }
 
-// set a query up for a replan from scratch on the device
-int search_begin(smplx_space* s, const smplx_search_params* p)
+// the budget of a call as the kernel checks it (smplx_time_params; ARAStar::timedOut, arastar.cpp:454-484)
+void search_set_budget(SmplxSearchDev& h, const smplx_time_params* p, double ticks_per_s)
+{
+    h.final_eps = std::max(p->final_eps, 1.0);   // ARAStar::setTargetEpsilon (arastar.h:112-114)
+    h.delta_eps = p->delta_eps;
+    h.improve = p->improve != 0; h.bounded = p->bounded != 0;
+    h.max_init = p->max_expansions_init; h.max_rep = p->max_expansions;
+    h.time_wall = p->type == SMPLX_TIME_WALL;
+    h.allow_partial = p->allow_partial != 0;
+    auto ticks = [&](double sec) { return (int64_t)std::min(std::max(sec, 0.0) * ticks_per_s, 4.0e18); };
+    h.budget_init = ticks(p->max_seconds_init);
+    h.budget_rep = ticks(p->max_seconds);
+    h.t_start = 0;                               // recorded by the call's first launch
+}
+
+// set a query up on the device: a replan from scratch (phase 0), or the continuation of the search it holds (phase 1:
+// OPEN, INCONS, the search states, iteration and epsilons stay; the call's counters and clock start again)
+int search_begin(smplx_space* s, const smplx_time_params* p, bool resume, double ticks_per_s)
 {
     DevSearch& D = s->ds;
+    if (resume) {
+        const int have = (int)s->h_of_id.size();
+        if (!D.host_behind && have > D.h.nstates) {
+            // states the host created since (smplx_get_succs of a state the search never expanded): the device takes them
+            SearchCaps c = D.caps;
+            c.states = std::max(c.states, have + 2 * s->M + 64);
+            c.heap = std::max(c.heap, c.states + c.states / 4);
+            if (int e = search_reserve(s, c)) return e;
+            if (int e = search_push_lattice(s)) return e;
+            if (int e = search_fill_table(s, D.h.nstates, have)) return e;
+            D.h.nstates = have;
+        }
+        SmplxSearchDev& h = D.h;
+        D.evals_base[0] = h.committed_evals; D.evals_base[1] = h.gpu_evals; D.evals_base[2] = h.lookups;
+        search_set_budget(h, p, ticks_per_s);
+        h.phase = 1; h.num = 0; h.err = 0; h.status = SMPLX_SS_RUNNING; h.n_path = 0; h.grow_what = 0;
+        HIP_TRY(hipMemcpyAsync(D.d_hdr, &h, sizeof(h), hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        return SMPLX_OK;
+    }
     if (int e = pull_lattice(s)) return e;       // a search the device ran earlier on this goal: one lattice
     const int have = (int)s->h_of_id.size();
     SearchCaps c;
     // a bounded search creates at most `bound * primitives` states; sized for ~10 per expansion so that the ordinary query
     // never has to stop for an enlargement (each costs its workgroup the rest of a launch)
-    const long long bound = p->bounded ? (long long)std::max(p->max_expansions_init, p->max_expansions) : -1;
+    const long long bound = p->bounded && p->type == SMPLX_TIME_EXPANSIONS ? (long long)std::max(p->max_expansions_init, p->max_expansions) : -1;
     const long long est_states = bound >= 0 ? std::min<long long>(bound * 10 + 4096, 1LL << 22) : 1LL << 18;
     c.states = (int)std::max<long long>(est_states, (long long)have + 2 * s->M + 64);
     if (D.test_capacity > 0) c.states = std::max(D.test_capacity, have + 2 * s->M + 64);
@@ -264,10 +300,7 @@ int search_begin(smplx_space* s, const smplx_search_params* p)
     if (int e = search_fill_table(s, have - (int)(s->pending_ins.size() / ((size_t)s->N + 2)), have)) return e;
     SmplxSearchDev& h = D.h;
     h.initial_eps = p->initial_eps;
-    h.final_eps = std::max(p->final_eps, 1.0);   // ARAStar::setTargetEpsilon (arastar.h:112-114)
-    h.delta_eps = p->delta_eps;
-    h.improve = p->improve != 0; h.bounded = p->bounded != 0;
-    h.max_init = p->max_expansions_init; h.max_rep = p->max_expansions;
+    search_set_budget(h, p, ticks_per_s);
     h.start_id = s->start_id;
     h.curr_eps = p->initial_eps; h.satisfied_eps = std::numeric_limits<double>::infinity();
     h.nstates = have;
@@ -277,6 +310,7 @@ int search_begin(smplx_space* s, const smplx_search_params* p)
     h.num = 0; h.expand_count = 0; h.expand_count_init = 0; h.err = 0; h.solved = 0; h.cost = 0; h.dup_pushes = 0; h.grow_what = 0;
     h.goal_f = 1000000000u;
     h.committed_evals = 0; h.gpu_evals = 0; h.lookups = 0;
+    D.evals_base[0] = D.evals_base[1] = D.evals_base[2] = 0;
     for (int k = 0; k < 8; ++k) h.ticks[k] = 0;
     HIP_TRY(hipMemcpyAsync(D.d_hdr, &h, sizeof(h), hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -298,6 +332,7 @@ int search_grow(smplx_space* s)
     if (h.n_incons + 2 * M > c.incons / 2) c.incons = c.incons * 2;
     if (h.n_log + 2 > c.log / 2) c.log = c.log * 2;
     if (h.n_succ + 2 * M > c.succ / 2) c.succ = c.succ * 2;
+    while (h.grow_what == 3 && c.path < h.n_path) c.path *= 2;        // the path (n_path: its length)
     const int nstates = h.nstates;
     if (int e = search_reserve(s, c)) return e;
     if (int e = search_fill_table(s, nstates, nstates)) return e;      // (only a fresh table needs anything)
@@ -308,14 +343,29 @@ int search_grow(smplx_space* s)
     return SMPLX_OK;
 }
 
-// ARAStar::replan for nq queries that share scene, robot and primitives: one workgroup each, launched until all are done
-int search_run(smplx_space** spaces, int nq, const smplx_search_params* p, int32_t* path_ids, int cap, smplx_search_stats* stats,
-               double* t_done, std::chrono::steady_clock::time_point t0)
+// device wall-clock ticks per second (hipDeviceAttributeWallClockRate: kHz)
+int search_tick_rate(int device, double* ticks_per_s)
+{
+    int khz = 0;
+    HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
+    if (khz <= 0) return set_error(SMPLX_E_HIP, "hipDeviceAttributeWallClockRate: no wall clock rate");
+    *ticks_per_s = 1000.0 * khz;
+    return SMPLX_OK;
+}
+
+// ARAStar::replan for nq queries that share scene, robot and primitives: one workgroup each, launched until all are done.
+// resume[q]: query q continues the search its space holds (search_begin).  t_done[q]: completion, seconds since t0; t_call:
+// when the call began (the wall-clock budget's clock)
+int search_run_launches(smplx_space** spaces, int nq, const smplx_time_params* p, const char* resume, int32_t* path_ids, int cap,
+                        smplx_replan_stats* stats, double* t_done, std::chrono::steady_clock::time_point t0,
+                        std::chrono::steady_clock::time_point t_call, bool& launched)
 {
     smplx_space* lead = spaces[0];
     HIP_TRY(hipSetDevice(lead->device));
+    double rate = 0.0;
+    if (int e = search_tick_rate(lead->device, &rate)) return e;
     for (int q = 0; q < nq; ++q)
-        if (int e = search_begin(spaces[q], p)) return e;
+        if (int e = search_begin(spaces[q], p, resume[q] != 0, rate)) return e;
     {
         std::vector<const SmplxSpaceDev*> tab(nq);
         for (int q = 0; q < nq; ++q) tab[q] = spaces[q]->d_space;
@@ -333,7 +383,11 @@ int search_run(smplx_space** spaces, int nq, const smplx_search_params* p, int32
     int64_t launches = 0;
     while (remaining > 0) {
         for (int q = 0; q < nq; ++q) status.p[q] = -1;
-        KLAUNCH(lead, K_SEARCH, k_search, dim3(nq), dim3(block), lds, lead->stream, (const SmplxSpaceDev* const*)lead->b_stab.p, max_steps, lh, status.p);
+        // host time of the call so far, in device ticks: a query's first launch of the call starts its budget clock that much earlier
+        const long long pre_ticks = (long long)(std::chrono::duration<double>(std::chrono::steady_clock::now() - t_call).count() * rate);
+        launched = true;
+        KLAUNCH(lead, K_SEARCH, k_search, dim3(nq), dim3(block), lds, lead->stream, (const SmplxSpaceDev* const*)lead->b_stab.p, max_steps, lh, status.p,
+                pre_ticks);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(lead->batch_done, lead->stream));
         if (int e = wait_event_polling(lead->batch_done)) return e;
@@ -360,8 +414,9 @@ int search_run(smplx_space** spaces, int nq, const smplx_search_params* p, int32
         DevSearch& D = s->ds;
         HIP_TRY(hipMemcpy(&D.h, D.d_hdr, sizeof(D.h), hipMemcpyDeviceToHost));
         const SmplxSearchDev& h = D.h;
-        smplx_search_stats& st = stats[q];
-        std::memset(&st, 0, sizeof(st));
+        smplx_replan_stats& rs = stats[q];
+        std::memset(&rs, 0, sizeof(rs));
+        smplx_search_stats& st = rs.s;
         st.solved = h.solved;
         st.path_len = h.n_path;
         st.cost = h.cost;
@@ -369,12 +424,19 @@ int search_run(smplx_space** spaces, int nq, const smplx_search_params* p, int32
         st.expansions_init = h.expand_count_init;
         st.satisfied_eps = h.satisfied_eps;
         st.seconds = t_done[q];
-        st.gpu_succ_evals = h.gpu_evals;
-        st.committed_succ_evals = h.committed_evals;
-        st.grid_lookups = h.lookups;
+        // this call's (the header counts since the search began)
+        const int64_t committed = h.committed_evals - D.evals_base[0], gpu = h.gpu_evals - D.evals_base[1];
+        st.gpu_succ_evals = gpu;
+        st.committed_succ_evals = committed;
+        st.grid_lookups = h.lookups - D.evals_base[2];
         st.gpu_batches = launches;
         st.cache_hits = h.expand_count;      // every expansion was served where the search runs
         st.cache_misses = 0;
+        rs.call_expansions = h.num;
+        rs.resumed = resume[q] != 0;
+        rs.result = h.err;
+        if (h.solved && h.satisfied_eps == std::numeric_limits<double>::infinity()) rs.result = SMPLX_ARA_PARTIAL;
+        else if (h.err == 0) rs.result = SMPLX_ARA_SUCCESS;
         if (path_ids && h.n_path > 0) {
             std::vector<int32_t> rev((size_t)h.n_path);
             HIP_TRY(hipMemcpy(rev.data(), h.path, sizeof(int32_t) * (size_t)h.n_path, hipMemcpyDeviceToHost));
@@ -387,9 +449,33 @@ int search_run(smplx_space** spaces, int nq, const smplx_search_params* p, int32
         D.searches += 1;
         for (int k = 0; k < 8; ++k) D.ticks[k] = h.ticks[k];
         D.dup_pushes = h.dup_pushes;
-        s->committed_evals += h.committed_evals;
-        s->gpu_evals += h.gpu_evals;
+        s->committed_evals += committed;
+        s->gpu_evals += gpu;
         s->gpu_batches += launches;
     }
     return SMPLX_OK;
+}
+
+// search_run_launches, and on an error after the first launch: the host's view of what the device holds made consistent
+// again (the lattice and log the workgroups wrote are pulled like a finished search's, and the next search continues the
+// committed lists and call numbers from the header), so that a later call can start from scratch
+int search_run(smplx_space** spaces, int nq, const smplx_time_params* p, const char* resume, int32_t* path_ids, int cap,
+               smplx_replan_stats* stats, double* t_done, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t_call)
+{
+    bool launched = false;
+    const int rc = search_run_launches(spaces, nq, p, resume, path_ids, cap, stats, t_done, t0, t_call, launched);
+    if (rc != SMPLX_OK && launched) {
+        const std::string msg = g_error;
+        for (int q = 0; q < nq; ++q) {
+            DevSearch& D = spaces[q]->ds;
+            if (hipStreamSynchronize(spaces[q]->stream) != hipSuccess) continue;
+            if (hipMemcpy(&D.h, D.d_hdr, sizeof(D.h), hipMemcpyDeviceToHost) != hipSuccess) continue;
+            D.call_number = D.h.call_number;
+            D.n_succ_kept = D.h.n_succ;
+            D.host_behind = true;
+            D.log_on_device = true;
+        }
+        g_error = msg;
+    }
+    return rc;
 }

@@ -26,6 +26,9 @@
 //
 // A launch runs at most `max_steps` expansions and then stores its state in the query's SmplxSearchDev, so that the host
 // sees progress, can stop a search, and can enlarge buffers (SMPLX_SS_GROW) between launches.
+// A wall-clock budget (smplx_time_params, SMPLX_TIME_WALL) is checked by the search wave itself, once per step where the
+// expansion bound is (ARAStar::timedOut, arastar.cpp:454-484): the first launch of a call records the call's start in the
+// header, moved back by the host time the call spent before that launch (`pre_ticks`); later launches of the call keep it.
 
 #define SMPLX_AC_LEVELS 16
 #define SMPLX_AC_SLOTS 128
@@ -443,7 +446,7 @@ __device__ __forceinline__ void search_book_table(const ModelLds* __restrict__ M
 }
 
 extern "C" __global__ void __launch_bounds__(512)
-k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, int* __restrict__ status_out)
+k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, int* __restrict__ status_out, long long pre_ticks)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     __shared__ ExpandLds Xb[2];                  // two evaluations can be open: the one being committed and the next, speculative one
@@ -586,6 +589,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
         long long ticks[8];
         for (int k = 0; k < 8; ++k) ticks[k] = P->ticks[k];
         long long tick = (long long)wall_clock64();
+        const long long t_start = P->t_start != 0 ? P->t_start : tick - pre_ticks;     // the call's start (wall-clock budget)
 #define SK_TICK(k) do { const long long now_ = (long long)wall_clock64(); ticks[k] += now_ - tick; tick = now_; } while (0)
 
         if (R.phase == 0) {
@@ -633,6 +637,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
             // =========================== what happens next (ARAStar::replan / improvePath) ===========================
             int action = -1, m = 0;
             while (action < 0) {
+                if (R.phase == 3) { action = SA_EXIT; break; }                          // finished; the path did not fit (below)
                 if (R.phase == 1) {
                     // arastar.cpp:169-186
                     if (!(R.satisfied_eps > P->final_eps)) { R.phase = 3; action = SA_EXIT; break; }
@@ -651,7 +656,11 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                 else {
                     top = hget(H, 1);
                     bool timed_out = false;
-                    if (P->bounded) timed_out = R.satisfied_eps == __builtin_inf() ? R.num >= P->max_init : R.num >= P->max_rep;
+                    if (P->bounded) {
+                        const bool init = R.satisfied_eps == __builtin_inf();
+                        if (P->time_wall) timed_out = tick - t_start >= (init ? P->budget_init : P->budget_rep);   // (tick: end of the last step)
+                        else timed_out = init ? R.num >= P->max_init : R.num >= P->max_rep;
+                    }
                     if (hent_f(top) >= R.goal_f || hent_id(top) == 0) err = 0;          // SUCCESS
                     else if (timed_out) err = 4;                                        // TIMED_OUT
                 }
@@ -1144,19 +1153,31 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
         if (lane == 0) {
             int solved = Ph.solved, cost = Ph.cost, n_path = Ph.n_path;
             if (R.phase == 3) {
-                // arastar.cpp:199-214
-                R.expand_count += R.num;
-                R.status = SMPLX_SS_DONE;
-                if (R.satisfied_eps == __builtin_inf()) {
-                    solved = 0; cost = 0; n_path = 0;
-                } else {
-                    int n = 0;
-                    for (int sid = 0; sid >= 0 && n < P->cap_path; sid = as_global(P->st)[sid].bp) as_global(P->path)[n++] = sid;
+                // arastar.cpp:199-214: the goal's chain once there is a solution (also after a time-out while improving), else
+                // with partial solutions allowed the chain of OPEN's minimum
+                int from = -1;
+                if (R.satisfied_eps != __builtin_inf()) from = 0;
+                else if (Ph.allow_partial && R.heap_size > 0) from = hent_id(hget(H, 1));
+                int n = 0;
+                if (from >= 0) for (int sid = from; sid >= 0; sid = as_global(P->st)[sid].bp) ++n;
+                if (n > P->cap_path) {
+                    // the path does not fit: the host enlarges the buffer and launches again (phase 3 leaves at once)
+                    R.status = SMPLX_SS_GROW; R.grow_what = 3;
                     n_path = n;
-                    cost = (int)as_global(P->st)[0].g;
-                    solved = 1;
+                } else {
+                    R.expand_count += R.num;
+                    R.status = SMPLX_SS_DONE;
+                    if (from < 0) {
+                        solved = 0; cost = 0; n_path = 0;
+                    } else {
+                        n = 0;
+                        for (int sid = from; sid >= 0; sid = as_global(P->st)[sid].bp) as_global(P->path)[n++] = sid;
+                        n_path = n;
+                        cost = (int)as_global(P->st)[from].g;
+                        solved = 1;
+                    }
+                    R.phase = 4;
                 }
-                R.phase = 4;
             }
             if (W.helper_gave_up) R.status = SMPLX_SS_ERROR;
             Pd->solved = solved; Pd->cost = cost; Pd->n_path = n_path;
@@ -1167,6 +1188,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
             Pd->dup_pushes = R.dup_pushes; Pd->goal_f = R.goal_f;
             Pd->status = R.status; Pd->grow_what = R.grow_what;
             Pd->committed_evals = R.committed_evals; Pd->gpu_evals = R.gpu_evals; Pd->lookups = R.lookups;
+            Pd->t_start = t_start;
             SK_TICK(6);
             ticks[7] += (spec_issued << 32) + spec_hits;            // rounds opened on a guess | guesses the next pop confirmed
             for (int k = 0; k < 8; ++k) Pd->ticks[k] = ticks[k];
