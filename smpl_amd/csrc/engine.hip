@@ -184,6 +184,24 @@ inline OutView carve_out(unsigned char* base, size_t BM, int N)
     return v;
 }
 
+// The buffers of one frontier batch (issue_frontier).  A space owns one for its own batches -- its b_q, b_work, b_cost,
+// b_lookups and b_out are also the scratch of the C-ABI expansion entry points -- and the asynchronous multi-query
+// driver keeps a ring of them.
+struct FrontierBatch {
+    DevBuf<double> b_q;                  // parents, then the staged K5 inserts (one upload)
+    DevBuf<unsigned short> b_stateq;     // cross-query batch: per-row query index
+    DevBuf<unsigned char> b_work, b_out;
+    DevBuf<int32_t> b_cost, b_lookups;
+    PinBuf<double> p_q;
+    PinBuf<unsigned short> p_stateq;
+    PinBuf<unsigned char> p_out;
+    std::vector<int32_t> ins_items;      // K5 inserts of the requesting spaces, tagged with their query slots
+    OutView dv, pv;                      // packed outputs: device block, pinned host twin
+    hipEvent_t done = nullptr;           // recorded behind the batch on its stream
+    bool zero_copy = false;              // the batch wrote its results straight into pv (single launch, no copies)
+    std::chrono::steady_clock::time_point t_issue;
+};
+
 }  // namespace
 
 #include "grid_handle.h"
@@ -247,9 +265,9 @@ struct smplx_space {
     int status = SMPLX_OK;            // sticky: first error of a call that has no way to report one (smplx_space_status)
     std::string status_msg;
     // scratch
-    DevBuf<double> b_q, b_q2, b_sq, b_xyz;
-    DevBuf<unsigned char> b_flags, b_work;
-    DevBuf<int32_t> b_coord, b_h, b_cost, b_lookups, b_way;
+    DevBuf<double> b_q2, b_sq, b_xyz;
+    DevBuf<unsigned char> b_flags;
+    DevBuf<int32_t> b_coord, b_h, b_way;
     smplx::KernelSet ks;       // per-robot kernels (specialize.h), generic ones with SMPLX_SPACE_GENERIC_KERNELS or SMPLX_SPECIALIZE=0
     std::string specialize_note;   // why the per-robot build is absent, if it is
     bool fused_mode = false;   // SMPLX_SPACE_FUSED: one thread per edge (reference lookup tallies)
@@ -257,10 +275,7 @@ struct smplx_space {
     int small_batch_max = 512;     // batches up to this many states take the single-launch kernel (SMPLX_SPACE_NO_SMALL_KERNEL disables)
     double small_latency_limit = 70e-6;   // SMPLX_SMALL_KERNEL=always lifts it, =never disables the single-launch kernel
     DevBuf<unsigned long long> b_counters;
-    PinBuf<double> p_q;
-    DevBuf<unsigned char> b_out;   // packed outputs of a planner batch (OutView)
-    PinBuf<unsigned char> p_out;
-    OutView dv, pv;                // views of the batch in flight: device block, pinned host twin
+    FrontierBatch batch;           // the space's own frontier batches (issued on `stream`)
     // lattice: commit-ordered state table (manip_lattice.cpp:1302-1354)
     std::vector<int32_t> coords;
     std::vector<double> qs;
@@ -296,18 +311,14 @@ struct smplx_space {
     double auto_w = 5.0;                // weight of h in the ranking (SMPLX_AUTO_SPECULATE_W)
     std::vector<uint32_t> g_est;        // per id, mirrored g (plain mode only)
     std::vector<std::pair<uint64_t, int32_t>> pool;   // binary min-heap of (rank key, id) of unevaluated states
-    // a frontier batch in flight (issued on `stream`, completion signalled by `batch_done`)
+    // the states of the frontier batch in flight
     std::vector<int32_t> inflight;
     std::vector<double> inflight_q;     // smplx_plan_multi: the joint values of `inflight`, staged by the query's worker
-    hipEvent_t batch_done = nullptr;
-    bool inflight_zero_copy = false;   // the batch in flight wrote its results straight into the pinned host buffers
     // Small batches: the single-launch kernel costs the host one launch (27 us issue-to-landing for the handful of states
     // a lone query misses on), the pipeline several launches and copies (~34 us).  Both give the same bytes.  The engine
     // watches the issue-to-landing time of the single-launch path and sits out 2000 batches on the pipeline path whenever
     // its moving average exceeds 70 us: a safety net from the time the kernel checked the snap-to-goal edge of every
     // state ungated (105 us per launch; fixed, see k_small_batch) -- it costs nothing when the kernel behaves.
-    std::chrono::steady_clock::time_point t_issue;
-    bool inflight_small = false;
     bool adaptive_small = false;  // only a lone query measures: with several queries per thread the landing time includes their turns
     double small_latency = 0.0;   // moving average, seconds
     int small_seen = 0, pipeline_left = 0;
@@ -316,8 +327,6 @@ struct smplx_space {
     int64_t gpu_batches = 0, cache_hits = 0, cache_misses = 0, committed_evals = 0, gpu_evals = 0;
     // cross-query batches (smplx_plan_multi): query table + per-state query index, owned by the leading space
     DevBuf<const SmplxSpaceDev*> b_stab;
-    DevBuf<unsigned short> b_stateq;
-    PinBuf<unsigned short> p_stateq;
     std::vector<int32_t> eval_count;    // per id: evaluated (active) primitives, for committed_evals
     std::vector<int32_t> expansion_log;
     // the search of the last smplx_plan / smplx_replan call, which a later smplx_replan may continue
@@ -372,11 +381,11 @@ bool host_check_limits(const SmplxModelDev& m, const double* q)
 int run_heuristic(smplx_space* s, const double* q, int n, int32_t* h, double* xyz)
 {
     const int N = s->N;
-    if (int e = s->b_q.reserve((size_t)n * N)) return e;
+    if (int e = s->batch.b_q.reserve((size_t)n * N)) return e;
     if (int e = s->b_h.reserve(n)) return e;
     if (int e = s->b_xyz.reserve((size_t)n * 3)) return e;
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, q, sizeof(double) * n * N, hipMemcpyHostToDevice, s->stream));
-    KLAUNCH(s, K_HEURISTIC, k_heuristic, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space, s->b_q.p, n,
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * N, hipMemcpyHostToDevice, s->stream));
+    KLAUNCH(s, K_HEURISTIC, k_heuristic, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space, s->batch.b_q.p, n,
                        s->b_h.p, s->b_xyz.p);
     HIP_TRY(hipGetLastError());
     if (h) HIP_TRY(hipMemcpyAsync(h, s->b_h.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
@@ -543,12 +552,9 @@ int table_alloc(smplx_space* s, size_t cap)
     return SMPLX_OK;
 }
 
-// load factor above 1/2: a table four times the size, every committed state re-inserted with the next batch
-int table_grow_if_needed(smplx_space* s)
+// a new, empty device table of `cap` slots; every committed state is queued for the next upload
+int table_realloc(smplx_space* s, size_t cap)
 {
-    if (!s->d_table || s->table_count * 2 <= s->table_cap) return SMPLX_OK;
-    size_t cap = s->table_cap;
-    while (s->table_count * 2 > cap) cap *= 4;
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (int e = table_alloc(s, cap)) return e;
     if (int e = upload_space(s)) return e;
@@ -561,6 +567,15 @@ int table_grow_if_needed(smplx_space* s)
         s->pending_ins.insert(s->pending_ins.end(), &s->coords[(size_t)id * s->N], &s->coords[(size_t)id * s->N] + s->N);
     }
     return SMPLX_OK;
+}
+
+// load factor above 1/2: a table four times the size, every committed state re-inserted with the next batch
+int table_grow_if_needed(smplx_space* s)
+{
+    if (!s->d_table || s->table_count * 2 <= s->table_cap) return SMPLX_OK;
+    size_t cap = s->table_cap;
+    while (s->table_count * 2 > cap) cap *= 4;
+    return table_realloc(s, cap);
 }
 
 // append the space's pending inserts to a staging array, tagged with its slot in the batch's query table
@@ -596,15 +611,7 @@ int table_ensure(smplx_space* s)
     size_t cap = (size_t)1 << 18;
     const size_t nstates = s->h_of_id.size();
     while (nstates * 2 > cap) cap *= 4;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (int e = table_alloc(s, cap)) return e;
-    if (int e = upload_space(s)) return e;
-    s->pending_ins.clear();
-    for (int id = 1; id < (int)nstates; ++id) {
-        s->pending_ins.push_back(0);
-        s->pending_ins.push_back(id);
-        s->pending_ins.insert(s->pending_ins.end(), &s->coords[(size_t)id * s->N], &s->coords[(size_t)id * s->N] + s->N);
-    }
+    if (int e = table_realloc(s, cap)) return e;
     s->table_count = nstates > 0 ? nstates - 1 : 0;
     return SMPLX_OK;
 }
@@ -648,80 +655,112 @@ struct ZeroCopy {
     int32_t* id = nullptr;
 };
 
-bool small_kernel_fits(const smplx_space* s, int B)
+// arguments of one expansion launch
+struct ExpandArgs {
+    const double* q = nullptr;                  // B x N parents (device)
+    int B = 0;
+    unsigned char* flags = nullptr;             // dense [B][M] outputs (device)
+    int32_t* coord = nullptr;
+    double* sq = nullptr;
+    int32_t* h = nullptr;
+    int32_t* cost = nullptr;
+    int32_t* lookups = nullptr;
+    void* work = nullptr;                       // expand_work_bytes(B, M)
+    unsigned long long* counters = nullptr;     // per-block tallies, or null
+    hipStream_t stream = nullptr;
+    const SmplxSpaceDev* const* stab = nullptr; // cross-query batch: query table ...
+    const unsigned short* state_q = nullptr;    // ... and per-row query index
+    const ZeroCopy* zero_copy = nullptr;        // pinned host parents and outputs (the zero-copy single launch)
+    const K5Out* k5 = nullptr;
+    bool force_pipeline = false;                // no single launch with copies
+};
+
+enum class ExpandPath { SmallZeroCopy, Small, Fused, Pipeline };
+
+inline size_t small_lds_bytes(const smplx_space* s)
 {
-    const int small_block = smplx_small_block(s->M);
-    const size_t small_lds = smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes, small_block);
-    return !s->fused_mode && B <= s->small_batch_max && small_block <= 512 && small_lds <= 150 * 1024 && s->work_list_items == 0 &&
-           s->pipeline_left == 0;
+    return smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes,
+                             smplx_small_block(s->M));
 }
 
-int launch_expand(smplx_space* s, const double* d_q, int B, unsigned char* d_flags, int32_t* d_coord, double* d_sq,
-                  int32_t* d_h, int32_t* d_cost, int32_t* d_lookups, void* d_work, unsigned long long* d_counters,
-                  hipStream_t stream, const SmplxSpaceDev* const* stab = nullptr, const unsigned short* state_q = nullptr,
-                  const ZeroCopy* zero_copy = nullptr, bool force_pipeline = false, const K5Out* k5 = nullptr)
+// The one rule for how an expansion launch runs.  What differs between callers comes in explicitly: zero_copy_max, the
+// largest batch whose parents and results may stay in pinned host memory (0: never), and force_pipeline, which rules out
+// the single launch with copies.  Armed profile events rule out the zero-copy launch, an event triple left for this
+// launch the single launch altogether; the fused mode takes precedence over the pipeline.
+ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool force_pipeline)
 {
-    ExpandWork k = carve_work(d_work, B, s->M);
-    int32_t* d_id = k5 ? k5->d_id : nullptr;
+    const bool small = !s->fused_mode && B <= s->small_batch_max && smplx_small_block(s->M) <= 512 &&
+                       small_lds_bytes(s) <= 150 * 1024 && s->work_list_items == 0 && s->pipeline_left == 0 &&
+                       s->prof_used + 3 > s->prof_events.size();
+    if (small && B <= zero_copy_max && s->prof_events.empty()) return ExpandPath::SmallZeroCopy;
+    if (small && !force_pipeline) return ExpandPath::Small;
+    return s->fused_mode ? ExpandPath::Fused : ExpandPath::Pipeline;
+}
+
+int launch_expand(smplx_space* s, const ExpandArgs& a)
+{
+    const int B = a.B;
+    ExpandWork k = carve_work(a.work, B, s->M);
+    int32_t* d_id = a.k5 ? a.k5->d_id : nullptr;
     SmplxCompactDev cmp;
     std::memset(&cmp, 0, sizeof(cmp));
-    if (k5 && k5->cmp) cmp = *k5->cmp;
-    if (cmp.rec_a) force_pipeline = true;   // the compact stream is produced by k_pipe_finish
-    const int32_t* ins_items = k5 && s->d_table ? k5->items : nullptr;
-    const int n_ins = ins_items ? k5->n_items : 0;
+    if (a.k5 && a.k5->cmp) cmp = *a.k5->cmp;
+    // (the compact stream is produced by k_pipe_finish)
+    const ExpandPath path = expand_path(s, B, a.zero_copy ? B : 0, a.force_pipeline || cmp.rec_a);
+    const int32_t* ins_items = a.k5 && s->d_table ? a.k5->items : nullptr;
+    const int n_ins = ins_items ? a.k5->n_items : 0;
     if (s->work_list_items > 0) k.capacity = s->work_list_items;   // test hook: almost every edge overflows into the deferred pass
     hipEvent_t* ev = nullptr;
     if (s->prof_used + 3 <= s->prof_events.size()) { ev = &s->prof_events[s->prof_used]; s->prof_used += 3; }
     const int bs = blocks_for(B, SMPLX_BLOCK);
     const int be = blocks_for((long long)B * s->M, SMPLX_BLOCK);
     const int64_t* norefs = nullptr;
-    const int small_block = smplx_small_block(s->M);
-    const size_t small_lds = smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes, small_block);
-    if (!force_pipeline && !s->fused_mode && !ev && B <= s->small_batch_max && small_block <= 512 && small_lds <= 150 * 1024 &&
-        s->work_list_items == 0 && s->pipeline_left == 0) {
+    if (path == ExpandPath::SmallZeroCopy || path == ExpandPath::Small) {
         ++s->small_launches;
         // a handful of states: ONE launch, all FK chains side by side (kernels.hip k_small_batch)
         // zero_copy: parents are read from, and results also written to, that space's pinned host buffers
-        const double* qsrc = zero_copy ? zero_copy->q : d_q;
-        KLAUNCH(s, K_SMALL_BATCH, k_small_batch, dim3(B + blocks_for(n_ins, small_block)), dim3(small_block), small_lds, stream, s->d_space, qsrc, norefs, B, k.goal_dist,
-                           k.state_bad, k.state_lookups, d_flags, d_coord, d_sq, d_h, d_cost, d_lookups, stab, state_q,
-                           zero_copy ? zero_copy->flags : (unsigned char*)nullptr, zero_copy ? zero_copy->coord : (int32_t*)nullptr,
-                           zero_copy ? zero_copy->sq : (double*)nullptr, zero_copy ? zero_copy->h : (int32_t*)nullptr, d_id,
-                           zero_copy ? zero_copy->id : (int32_t*)nullptr, ins_items, n_ins);
-    } else if (s->fused_mode) {
+        const ZeroCopy* zc = path == ExpandPath::SmallZeroCopy ? a.zero_copy : nullptr;
+        const int small_block = smplx_small_block(s->M);
+        KLAUNCH(s, K_SMALL_BATCH, k_small_batch, dim3(B + blocks_for(n_ins, small_block)), dim3(small_block), small_lds_bytes(s), a.stream, s->d_space,
+                           zc ? zc->q : a.q, norefs, B, k.goal_dist,
+                           k.state_bad, k.state_lookups, a.flags, a.coord, a.sq, a.h, a.cost, a.lookups, a.stab, a.state_q,
+                           zc ? zc->flags : (unsigned char*)nullptr, zc ? zc->coord : (int32_t*)nullptr,
+                           zc ? zc->sq : (double*)nullptr, zc ? zc->h : (int32_t*)nullptr, d_id,
+                           zc ? zc->id : (int32_t*)nullptr, ins_items, n_ins);
+    } else if (path == ExpandPath::Fused) {
         // one thread walks a whole edge: exact reference early-exit order (and lookup tallies)
-        if (d_id) HIP_TRY(hipMemsetAsync(d_id, 0xFF, sizeof(int32_t) * (size_t)B * s->M, stream));   // fused mode: no table lookups
+        if (d_id) HIP_TRY(hipMemsetAsync(d_id, 0xFF, sizeof(int32_t) * (size_t)B * s->M, a.stream));   // fused mode: no table lookups
         if (n_ins > 0) {
-            hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, stream, s->d_space, stab, ins_items, n_ins, s->N);
+            hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, a.stream, s->d_space, a.stab, ins_items, n_ins, s->N);
         }
-        if (ev) (void)hipEventRecord(ev[0], stream);
-        KLAUNCH(s, K_STATE_PREP, k_state_prep, dim3(bs), dim3(SMPLX_BLOCK), s->lds_bytes, stream, s->d_space, d_q, norefs, B,
-                           k.goal_dist, k.state_bad, k.state_lookups, stab, state_q);
-        if (ev) (void)hipEventRecord(ev[1], stream);
-        KLAUNCH(s, K_EXPAND, k_expand, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, stream, s->d_space, d_q, norefs, B,
-                           k.goal_dist, k.state_bad, k.state_lookups, d_flags, d_coord, d_sq, d_h, d_cost, d_lookups,
-                           d_counters, (const int*)nullptr, stab, state_q);
-        if (ev) (void)hipEventRecord(ev[2], stream);
+        if (ev) (void)hipEventRecord(ev[0], a.stream);
+        KLAUNCH(s, K_STATE_PREP, k_state_prep, dim3(bs), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+                           k.goal_dist, k.state_bad, k.state_lookups, a.stab, a.state_q);
+        if (ev) (void)hipEventRecord(ev[1], a.stream);
+        KLAUNCH(s, K_EXPAND, k_expand, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+                           k.goal_dist, k.state_bad, k.state_lookups, a.flags, a.coord, a.sq, a.h, a.cost, a.lookups,
+                           a.counters, (const int*)nullptr, a.stab, a.state_q);
+        if (ev) (void)hipEventRecord(ev[2], a.stream);
     } else {
         const size_t lm = s->blob_bytes;
         ++s->pipe_launches;
-        KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, stream, s->d_space, d_q, norefs, B,
-                           k.goal_dist, k.work_count, stab, state_q, cmp.totals, ins_items, n_ins);
-        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be), dim3(SMPLX_BLOCK), lm, stream, s->d_space, d_q, norefs, B,
-                           k.goal_dist, d_flags, d_sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
-                           k.work, k.work_count, k.capacity, stab, state_q);
-        if (ev) (void)hipEventRecord(ev[0], stream);
+        KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+                           k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins);
+        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+                           k.goal_dist, a.flags, a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
+                           k.work, k.work_count, k.capacity, a.stab, a.state_q);
+        if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
         const int bc = blocks_for((long long)B + (long long)B * s->M * 3, SMPLX_BLOCK);
-        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc), dim3(SMPLX_BLOCK), s->lds_bytes_valid, stream, s->d_space, d_q, norefs, B,
-                           d_sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
+        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, norefs, B,
+                           a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
                            k.capacity);
-        if (ev) (void)hipEventRecord(ev[1], stream);
+        if (ev) (void)hipEventRecord(ev[1], a.stream);
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
-        KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, stream, s->d_space, d_q, norefs, B,
-                           k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, d_flags, d_coord, d_sq, d_h,
-                           d_cost, d_lookups, d_counters, k.goal_dist, stab, state_q, d_id, cmp);
-        if (ev) (void)hipEventRecord(ev[2], stream);
+        KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+                           k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, a.flags, a.coord, a.sq, a.h,
+                           a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp);
+        if (ev) (void)hipEventRecord(ev[2], a.stream);
     }
     HIP_TRY(hipGetLastError());
     return SMPLX_OK;
@@ -731,14 +770,14 @@ int reserve_expand(smplx_space* s, int B)
 {
     const size_t BM = (size_t)B * s->M;
     int e;
-    if ((e = s->b_q.reserve((size_t)B * s->N))) return e;
-    if ((e = s->b_work.reserve(expand_work_bytes(B, s->M)))) return e;
+    if ((e = s->batch.b_q.reserve((size_t)B * s->N))) return e;
+    if ((e = s->batch.b_work.reserve(expand_work_bytes(B, s->M)))) return e;
     if ((e = s->b_flags.reserve(BM))) return e;
     if ((e = s->b_coord.reserve(BM * s->N))) return e;
     if ((e = s->b_sq.reserve(BM * s->N))) return e;
     if ((e = s->b_h.reserve(BM))) return e;
-    if ((e = s->b_cost.reserve(BM))) return e;
-    if ((e = s->b_lookups.reserve(BM))) return e;
+    if ((e = s->batch.b_cost.reserve(BM))) return e;
+    if ((e = s->batch.b_lookups.reserve(BM))) return e;
     if ((e = s->b_counters.reserve(counter_words(B, s->M)))) return e;
     return SMPLX_OK;
 }
@@ -871,75 +910,98 @@ int wait_event_polling(hipEvent_t ev)
     }
 }
 
-// small batches skip the DMA copies: the kernel reads the parents from, and writes the results to, pinned host memory
-bool takes_small_kernel(const smplx_space* s, int B)
+// How a driver issues its frontier batches.  Each keeps the launch choice it was measured with (expand_path).
+struct BatchMode {
+    int zero_copy_max;      // largest batch that may take the zero-copy single launch (0: never)
+    bool force_pipeline;    // no single launch with copies
+    bool staged_parents;    // the parents' joint values wait in each space's inflight_q (staged by its worker), else in qs
+};
+
+// Enqueue one frontier batch on `stream` and return without waiting: the `inflight` states of spaces[q] for every q in
+// slots[0..nslots), rows in that order.  q is also the space's slot in the query table `stab` of a cross-query batch
+// (null: the batch of `lead` alone).  Parents and the spaces' pending K5 inserts go up in one upload (or stay in pinned
+// memory for the zero-copy launch), the outputs come back into fb.pv, and fb.done is recorded behind them.
+int issue_frontier(smplx_space* lead, FrontierBatch& fb, smplx_space* const* spaces, const int* slots, int nslots,
+                   const SmplxSpaceDev* const* stab, hipStream_t stream, const BatchMode& mode)
 {
-    const int small_block = smplx_small_block(s->M);
-    const size_t small_lds = smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes, small_block);
-    return !s->fused_mode && s->prof_events.empty() && B <= s->small_batch_max && small_block <= 512 && small_lds <= 150 * 1024 &&
-           s->work_list_items == 0 && s->pipeline_left == 0;
+    const int N = lead->N, M = lead->M;
+    size_t total = 0;
+    fb.ins_items.clear();
+    for (int i = 0; i < nslots; ++i) {
+        smplx_space* sq = spaces[slots[i]];
+        total += sq->inflight.size();
+        // K5: the states committed since the space's last batch join its device table at the head of this batch's first
+        // kernel (a requesting space is not being touched by its search)
+        if (int e = table_grow_if_needed(sq)) return e;
+        table_take_pending(sq, slots[i], fb.ins_items);
+    }
+    const int B = (int)total;
+    const size_t BM = total * M;
+    const size_t staged = total * N + (fb.ins_items.size() + 1) / 2;   // doubles: the parents, then the inserts
+    const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
+    int e;
+    if ((e = fb.b_q.reserve(staged)) || (e = fb.p_q.reserve(staged)) || (e = fb.b_work.reserve(expand_work_bytes(B, M))) ||
+        (e = fb.b_cost.reserve(BM)) || (e = fb.b_lookups.reserve(BM)) || (e = fb.b_out.reserve(out_bytes)) ||
+        (e = fb.p_out.reserve(out_bytes)))
+        return e;
+    if (stab && ((e = fb.b_stateq.reserve(total)) || (e = fb.p_stateq.reserve(total)))) return e;
+    // a cross-query batch keeps no tallies: they would mix the queries
+    if (!stab && (e = lead->b_counters.reserve(counter_words(B, M)))) return e;
+    fb.dv = carve_out(fb.b_out.p, BM, N);
+    fb.pv = carve_out(fb.p_out.p, BM, N);
+    size_t row = 0;
+    for (int i = 0; i < nslots; ++i) {
+        const smplx_space* sq = spaces[slots[i]];
+        const size_t nrows = sq->inflight.size();
+        if (mode.staged_parents) std::memcpy(&fb.p_q.p[row * N], sq->inflight_q.data(), sizeof(double) * N * nrows);
+        else
+            for (size_t k = 0; k < nrows; ++k) std::memcpy(&fb.p_q.p[(row + k) * N], &sq->qs[(size_t)sq->inflight[k] * N], sizeof(double) * N);
+        if (stab) for (size_t k = 0; k < nrows; ++k) fb.p_stateq.p[row + k] = (unsigned short)slots[i];
+        row += nrows;
+    }
+    const size_t item_doubles = stage_items(fb.p_q, total * N, fb.ins_items);
+    fb.t_issue = std::chrono::steady_clock::now();
+    fb.zero_copy = expand_path(lead, B, mode.zero_copy_max, mode.force_pipeline) == ExpandPath::SmallZeroCopy;
+    K5Out k5;
+    k5.d_id = fb.dv.id;
+    k5.n_items = (int)(fb.ins_items.size() / ((size_t)N + 2));
+    ExpandArgs a;
+    a.q = fb.b_q.p; a.B = B;
+    a.flags = fb.dv.flags; a.coord = fb.dv.coord; a.sq = fb.dv.sq; a.h = fb.dv.h; a.cost = fb.b_cost.p; a.lookups = fb.b_lookups.p;
+    a.work = fb.b_work.p;
+    a.counters = stab ? nullptr : lead->b_counters.p;
+    a.stream = stream;
+    a.stab = stab;
+    a.k5 = &k5;
+    a.force_pipeline = mode.force_pipeline;
+    ZeroCopy zc;
+    if (fb.zero_copy) {
+        // one launch, no copies: parents, query indices, inserts and results live in pinned host memory
+        zc.q = fb.p_q.p; zc.flags = fb.pv.flags; zc.coord = fb.pv.coord; zc.sq = fb.pv.sq; zc.h = fb.pv.h; zc.id = fb.pv.id;
+        a.zero_copy = &zc;
+        a.state_q = stab ? fb.p_stateq.p : nullptr;
+        k5.items = (const int32_t*)(fb.p_q.p + total * N);
+    } else {
+        HIP_TRY(hipMemcpyAsync(fb.b_q.p, fb.p_q.p, sizeof(double) * (total * N + item_doubles), hipMemcpyHostToDevice, stream));
+        if (stab) HIP_TRY(hipMemcpyAsync(fb.b_stateq.p, fb.p_stateq.p, sizeof(unsigned short) * total, hipMemcpyHostToDevice, stream));
+        a.state_q = stab ? fb.b_stateq.p : nullptr;
+        k5.items = (const int32_t*)(fb.b_q.p + total * N);
+    }
+    if ((e = launch_expand(lead, a))) return e;
+    if (!fb.zero_copy)   // one copy for all five outputs
+        HIP_TRY(hipMemcpyAsync(fb.p_out.p, fb.b_out.p, out_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(fb.done, stream));
+    ++lead->gpu_batches;
+    return SMPLX_OK;
 }
 
-// enqueue one frontier batch (state `id` plus hinted frontier states) on the space's stream: upload, the
-// expansion pipeline, download, completion event.  Returns without waiting.
+// enqueue one frontier batch of the space's own (state `id` plus hinted frontier states) on its stream
 int issue_batch(smplx_space* s, int id)
 {
-    const int N = s->N, M = s->M;
-    const int cap = s->params.batch_states > 0 ? s->params.batch_states : 4096;
-    select_batch(s, id, cap);
-    std::vector<int32_t>& batch = s->inflight;
-    const int B = (int)batch.size();
-    const size_t BM = (size_t)B * M;
-    if (int e = reserve_expand(s, B)) return e;
-    int e;
-    if ((e = s->p_q.reserve((size_t)B * N))) return e;
-    const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
-    if ((e = s->b_out.reserve(out_bytes))) return e;
-    if ((e = s->p_out.reserve(out_bytes))) return e;
-    s->dv = carve_out(s->b_out.p, BM, N);
-    s->pv = carve_out(s->p_out.p, BM, N);
-    auto pack_parents = [&]() {
-        for (int i = 0; i < B; ++i) std::memcpy(&s->p_q.p[(size_t)i * N], &s->qs[(size_t)batch[i] * N], sizeof(double) * N);
-    };
-    pack_parents();
-    if (s->pipeline_left > 0 && B <= s->small_batch_max) --s->pipeline_left;   // sitting out on the pipeline path (see smplx_space)
-    s->inflight_small = takes_small_kernel(s, B);
-    s->inflight_zero_copy = s->inflight_small;
-    s->t_issue = std::chrono::steady_clock::now();
-    // K5: the states committed since the last batch join the device table at the head of this batch's first kernel;
-    // their (id, coordinate) triples ride in the parents' upload
-    K5Out k5;
-    k5.d_id = s->dv.id;
-    size_t item_doubles = 0;
-    if (s->d_table) {
-        if ((e = table_grow_if_needed(s))) return e;
-        if (!s->pending_ins.empty()) {
-            if ((e = s->p_q.reserve((size_t)B * N + s->pending_ins.size() / 2 + 1))) return e;
-            if ((e = s->b_q.reserve((size_t)B * N + s->pending_ins.size() / 2 + 1))) return e;
-            pack_parents();   // the buffer may have moved
-            k5.n_items = (int)(s->pending_ins.size() / ((size_t)N + 2));
-            item_doubles = stage_items(s->p_q, (size_t)B * N, s->pending_ins);
-            s->pending_ins.clear();
-        }
-    }
-    if (s->inflight_zero_copy) {
-        k5.items = (const int32_t*)(s->p_q.p + (size_t)B * N);
-        ZeroCopy zc;
-        zc.q = s->p_q.p; zc.flags = s->pv.flags; zc.coord = s->pv.coord; zc.sq = s->pv.sq; zc.h = s->pv.h; zc.id = s->pv.id;
-        if ((e = launch_expand(s, s->b_q.p, B, s->dv.flags, s->dv.coord, s->dv.sq, s->dv.h, s->b_cost.p, s->b_lookups.p,
-                               s->b_work.p, s->b_counters.p, s->stream, nullptr, nullptr, &zc, false, &k5))) return e;
-        HIP_TRY(hipEventRecord(s->batch_done, s->stream));
-        ++s->gpu_batches;
-        return SMPLX_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, s->p_q.p, sizeof(double) * ((size_t)B * N + item_doubles), hipMemcpyHostToDevice, s->stream));
-    k5.items = (const int32_t*)(s->b_q.p + (size_t)B * N);
-    if ((e = launch_expand(s, s->b_q.p, B, s->dv.flags, s->dv.coord, s->dv.sq, s->dv.h, s->b_cost.p, s->b_lookups.p,
-                           s->b_work.p, s->b_counters.p, s->stream, nullptr, nullptr, nullptr, false, &k5))) return e;
-    HIP_TRY(hipMemcpyAsync(s->p_out.p, s->b_out.p, out_bytes, hipMemcpyDeviceToHost, s->stream));   // one copy for all five outputs
-    HIP_TRY(hipEventRecord(s->batch_done, s->stream));
-    ++s->gpu_batches;
-    return SMPLX_OK;
+    select_batch(s, id, s->params.batch_states > 0 ? s->params.batch_states : 4096);
+    if (s->pipeline_left > 0 && (int)s->inflight.size() <= s->small_batch_max) --s->pipeline_left;   // sitting out on the pipeline path (see smplx_space)
+    const int self = 0;
+    return issue_frontier(s, s->batch, &s, &self, 1, nullptr, s->stream, BatchMode{s->small_batch_max, false, false});
 }
 
 // one dense output row -> cached successor records (appended to recs); returns the record count
@@ -977,26 +1039,23 @@ int ingest_row(smplx_space* s, const OutView& pv, size_t row, int* evals_out)
     return cnt;
 }
 
-// the batch in flight has completed: turn its dense outputs into cached successor records
-int collect_batch(smplx_space* s, const smplx_space* src = nullptr, size_t first = 0, const OutView* view = nullptr)
+// a frontier batch has landed: the space's rows of it, from row `first` on, become cached successor records
+int collect_batch(smplx_space* s, const FrontierBatch& fb, size_t first)
 {
-    if (!src) src = s;   // a cross-query batch lands in the leading space's buffers (or in `view`), at row `first`
-    const OutView& pv = view ? *view : src->pv;
     const std::vector<int32_t>& batch = s->inflight;
     const int B = (int)batch.size();
-    if (src == s && s->inflight_small && s->adaptive_small && B <= 16) {
+    if (&fb == &s->batch && fb.zero_copy && s->adaptive_small && B <= 16) {
         // issue-to-landing time of the single-launch path (the search thread has been polling since the issue); only the
         // handful-of-states batches are watched: a batch of hundreds of states legitimately takes longer
-        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - s->t_issue).count();
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - fb.t_issue).count();
         s->small_latency = s->small_seen == 0 ? dt : 0.8 * s->small_latency + 0.2 * dt;
         if (++s->small_seen >= 16 && s->small_latency > s->small_latency_limit) { s->pipeline_left = 2000; s->small_seen = 0; }
     }
-    if (src == s) { s->inflight_small = false; s->inflight_zero_copy = false; }
     for (int i = 0; i < B; ++i) {
         const int sid = batch[i];
         s->cache_off[sid] = (int64_t)s->recs.size();
         int evals = 0;
-        s->cache_cnt[sid] = ingest_row(s, pv, first + (size_t)i, &evals);
+        s->cache_cnt[sid] = ingest_row(s, fb.pv, first + (size_t)i, &evals);
         s->eval_count[sid] = evals;
         s->gpu_evals += evals;
     }
@@ -1008,8 +1067,8 @@ int run_batch(smplx_space* s, int id)
 {
     s->adaptive_small = true;   // synchronous: the landing time is the GPU's
     if (int e = issue_batch(s, id)) return e;
-    if (int e = wait_event_polling(s->batch_done)) return e;
-    return collect_batch(s);
+    if (int e = wait_event_polling(s->batch.done)) return e;
+    return collect_batch(s, s->batch, 0);
 }
 
 // GetSuccs (manip_lattice.cpp:219-313): ids are assigned here, in the caller's sequential order
@@ -1303,7 +1362,7 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
     s->lds_bytes = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
     s->lds_bytes_valid = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->ks.specialized ? 0 : s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
     if (s->lds_bytes > 160 * 1024) { smplx_space_destroy(s); return set_error(SMPLX_E_LIMIT, "model needs more LDS per block than a CU has (160 KB)"); }
-    if ((e = hipEventCreateWithFlags(&s->batch_done, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
+    if ((e = hipEventCreateWithFlags(&s->batch.done, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipMalloc((void**)&s->d_space, sizeof(SmplxSpaceDev))) != hipSuccess) return bail(e, "hipMalloc space");
     const int dx = grid->n[0] + 2, dy = grid->n[1] + 2, dz = grid->n[2] + 2;
     s->bfs_total = (int64_t)dx * dy * dz;
@@ -1347,7 +1406,7 @@ void smplx_space_destroy(smplx_space* s)
     if (!s) return;
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     for (hipEvent_t e : s->prof_events) (void)hipEventDestroy(e);
-    if (s->batch_done) (void)hipEventDestroy(s->batch_done);
+    if (s->batch.done) (void)hipEventDestroy(s->batch.done);
     if (s->d_space) (void)hipFree(s->d_space);
     if (s->d_bfs) (void)hipFree(s->d_bfs);
     if (s->d_queue) (void)hipFree(s->d_queue);
@@ -1451,15 +1510,15 @@ int smplx_cc_state_valid_batch(smplx_space* s, const double* q, int n, uint8_t* 
     if (n == 0) return SMPLX_OK;
     if (!sane_values(q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
     int e;
-    if ((e = s->b_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->batch.b_q.reserve((size_t)n * s->N))) return e;
     if ((e = s->b_flags.reserve(n))) return e;
-    if ((e = s->b_lookups.reserve(n))) return e;
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    if ((e = s->batch.b_lookups.reserve(n))) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
     KLAUNCH(s, K_STATE_VALID, k_state_valid, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes_valid, s->stream, s->d_space,
-                       s->b_q.p, n, s->b_flags.p, s->b_lookups.p);
+                       s->batch.b_q.p, n, s->b_flags.p, s->batch.b_lookups.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(valid, s->b_flags.p, n, hipMemcpyDeviceToHost, s->stream));
-    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->b_lookups.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->batch.b_lookups.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return SMPLX_OK;
 }
@@ -1481,18 +1540,18 @@ int smplx_cc_edge_valid_batch(smplx_space* s, const double* a, const double* b, 
     if (!sane_values(a, (size_t)n * s->N) || !sane_values(b, (size_t)n * s->N))
         return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
     int e;
-    if ((e = s->b_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->batch.b_q.reserve((size_t)n * s->N))) return e;
     if ((e = s->b_q2.reserve((size_t)n * s->N))) return e;
     if ((e = s->b_flags.reserve(n))) return e;
-    if ((e = s->b_lookups.reserve(n))) return e;
+    if ((e = s->batch.b_lookups.reserve(n))) return e;
     if ((e = s->b_way.reserve(n))) return e;
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, a, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, a, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(s->b_q2.p, b, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
     KLAUNCH(s, K_EDGE_VALID, k_edge_valid, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes_valid, s->stream, s->d_space,
-                       s->b_q.p, s->b_q2.p, n, s->b_flags.p, s->b_lookups.p, s->b_way.p);
+                       s->batch.b_q.p, s->b_q2.p, n, s->b_flags.p, s->batch.b_lookups.p, s->b_way.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(valid, s->b_flags.p, n, hipMemcpyDeviceToHost, s->stream));
-    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->b_lookups.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->batch.b_lookups.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
     if (waypoints) HIP_TRY(hipMemcpyAsync(waypoints, s->b_way.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return SMPLX_OK;
@@ -1533,11 +1592,11 @@ int smplx_cc_sphere_positions(smplx_space* s, const double* q, int n, double* ou
     if (!sane_values(q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
     int e;
     const size_t cnt = (size_t)n * s->model.dev.nnodes * 3;
-    if ((e = s->b_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->batch.b_q.reserve((size_t)n * s->N))) return e;
     if ((e = s->b_sq.reserve(cnt))) return e;
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
     KLAUNCH(s, K_SPHERE_POSITIONS, k_sphere_positions, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes, s->stream,
-                       s->d_space, s->b_q.p, n, s->b_sq.p);
+                       s->d_space, s->batch.b_q.p, n, s->b_sq.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, s->b_sq.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1691,15 +1750,15 @@ int smplx_expand_batch(smplx_space* s, const double* q, int B, uint8_t* flags, i
     const size_t BM = (size_t)B * s->M;
     HIP_TRY(hipMemsetAsync(s->b_coord.p, 0, sizeof(int32_t) * BM * s->N, s->stream));
     HIP_TRY(hipMemsetAsync(s->b_sq.p, 0, sizeof(double) * BM * s->N, s->stream));
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, q, sizeof(double) * B * s->N, hipMemcpyHostToDevice, s->stream));
-    if (int e = launch_expand(s, s->b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->b_cost.p, s->b_lookups.p,
-                              s->b_work.p, nullptr, s->stream)) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * B * s->N, hipMemcpyHostToDevice, s->stream));
+    if (int e = smplx_expand_batch_device(s, s->batch.b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->batch.b_cost.p,
+                                          s->batch.b_lookups.p, s->batch.b_work.p, nullptr, s->stream)) return e;
     if (flags) HIP_TRY(hipMemcpyAsync(flags, s->b_flags.p, BM, hipMemcpyDeviceToHost, s->stream));
     if (coord) HIP_TRY(hipMemcpyAsync(coord, s->b_coord.p, sizeof(int32_t) * BM * s->N, hipMemcpyDeviceToHost, s->stream));
     if (succ_q) HIP_TRY(hipMemcpyAsync(succ_q, s->b_sq.p, sizeof(double) * BM * s->N, hipMemcpyDeviceToHost, s->stream));
     if (h) HIP_TRY(hipMemcpyAsync(h, s->b_h.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
-    if (cost) HIP_TRY(hipMemcpyAsync(cost, s->b_cost.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
-    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->b_lookups.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, s->batch.b_cost.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
+    if (lookups) HIP_TRY(hipMemcpyAsync(lookups, s->batch.b_lookups.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return SMPLX_OK;
 }
@@ -1716,8 +1775,9 @@ int smplx_expand_batch_device(smplx_space* s, const double* d_q, int B, uint8_t*
     if (!s || !d_q || !d_flags || !d_coord || !d_succ_q || !d_h || !d_cost || !d_lookups || !d_work || B <= 0)
         return set_error(SMPLX_E_ARG, "bad argument");
     if (!s->goal_set) return set_error(SMPLX_E_STATE, "set a goal first");
-    return launch_expand(s, d_q, B, d_flags, d_coord, d_succ_q, d_h, d_cost, d_lookups, d_work,
-                         (unsigned long long*)d_counters, (hipStream_t)stream);
+    // the K5 launch without its outputs
+    return smplx_expand_batch_k5_device(s, d_q, B, d_flags, d_coord, d_succ_q, d_h, d_cost, d_lookups, nullptr, nullptr, 0, nullptr, 0,
+                                        nullptr, nullptr, d_work, d_counters, stream);
 }
 
 int smplx_table_sync(smplx_space* s)
@@ -1759,8 +1819,14 @@ int smplx_expand_batch_k5_device(smplx_space* s, const double* d_q, int B, uint8
     K5Out k5;
     k5.d_id = d_succ_id;
     k5.cmp = d_rec_a ? &cmp : nullptr;
-    return launch_expand(s, d_q, B, d_flags, d_coord, d_succ_q, d_h, d_cost, d_lookups, d_work, (unsigned long long*)d_counters,
-                         (hipStream_t)stream, nullptr, nullptr, nullptr, false, &k5);
+    ExpandArgs a;
+    a.q = d_q; a.B = B;
+    a.flags = d_flags; a.coord = d_coord; a.sq = d_succ_q; a.h = d_h; a.cost = d_cost; a.lookups = d_lookups;
+    a.work = d_work;
+    a.counters = (unsigned long long*)d_counters;
+    a.stream = (hipStream_t)stream;
+    a.k5 = &k5;
+    return launch_expand(s, a);
 }
 
 int smplx_expand_batch_k5(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* coord, double* succ_q, int32_t* h,
@@ -1776,22 +1842,22 @@ int smplx_expand_batch_k5(smplx_space* s, const double* q, int B, uint8_t* flags
     int e;
     if ((e = s->b_way.reserve(BM))) return e;                                       // dense ids
     if ((e = s->b_ins.reserve(2 * (size_t)cap_a + 4 * (size_t)nblocks + SMPLX_CMP_TOTALS))) return e;   // A records | block table | totals
-    if ((e = s->b_out.reserve(rb * (size_t)cap_b))) return e;                       // B records
+    if ((e = s->batch.b_out.reserve(rb * (size_t)cap_b))) return e;                       // B records
     if ((e = table_ensure(s))) return e;
     if ((e = table_flush(s, s->stream))) return e;
     int32_t* d_a = s->b_ins.p;
     int32_t* d_bt = d_a + 2 * (size_t)cap_a;
     int32_t* d_tot = d_bt + 4 * (size_t)nblocks;
-    HIP_TRY(hipMemcpyAsync(s->b_q.p, q, sizeof(double) * B * s->N, hipMemcpyHostToDevice, s->stream));
-    if ((e = smplx_expand_batch_k5_device(s, s->b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->b_cost.p, s->b_lookups.p,
-                                          s->b_way.p, d_a, cap_a, s->b_out.p, cap_b, d_bt, d_tot, s->b_work.p, nullptr, s->stream))) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * B * s->N, hipMemcpyHostToDevice, s->stream));
+    if ((e = smplx_expand_batch_k5_device(s, s->batch.b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->batch.b_cost.p, s->batch.b_lookups.p,
+                                          s->b_way.p, d_a, cap_a, s->batch.b_out.p, cap_b, d_bt, d_tot, s->batch.b_work.p, nullptr, s->stream))) return e;
     if (flags) HIP_TRY(hipMemcpyAsync(flags, s->b_flags.p, BM, hipMemcpyDeviceToHost, s->stream));
     if (coord) HIP_TRY(hipMemcpyAsync(coord, s->b_coord.p, sizeof(int32_t) * BM * s->N, hipMemcpyDeviceToHost, s->stream));
     if (succ_q) HIP_TRY(hipMemcpyAsync(succ_q, s->b_sq.p, sizeof(double) * BM * s->N, hipMemcpyDeviceToHost, s->stream));
     if (h) HIP_TRY(hipMemcpyAsync(h, s->b_h.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
     if (succ_id) HIP_TRY(hipMemcpyAsync(succ_id, s->b_way.p, sizeof(int32_t) * BM, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipMemcpyAsync(rec_a, d_a, sizeof(int32_t) * 2 * (size_t)cap_a, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(rec_b, s->b_out.p, rb * (size_t)cap_b, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(rec_b, s->batch.b_out.p, rb * (size_t)cap_b, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipMemcpyAsync(block_tab, d_bt, sizeof(int32_t) * 4 * (size_t)nblocks, hipMemcpyDeviceToHost, s->stream));
     int32_t raw[SMPLX_CMP_TOTALS];
     HIP_TRY(hipMemcpyAsync(raw, d_tot, sizeof(raw), hipMemcpyDeviceToHost, s->stream));
@@ -2247,120 +2313,55 @@ void fill_search(Search& S, smplx_space* s, const smplx_time_params* p, std::chr
 
 }  // namespace
 
-// One slice [q0, q1) of a set of queries that share scene, robot and primitives, driven by the calling thread:
-// every sweep runs each live query until it misses, gathers the misses into ONE cross-query frontier batch
-// (per-state query index -> that query's goal and BFS grid), and hands the results back.
-int run_group(smplx_space** spaces, Search* S, int q0, int q1, char* done, double* t_done,
-              std::chrono::steady_clock::time_point t0)
+// Queries that share scene, robot and primitives, driven by the calling thread: every sweep runs each live query until
+// it misses, gathers the misses into ONE cross-query frontier batch (per-state query index -> that query's goal and
+// BFS grid), and hands the results back.
+int run_group(smplx_space** spaces, Search* S, int nq, char* done, double* t_done, std::chrono::steady_clock::time_point t0)
 {
-    smplx_space* lead = spaces[q0];
-    HIP_TRY(hipSetDevice(lead->device));   // a fresh host thread starts on device 0
-    const int nq = q1 - q0;
+    smplx_space* lead = spaces[0];
     int remaining = nq;
-        const int N = lead->N, M = lead->M;
-        {
-            std::vector<const SmplxSpaceDev*> tab(nq);
-            for (int q = 0; q < nq; ++q) tab[q] = spaces[q0 + q]->d_space;
-            if (int e = lead->b_stab.reserve(nq)) return e;
-            HIP_TRY(hipMemcpy(lead->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
+    for (int q = 0; q < nq; ++q) S[q].defer_issue = true;
+    // hinted frontier states per query and sweep: enough to keep a query fed, small enough that the dense
+    // download of a sweep stays in the hundreds of kilobytes
+    const int cap_q = std::max(16, std::min(512, (lead->params.batch_states > 0 ? lead->params.batch_states : 4096) / std::max(1, nq / 4)));
+    std::vector<int> reqs;
+    const bool dbg = getenv("SMPLX_DEBUG_TIMING") != nullptr;
+    double t_resume = 0, t_gpu = 0, t_collect = 0;
+    long sweeps = 0, swept_states = 0;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+    while (remaining > 0) {
+        reqs.clear();
+        const auto tr0 = now();
+        for (int q = 0; q < nq; ++q) {
+            if (done[q]) continue;
+            const int r = S[q].resume();
+            if (S[q].error) return S[q].error;
+            if (r == Search::R_YIELD) { reqs.push_back(q); continue; }
+            done[q] = 1;
+            --remaining;
+            t_done[q] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
-        for (int q = q0; q < q1; ++q) S[q].defer_issue = true;
-        // hinted frontier states per query and sweep: enough to keep a query fed, small enough that the dense
-        // download of a sweep stays in the hundreds of kilobytes
-        const int cap_q = std::max(16, std::min(512, (lead->params.batch_states > 0 ? lead->params.batch_states : 4096) / std::max(1, nq / 4)));
-        std::vector<int> reqs;
-        std::vector<int32_t> ins_items;
-        const bool dbg = getenv("SMPLX_DEBUG_TIMING") != nullptr;
-        double t_resume = 0, t_pack = 0, t_gpu = 0, t_collect = 0;
-        long sweeps = 0, swept_states = 0;
-        auto now = [] { return std::chrono::steady_clock::now(); };
-        auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-        while (remaining > 0) {
-            reqs.clear();
-            const auto tr0 = now();
-            for (int q = q0; q < q1; ++q) {
-                if (done[q]) continue;
-                const int r = S[q].resume();
-                if (S[q].error) return S[q].error;
-                if (r == Search::R_YIELD) { reqs.push_back(q); continue; }
-                done[q] = 1;
-                --remaining;
-                t_done[q] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            }
-            const auto tr1 = now();
-            t_resume += secs(tr0, tr1);
-            if (reqs.empty()) break;
-            size_t total = 0;
-            for (int q : reqs) { select_batch(spaces[q], S[q].miss_id, cap_q); total += spaces[q]->inflight.size(); }
-            ++sweeps; swept_states += (long)total;
-            const int B = (int)total;
-            const size_t BM = total * M;
-            int e;
-            if ((e = reserve_expand(lead, B))) return e;
-            if ((e = lead->b_stateq.reserve(total))) return e;
-            if ((e = lead->p_stateq.reserve(total))) return e;
-            if ((e = lead->p_q.reserve(total * N))) return e;
-            const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
-            if ((e = lead->b_out.reserve(out_bytes))) return e;
-            if ((e = lead->p_out.reserve(out_bytes))) return e;
-            lead->dv = carve_out(lead->b_out.p, BM, N);
-            lead->pv = carve_out(lead->p_out.p, BM, N);
-            size_t row = 0;
-            for (int q : reqs) {
-                const smplx_space* sq = spaces[q];
-                for (int32_t id : sq->inflight) {
-                    std::memcpy(&lead->p_q.p[row * N], &sq->qs[(size_t)id * N], sizeof(double) * N);
-                    lead->p_stateq.p[row] = (unsigned short)(q - q0);
-                    ++row;
-                }
-            }
-            const auto tp1 = now();
-            t_pack += secs(tr1, tp1);
-            K5Out k5;
-            k5.d_id = lead->dv.id;
-            size_t item_doubles = 0;
-            if (lead->d_table) {
-                std::vector<int32_t>& items = ins_items;
-                items.clear();
-                for (int q : reqs) {
-                    if ((e = table_grow_if_needed(spaces[q]))) return e;
-                    table_take_pending(spaces[q], q - q0, items);
-                }
-                if (!items.empty()) {
-                    if ((e = lead->p_q.reserve(total * N + items.size() / 2 + 1))) return e;   // (may move the buffer: packed below)
-                    if ((e = lead->b_q.reserve(total * N + items.size() / 2 + 1))) return e;
-                    k5.n_items = (int)(items.size() / ((size_t)N + 2));
-                }
-            }
-            {   // parents (packed again here: the pinned buffer may just have been re-allocated)
-                size_t r2 = 0;
-                for (int q : reqs) {
-                    const smplx_space* sq = spaces[q];
-                    for (int32_t id : sq->inflight) { std::memcpy(&lead->p_q.p[r2 * N], &sq->qs[(size_t)id * N], sizeof(double) * N); ++r2; }
-                }
-                item_doubles = stage_items(lead->p_q, total * N, ins_items);
-            }
-            HIP_TRY(hipMemcpyAsync(lead->b_q.p, lead->p_q.p, sizeof(double) * (total * N + item_doubles), hipMemcpyHostToDevice, lead->stream));
-            HIP_TRY(hipMemcpyAsync(lead->b_stateq.p, lead->p_stateq.p, sizeof(unsigned short) * total, hipMemcpyHostToDevice, lead->stream));
-            k5.items = (const int32_t*)(lead->b_q.p + total * N);
-            if ((e = launch_expand(lead, lead->b_q.p, B, lead->dv.flags, lead->dv.coord, lead->dv.sq, lead->dv.h, lead->b_cost.p,
-                                   lead->b_lookups.p, lead->b_work.p, nullptr, lead->stream, lead->b_stab.p, lead->b_stateq.p,
-                                   nullptr, false, &k5))) return e;
-            HIP_TRY(hipMemcpyAsync(lead->p_out.p, lead->b_out.p, out_bytes, hipMemcpyDeviceToHost, lead->stream));
-            HIP_TRY(hipStreamSynchronize(lead->stream));
-            const auto tg1 = now();
-            t_gpu += secs(tp1, tg1);
-            ++lead->gpu_batches;
-            row = 0;
-            for (int q : reqs) {
-                const size_t nb = spaces[q]->inflight.size();
-                if ((e = collect_batch(spaces[q], lead, row))) return e;
-                row += nb;
-            }
-            t_collect += secs(tg1, now());
+        const auto tr1 = now();
+        t_resume += secs(tr0, tr1);
+        if (reqs.empty()) break;
+        for (int q : reqs) { select_batch(spaces[q], S[q].miss_id, cap_q); swept_states += (long)spaces[q]->inflight.size(); }
+        ++sweeps;
+        if (int e = issue_frontier(lead, lead->batch, spaces, reqs.data(), (int)reqs.size(), lead->b_stab.p, lead->stream,
+                                   BatchMode{0, false, false})) return e;
+        HIP_TRY(hipStreamSynchronize(lead->stream));
+        const auto tg1 = now();
+        t_gpu += secs(tr1, tg1);
+        size_t row = 0;
+        for (int q : reqs) {
+            const size_t nb = spaces[q]->inflight.size();
+            if (int e = collect_batch(spaces[q], lead->batch, row)) return e;
+            row += nb;
         }
-        if (dbg) fprintf(stderr, "[smplx timing] slice [%d,%d): %ld sweeps, %.1f states/sweep; search+commit %.3fs pack %.3fs gpu(issue..sync) %.3fs collect %.3fs\n",
-                         q0, q1, sweeps, sweeps ? (double)swept_states / sweeps : 0.0, t_resume, t_pack, t_gpu, t_collect);
+        t_collect += secs(tg1, now());
+    }
+    if (dbg) fprintf(stderr, "[smplx timing] %d queries: %ld sweeps, %.1f states/sweep; search+commit %.3fs pack+gpu(issue..sync) %.3fs collect %.3fs\n",
+                     nq, sweeps, sweeps ? (double)swept_states / sweeps : 0.0, t_resume, t_gpu, t_collect);
     return SMPLX_OK;
 }
 
@@ -2380,24 +2381,11 @@ int run_group(smplx_space** spaces, Search* S, int q0, int q1, char* done, doubl
 //     comes round.
 // Every query sees only its own successor records, in its own sequential order: results are those of a solo run.
 // ---------------------------------------------------------------------------------------------------------------
-struct BatchBuffers {
-    DevBuf<double> b_q;
-    DevBuf<unsigned short> b_stateq;
-    DevBuf<unsigned char> b_work, b_out;
-    DevBuf<int32_t> b_cost, b_lookups;
-    PinBuf<double> p_q;
-    PinBuf<unsigned short> p_stateq;
-    PinBuf<unsigned char> p_out;
-    DevBuf<int32_t> b_ins;
-    PinBuf<int32_t> p_ins;
-    std::vector<int32_t> ins_items;
-    OutView dv, pv;
+struct RingSet : FrontierBatch {
     hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
     std::atomic<int> uncollected{0};   // queries of the batch that landed in this set and have not been ingested yet
     std::vector<int> queries;          // the queries of the batch in flight
     bool in_flight = false;
-    size_t total = 0;
 };
 
 enum { QS_RUNNABLE = 0, QS_REQUESTED = 1, QS_LANDED = 2, QS_IN_FLIGHT = 3 };
@@ -2410,7 +2398,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     enum { kSets = 8, kInFlight = 4 };
     const int small_zero_copy_max = 512;   // batches up to this size: one launch, results written straight to pinned host memory
     smplx_space* lead = spaces[0];
-    const int N = lead->N, M = lead->M;
+    const int N = lead->N;
     // one cache line per query state and per counter: the submitter polls them while the workers write them (with the
     // states packed 16 to a line, a scan of all queries cost the submitter 15-50 us per batch and slowed every worker store)
     struct alignas(64) PaddedInt { std::atomic<int> v{0}; };
@@ -2423,19 +2411,13 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     std::string error_msg;
     const int pause_after = 16;   // expansions without a miss before a query hands its worker to the next one (measured flat between 4 and 1000)
     for (int q = 0; q < nq; ++q) { qstate(q).store(QS_RUNNABLE); S[q].defer_issue = true; S[q].pause_after = pause_after; }
-    {
-        std::vector<const SmplxSpaceDev*> tab(nq);
-        for (int q = 0; q < nq; ++q) tab[q] = spaces[q]->d_space;
-        if (int e = lead->b_stab.reserve(nq)) return e;
-        HIP_TRY(hipMemcpy(lead->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
-    }
     const int cap_q = std::max(16, std::min(512, (lead->params.batch_states > 0 ? lead->params.batch_states : 4096) / std::max(1, nq / 8)));
     const bool dbg = getenv("SMPLX_DEBUG_TIMING") != nullptr;
     const int device = lead->device;
     const int issue_percent = 45;   // a batch is issued when this share of the live queries waits (1 %: 9.9e5 states/s, 45 %: 1.22e6, 70 %: 1.17e6)
     const int groups = 1;           // (forming batches within 2-3 independent groups of queries was measured: 1.37-1.39e6 against 1.42e6)
     for (int q = 0; q < nq; ++q) live_cnt[(q / nworkers) % groups].v.fetch_add(1, std::memory_order_relaxed);
-    std::vector<BatchBuffers> sets(kSets);
+    std::vector<RingSet> sets(kSets);
 
     auto fail = [&](int code, const std::string& msg) {
         int expect = 0;
@@ -2455,8 +2437,8 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
                 if (st == QS_REQUESTED || st == QS_IN_FLIGHT) continue;
                 const auto a0 = std::chrono::steady_clock::now();
                 if (st == QS_LANDED) {
-                    BatchBuffers& Bf = sets[set_of[q]];
-                    if (int e = collect_batch(spaces[q], lead, (size_t)row_of[q], &Bf.pv)) { fail(e, g_error); return; }
+                    RingSet& Bf = sets[set_of[q]];
+                    if (int e = collect_batch(spaces[q], Bf, (size_t)row_of[q])) { fail(e, g_error); return; }
                     Bf.uncollected.fetch_sub(1, std::memory_order_acq_rel);
                     qstate(q).store(QS_RUNNABLE, std::memory_order_relaxed);
                     if (dbg) { t_ingest += std::chrono::duration<double>(std::chrono::steady_clock::now() - a0).count(); ++n_ingest; }
@@ -2496,7 +2478,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
 
     auto submitter = [&]() -> int {
         HIP_TRY(hipSetDevice(device));
-        for (BatchBuffers& Bf : sets) {
+        for (RingSet& Bf : sets) {
             HIP_TRY(hipStreamCreate(&Bf.stream));
             HIP_TRY(hipEventCreateWithFlags(&Bf.done, hipEventDisableTiming));
         }
@@ -2504,7 +2486,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
         double t_issue = 0;
         int in_flight = 0, next_set = 0, oldest = 0;
         // SMPLX_DEBUG_TIMING: how long the GPU had nothing of this shard, issue-to-landing time, depth at issue
-        double t_gpu_idle = 0, lat_sum = 0, t_pack = 0;
+        double t_gpu_idle = 0, lat_sum = 0;
         long depth_sum = 0;
         auto idle_since = std::chrono::steady_clock::now();
         std::chrono::steady_clock::time_point issued_at[kSets];
@@ -2513,7 +2495,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
             bool did = false;
             // retire landed batches in issue order
             while (in_flight > 0) {
-                BatchBuffers& Bf = sets[oldest];
+                RingSet& Bf = sets[oldest];
                 const hipError_t st = hipEventQuery(Bf.done);
                 if (st == hipErrorNotReady) {
                     // a batch takes well under a millisecond: one that has not landed after SMPLX_BATCH_TIMEOUT_S is a hung
@@ -2537,7 +2519,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
                 did = true;
             }
             // issue: every request pending right now, if a buffer set is free
-            BatchBuffers& Nf = sets[next_set];
+            RingSet& Nf = sets[next_set];
             if (in_flight < kInFlight && !Nf.in_flight && Nf.uncollected.load(std::memory_order_acquire) == 0) {
                 const auto i0 = std::chrono::steady_clock::now();
                 // A batch has a fixed cost (issuing ~15 us, ~40 us on the GPU whatever its size).  Taking every request the
@@ -2569,88 +2551,25 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
                     pend_cnt[pick].v.fetch_sub((int)Nf.queries.size(), std::memory_order_acq_rel);
                 }
                 if (total > 0) {
-                    const int B = (int)total;
-                    const size_t BM = total * M;
-                    int e;
-                    if ((e = Nf.b_q.reserve(total * N))) return e;
-                    if ((e = Nf.b_work.reserve(expand_work_bytes(B, M)))) return e;
-                    if ((e = Nf.b_cost.reserve(BM))) return e;
-                    if ((e = Nf.b_lookups.reserve(BM))) return e;
-                    if ((e = Nf.b_stateq.reserve(total))) return e;
-                    if ((e = Nf.p_stateq.reserve(total))) return e;
-                    if ((e = Nf.p_q.reserve(total * N))) return e;
-                    const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
-                    if ((e = Nf.b_out.reserve(out_bytes))) return e;
-                    if ((e = Nf.p_out.reserve(out_bytes))) return e;
-                    Nf.dv = carve_out(Nf.b_out.p, BM, N);
-                    Nf.pv = carve_out(Nf.p_out.p, BM, N);
-                    size_t row = 0;
-                    Nf.ins_items.clear();
-                    for (int q : Nf.queries) {
-                        smplx_space* sq = spaces[q];
-                        // the parents' joint values were staged by the query's worker when it made the request (they were in
-                        // its cache then; gathering 270 rows from 58 queries' state arrays here cost the submitter ~20 us
-                        // of cache misses per batch)
-                        const size_t nrows = sq->inflight.size();
-                        std::memcpy(&Nf.p_q.p[row * N], sq->inflight_q.data(), sizeof(double) * N * nrows);
-                        for (size_t k = 0; k < nrows; ++k) Nf.p_stateq.p[row + k] = (unsigned short)q;
-                        row += nrows;
-                        // a requesting query is not being touched by its worker: its committed states join the device table
-                        if ((e = table_grow_if_needed(sq))) return e;
-                        table_take_pending(sq, q, Nf.ins_items);
-                        qstate(q).store(QS_IN_FLIGHT, std::memory_order_relaxed);
-                    }
-                    K5Out k5;
-                    k5.d_id = Nf.dv.id;
-                    size_t item_doubles = 0;
-                    if (!Nf.ins_items.empty()) {
-                        const size_t need = total * N + Nf.ins_items.size() / 2 + 1;
-                        if (need > Nf.p_q.cap) {   // re-allocate and pack the parents again
-                            if ((e = Nf.p_q.reserve(need))) return e;
-                            size_t r2 = 0;
-                            for (int q : Nf.queries)
-                            {
-                                const size_t nrows = spaces[q]->inflight.size();
-                                std::memcpy(&Nf.p_q.p[r2 * N], spaces[q]->inflight_q.data(), sizeof(double) * N * nrows);
-                                r2 += nrows;
-                            }
-                        }
-                        if ((e = Nf.b_q.reserve(need))) return e;
-                        k5.n_items = (int)(Nf.ins_items.size() / ((size_t)N + 2));
-                        item_doubles = stage_items(Nf.p_q, total * N, Nf.ins_items);
-                    }
-                    // Batches of up to 512 states: ONE launch, results written straight to pinned host memory.  Against the
-                    // pipeline (two uploads, four kernels, one download: seven runtime calls) the submitter spends 34
-                    // instead of 48 us per batch and a batch lands after 78 instead of 113 us: shard +8..17 % (same box,
-                    // A/B).  (Round 2 first measured the opposite -- 152 us per launch at ~100 states -- because the
-                    // kernel then checked the snap-to-goal edge of every state ungated, see k_small_batch.)
-                    if (B <= small_zero_copy_max && small_kernel_fits(lead, B) && lead->prof_events.empty()) {
-                        // one launch, no copies: parents, query indices and results live in pinned host memory
-                        if (dbg) t_pack += std::chrono::duration<double>(std::chrono::steady_clock::now() - i0).count();
-                        ZeroCopy zc;
-                        zc.q = Nf.p_q.p; zc.flags = Nf.pv.flags; zc.coord = Nf.pv.coord; zc.sq = Nf.pv.sq; zc.h = Nf.pv.h; zc.id = Nf.pv.id;
-                        k5.items = (const int32_t*)(Nf.p_q.p + total * N);
-                        if ((e = launch_expand(lead, Nf.b_q.p, B, Nf.dv.flags, Nf.dv.coord, Nf.dv.sq, Nf.dv.h, Nf.b_cost.p, Nf.b_lookups.p,
-                                               Nf.b_work.p, nullptr, Nf.stream, lead->b_stab.p, Nf.p_stateq.p, &zc, false, &k5))) return e;
-                    } else {
-                        HIP_TRY(hipMemcpyAsync(Nf.b_q.p, Nf.p_q.p, sizeof(double) * (total * N + item_doubles), hipMemcpyHostToDevice, Nf.stream));
-                        HIP_TRY(hipMemcpyAsync(Nf.b_stateq.p, Nf.p_stateq.p, sizeof(unsigned short) * total, hipMemcpyHostToDevice, Nf.stream));
-                        k5.items = (const int32_t*)(Nf.b_q.p + total * N);
-                        if ((e = launch_expand(lead, Nf.b_q.p, B, Nf.dv.flags, Nf.dv.coord, Nf.dv.sq, Nf.dv.h, Nf.b_cost.p, Nf.b_lookups.p,
-                                               Nf.b_work.p, nullptr, Nf.stream, lead->b_stab.p, Nf.b_stateq.p, nullptr, true, &k5))) return e;
-                        HIP_TRY(hipMemcpyAsync(Nf.p_out.p, Nf.b_out.p, out_bytes, hipMemcpyDeviceToHost, Nf.stream));
-                    }
-                    HIP_TRY(hipEventRecord(Nf.done, Nf.stream));
+                    for (int q : Nf.queries) qstate(q).store(QS_IN_FLIGHT, std::memory_order_relaxed);
+                    // The parents' joint values were staged by each query's worker when it made the request (they were in
+                    // its cache then; gathering 270 rows from 58 queries' state arrays here cost the submitter ~20 us of
+                    // cache misses per batch).  Batches of up to 512 states: ONE launch, results written straight to
+                    // pinned host memory.  Against the pipeline (two uploads, four kernels, one download: seven runtime
+                    // calls) the submitter spends 34 instead of 48 us per batch and a batch lands after 78 instead of
+                    // 113 us: shard +8..17 % (same box, A/B).  (Round 2 first measured the opposite -- 152 us per launch
+                    // at ~100 states -- because the kernel then checked the snap-to-goal edge of every state ungated, see
+                    // k_small_batch.)
+                    if (int e = issue_frontier(lead, Nf, spaces, Nf.queries.data(), (int)Nf.queries.size(), lead->b_stab.p, Nf.stream,
+                                               BatchMode{small_zero_copy_max, true, true})) return e;
                     issued_at[next_set] = i0;
                     if (dbg) {
                         depth_sum += in_flight;
                         if (in_flight == 0) t_gpu_idle += std::chrono::duration<double>(i0 - idle_since).count();
                     }
                     Nf.in_flight = true;
-                    Nf.total = total;
                     ++in_flight;
                     next_set = (next_set + 1) % kSets;
-                    ++lead->gpu_batches;
                     ++sweeps; states += (long)total;
                     did = true;
                     t_issue += std::chrono::duration<double>(std::chrono::steady_clock::now() - i0).count();
@@ -2659,11 +2578,11 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
             if (!did) cpu_relax();
         }
         // drain what is still in flight (only on error paths: with no live query nothing is pending)
-        for (BatchBuffers& Bf : sets) if (Bf.stream) (void)hipStreamSynchronize(Bf.stream);
+        for (RingSet& Bf : sets) if (Bf.stream) (void)hipStreamSynchronize(Bf.stream);
         if (dbg) fprintf(stderr, "[smplx timing] submitter: %ld batches, %.1f states/batch; issuing %.3fs (pack + enqueue); GPU without a batch %.3fs; "
-                                 "issue-to-landing %.1f us on average; %.2f batches already in flight at issue; of the issuing, %.3fs before the launch call\n",
+                                 "issue-to-landing %.1f us on average; %.2f batches already in flight at issue\n",
                          sweeps, sweeps ? (double)states / sweeps : 0.0, t_issue, t_gpu_idle, sweeps ? 1e6 * lat_sum / sweeps : 0.0,
-                         sweeps ? (double)depth_sum / sweeps : 0.0, t_pack);
+                         sweeps ? (double)depth_sum / sweeps : 0.0);
         return SMPLX_OK;
     };
 
@@ -2672,7 +2591,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     int rc = submitter();
     if (rc != SMPLX_OK) fail(rc, g_error);
     for (auto& x : th) x.join();
-    for (BatchBuffers& Bf : sets) {
+    for (RingSet& Bf : sets) {
         if (Bf.stream) { (void)hipStreamSynchronize(Bf.stream); (void)hipStreamDestroy(Bf.stream); }
         if (Bf.done) (void)hipEventDestroy(Bf.done);
     }
@@ -2755,7 +2674,6 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
     }
     std::vector<char> done(nq, 0), waiting(nq, 0);
     std::vector<double> t_done(nq, 0.0);
-    int remaining = nq;
     // Queries that share the scene (same grid handle), robot and primitives can share launches: their misses are
     // gathered into ONE cross-query frontier batch per sweep (per-state query index -> that query's goal and BFS
     // grid).  Otherwise each query issues its own batches on its own stream.
@@ -2781,26 +2699,19 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
         return SMPLX_OK;
     }
     if (grouped) {
-        // host threads: each drives a contiguous slice of the queries with its own leading space / stream, so the
-        // commit work (hashing, heap, record ingestion) of different slices overlaps; the GPU serves all of them
-        int nthreads = host_threads > 0 ? host_threads : 1;
-        nthreads = std::max(1, std::min(nthreads, nq));
-        std::vector<int> rc(nthreads, SMPLX_OK);
-        std::vector<std::string> msg(nthreads);
-        auto worker = [&](int t) {
-            const int nt = (nthreads == 1 || nq < 4) ? 1 : nthreads;
-            const int q0 = (int)((long long)nq * t / nt), q1 = (int)((long long)nq * (t + 1) / nt);
-            rc[t] = run_group(spaces, S.data(), q0, q1, done.data(), t_done.data(), t0);
-            if (rc[t] != SMPLX_OK) msg[t] = g_error;
-        };
-        if (nthreads == 1 || nq < 4) {
-            worker(0);
-            if (rc[0] != SMPLX_OK) return set_error(rc[0], msg[0]);
-        } else {
-            // host_threads worker threads + this thread as the only GPU submitter (run_pipelined)
-            if (int e = run_pipelined(spaces, S.data(), nq, std::min(nthreads, nq), done.data(), t_done.data(), t0)) return e;
-        }
-        remaining = 0;
+        // the query table of the cross-query batches (per-row query index -> that query's goal and BFS grid), held by
+        // the leading space
+        HIP_TRY(hipSetDevice(spaces[0]->device));
+        std::vector<const SmplxSpaceDev*> tab(nq);
+        for (int q = 0; q < nq; ++q) tab[q] = spaces[q]->d_space;
+        if (int e = spaces[0]->b_stab.reserve(nq)) return e;
+        HIP_TRY(hipMemcpy(spaces[0]->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
+        // one thread sweeps all queries (run_group), or host_threads worker threads own them and this thread is the only
+        // GPU submitter (run_pipelined)
+        const int nthreads = std::max(1, std::min(host_threads > 0 ? host_threads : 1, nq));
+        const int e = nthreads == 1 || nq < 4 ? run_group(spaces, S.data(), nq, done.data(), t_done.data(), t0)
+                                              : run_pipelined(spaces, S.data(), nq, nthreads, done.data(), t_done.data(), t0);
+        if (e) return e;
     } else {
         // One host thread drives every query: a query runs until it misses, its frontier batch goes to its own
         // stream, and the thread moves on to the next query; a landed batch is collected when its turn comes again.
@@ -2808,17 +2719,18 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
         const bool dbg = getenv("SMPLX_DEBUG_TIMING") != nullptr;
         auto now = [] { return std::chrono::steady_clock::now(); };
         auto secs = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+        int remaining = nq;
         while (remaining > 0) {
             bool progressed = false;
             for (int q = 0; q < nq; ++q) {
                 if (done[q]) continue;
                 smplx_space* s = spaces[q];
                 if (waiting[q]) {
-                    const hipError_t st = hipEventQuery(s->batch_done);
+                    const hipError_t st = hipEventQuery(s->batch.done);
                     if (st == hipErrorNotReady) continue;
                     if (st != hipSuccess) return set_error(SMPLX_E_HIP, std::string("hipEventQuery: ") + hipGetErrorString(st));
                     const auto c0 = now();
-                    if (int e = collect_batch(s)) return e;
+                    if (int e = collect_batch(s, s->batch, 0)) return e;
                     t_collect += secs(c0, now());
                     waiting[q] = 0;
                 }
@@ -2836,7 +2748,7 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
                 // every live query is waiting on the GPU: block on one of them instead of spinning
                 const auto w0 = now();
                 for (int q = 0; q < nq; ++q)
-                    if (!done[q] && waiting[q]) { if (int e = wait_event_polling(spaces[q]->batch_done)) return e; break; }
+                    if (!done[q] && waiting[q]) { if (int e = wait_event_polling(spaces[q]->batch.done)) return e; break; }
                 t_wait += secs(w0, now());
             }
         }

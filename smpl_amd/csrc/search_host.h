@@ -389,8 +389,8 @@ int search_run_launches(smplx_space** spaces, int nq, const smplx_time_params* p
         KLAUNCH(lead, K_SEARCH, k_search, dim3(nq), dim3(block), lds, lead->stream, (const SmplxSpaceDev* const*)lead->b_stab.p, max_steps, lh, status.p,
                 pre_ticks);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(lead->batch_done, lead->stream));
-        if (int e = wait_event_polling(lead->batch_done)) return e;
+        HIP_TRY(hipEventRecord(lead->batch.done, lead->stream));
+        if (int e = wait_event_polling(lead->batch.done)) return e;
         ++launches;
         const auto now = std::chrono::steady_clock::now();
         for (int q = 0; q < nq; ++q) {

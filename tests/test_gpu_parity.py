@@ -415,18 +415,23 @@ def test_dual_arm_expand_batch(dual_ctx):
     assert (got["flags"] & 1).sum() > 50
 
 
-@pytest.mark.parametrize("shared_scene", ["device", True, 3, 1, False])
-def test_interleaved_multi_query_equals_each_query_alone(small_cfg, shared_scene, monkeypatch):
+@pytest.mark.parametrize("shared_scene,device_table",
+                         [pytest.param(x, False, id=str(x)) for x in ("device", True, 3, 1, False)] +
+                         [pytest.param(x, True, id=f"{x}-device_table") for x in (True, 3, 1, False)])
+def test_interleaved_multi_query_equals_each_query_alone(small_cfg, shared_scene, device_table, monkeypatch):
     """smplx_plan_multi: independent queries side by side on one GPU (BASELINE config 4 shape).  Every query must come
     out exactly as it does alone -- and as the oracle computes it.  "device": the default, one persistent workgroup per
     query (the searches themselves are in tests/test_gpu_device_search.py); the other four the host-driven loop
-    (SMPLX_SEARCH=host) with its thread layouts."""
+    (SMPLX_SEARCH=host) with its thread layouts, each also with the device state table (SMPLX_DEVICE_TABLE=1), whose
+    inserts ride in the cross-query batches."""
     from oracle_binding import Oracle
     from smpl_amd import capi
     cfg = small_cfg
     on_device = shared_scene == "device"
     if not on_device:
         monkeypatch.setenv("SMPLX_SEARCH", "host")
+    if device_table:
+        monkeypatch.setenv("SMPLX_DEVICE_TABLE", "1")
     cells = [[-49, 7, 21, -14, -8, -12, 16], [-21, 7, 14, -7, 8, -4, 12], [-35, 14, 7, -14, 4, -8, 8], [-42, 10, 14, -10, 0, -8, 12]]
     goals = [[cfg.start[i] + c * DEG for i, c in enumerate(cs)] for cs in cells]
     spaces = []
