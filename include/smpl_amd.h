@@ -172,6 +172,37 @@ int smplx_cc_interpolate(smplx_space* s, const double* a, const double* b, doubl
 /* world positions of all sphere-tree nodes for n states: out[n][nnodes][3] (RobotCollisionState::updateSphereState) */
 int smplx_cc_sphere_positions(smplx_space* s, const double* q, int n, double* out);
 
+/* ---- attached collision bodies (CollisionSpace::processAttachedCollisionObject -> attachObject / detachObject,
+ * sbpl_collision_checking/src/collision_space.cpp:119-124, 297-345) ----
+ * A body is a set of spheres (n x {x, y, z, r}, metres, in the frame of `link`) rigidly attached to a link of the
+ * collision group.  The engine builds its bounding sphere tree as it builds a link's (base_collision_models.cpp:337-444;
+ * voxelising shapes into spheres is the caller's part) and from then on every state and edge check -- smplx_cc_*, the
+ * start check of smplx_set_start, successor evaluation and both searches -- also checks the body:
+ *   - against the grid, with the space's padding (collision_operations.h:67-77);
+ *   - against every tree of the robot whose link is not in `allowed`, and against every other body unless either
+ *     body lists the other's id in `allowed` (self_collision_model.cpp:1270-1345; leaf x leaf overlap = collision).
+ *     The link the body hangs on is NOT implicitly allowed: list it (MoveIt's touch links).  Names in `allowed` that are
+ *     neither a link nor an attached body are kept: they take effect when a body with that id is attached.
+ * Motion-sphere factors and waypoint counts are those of the robot alone (the reference's RobotMotionCollisionModel).
+ * Refused with SMPLX_E_ARG: an id already attached (or empty, or with white space), an unknown link, a link outside the
+ * collision group (the reference would accept it and never check it); SMPLX_E_LIMIT above SMPLX_MAX_BODIES (8) bodies or
+ * SMPLX_MAX_BODY_NODES (1024) tree nodes (n spheres make 2n - 1 nodes) per space.
+ * An attach or detach acts like a grid edit (see EDITS AND SPACES above): smplx_get_succs / smplx_plan* return
+ * SMPLX_E_STATE and smplx_replan* does not resume until the goal is set again.  It waits for the device to finish its
+ * work (launches on the caller's streams included) before it changes the bodies' image. */
+int smplx_attach_body(smplx_space* s, const char* id, const char* link, const double* spheres, int n, const char* const* allowed,
+                      int nallowed);
+int smplx_detach_body(smplx_space* s, const char* id);            /* SMPLX_E_ARG for an id not attached */
+/* the attached bodies in attach order: returns their number; names gets one "id link\n" line per body (cap bytes,
+ * NUL-terminated, may be NULL with cap 0); first_node / nnodes (SMPLX_MAX_BODIES entries each, may be NULL): each body's
+ * range of nodes in the order of smplx_attached_nodes and smplx_cc_attached_positions */
+int smplx_attached_bodies(const smplx_space* s, char* names, int cap, int32_t* first_node, int32_t* nnodes);
+/* returns the number of body tree nodes; xyzr[4 * count] (centre in the link frame, radius), left[count] and right[count]
+ * (children, -1 for a leaf; a body's tree is stored in pre-order, root first) may be NULL */
+int smplx_attached_nodes(const smplx_space* s, double* xyzr, int32_t* left, int32_t* right);
+/* world positions of all body tree nodes for n states: out[n][count][3], the counterpart of smplx_cc_sphere_positions */
+int smplx_cc_attached_positions(smplx_space* s, const double* q, int n, double* out);
+
 /* ---- RobotHeuristic / BfsHeuristic (smpl/include/smpl/heuristic/robot_heuristic.h:53-101) ---- */
 /* RobotPlanningSpace::setGoal with a JOINT_STATE_GOAL (manip_lattice.cpp:2248-2287; goal pose = FK of the
  * angles, planner_interface.cpp:1232-1235) -> BfsHeuristic::updateGoal -> BFS_3D::run to completion */

@@ -14,6 +14,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstddef>
 #include <cstdint>
@@ -308,6 +309,20 @@ public:
         for (int i = 0; i < n; ++i) path.emplace_back(buf.begin() + (size_t)i * ctx_->nvars(), buf.begin() + (size_t)(i + 1) * ctx_->nvars());
         return true;
     }
+    // collision_space.cpp:297-312.  The object arrives as spheres (x, y, z, r in the link's frame) instead of shapes and
+    // transforms; `allowed` holds the links and attached objects it may touch (MoveIt's touch links).  False with the
+    // reason in smplx_last_error() where the reference returns false, and also for a link outside the collision group.
+    bool attachObject(const std::string& id, const std::vector<std::array<double, 4>>& spheres, const std::string& link_name,
+                      const std::vector<std::string>& allowed = {})
+    {
+        std::vector<double> xyzr;
+        for (const auto& s : spheres) xyzr.insert(xyzr.end(), s.begin(), s.end());
+        std::vector<const char*> names;
+        for (const std::string& a : allowed) names.push_back(a.c_str());
+        return smplx_attach_body(ctx_->space(), id.c_str(), link_name.c_str(), xyzr.data(), (int)spheres.size(), names.data(),
+                                 (int)names.size()) == SMPLX_OK;
+    }
+    bool detachObject(const std::string& id) { return smplx_detach_body(ctx_->space(), id.c_str()) == SMPLX_OK; }
     Extension* getExtension(size_t class_code) override
     {
         return class_code == GetClassCode<CollisionChecker>() ? this : nullptr;   // collision_space.cpp:523-529

@@ -37,6 +37,7 @@ SYMBOLS = [
     "smplx_grid_create_empty", "smplx_grid_add_boxes", "smplx_grid_add_points", "smplx_grid_remove_points", "smplx_grid_copy_d2",
     "smplx_search_counters", "smplx_grid_set_ref_counted", "smplx_grid_update_points", "smplx_grid_copy_counts", "smplx_grid_last_edit_cells",
     "smplx_replan", "smplx_replan_multi",
+    "smplx_attach_body", "smplx_detach_body", "smplx_attached_bodies", "smplx_attached_nodes", "smplx_cc_attached_positions",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -349,6 +350,52 @@ class Space:
         q = _f64(q).reshape(-1, self.N); n = q.shape[0]
         out = np.zeros((n, self.model.nnodes, 3))
         _chk(lib().smplx_cc_sphere_positions(self.h, _p(q, _dp), n, _p(out, _dp)))
+        return out
+
+    # ---- attached collision bodies (CollisionSpace::attachObject / detachObject) ----
+    def attach_body(self, body_id, link, spheres, allowed=()):
+        """spheres: n x (x, y, z, r) in the frame of `link`; allowed: link names and body ids the body may touch"""
+        sp = _f64(spheres).reshape(-1, 4)
+        names = [str(a).encode() for a in allowed]
+        arr = (C.c_char_p * max(1, len(names)))(*names)
+        L = lib()
+        L.smplx_attach_body.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp, C.c_int, C.POINTER(C.c_char_p), C.c_int]
+        _chk(L.smplx_attach_body(self.h, str(body_id).encode(), str(link).encode(), _p(sp, _dp), sp.shape[0], arr, len(names)))
+
+    def detach_body(self, body_id):
+        lib().smplx_detach_body.argtypes = [C.c_void_p, C.c_char_p]
+        _chk(lib().smplx_detach_body(self.h, str(body_id).encode()))
+
+    def attached_bodies(self):
+        """[{id, link, first, count}] in attach order: each body's range of nodes in attached_nodes / attached_positions"""
+        L = lib()
+        L.smplx_attached_bodies.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _ip, _ip]
+        first = np.zeros(8, np.int32); cnt = np.zeros(8, np.int32)
+        buf = C.create_string_buffer(8 * 600)
+        n = L.smplx_attached_bodies(self.h, buf, len(buf), _p(first, _ip), _p(cnt, _ip))
+        _chk(min(n, 0))
+        lines = buf.value.decode().splitlines()
+        return [dict(id=lines[b].split(" ")[0], link=lines[b].split(" ")[1], first=int(first[b]), count=int(cnt[b]))
+                for b in range(n)]
+
+    def attached_nodes(self):
+        """(xyzr in the link frame, left child, right child; -1 for a leaf) of every body tree node"""
+        L = lib()
+        L.smplx_attached_nodes.argtypes = [C.c_void_p, _dp, _ip, _ip]
+        n = L.smplx_attached_nodes(self.h, None, None, None)
+        _chk(min(n, 0))
+        xyzr = np.zeros((n, 4)); left = np.zeros(n, np.int32); right = np.zeros(n, np.int32)
+        if n:
+            _chk(min(L.smplx_attached_nodes(self.h, _p(xyzr, _dp), _p(left, _ip), _p(right, _ip)), 0))
+        return xyzr, left, right
+
+    def attached_positions(self, q):
+        """world positions of every body tree node: [n states][nodes][3]"""
+        q = _f64(q).reshape(-1, self.N); n = q.shape[0]
+        nn = sum(b["count"] for b in self.attached_bodies())
+        out = np.zeros((n, nn, 3))
+        lib().smplx_cc_attached_positions.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
+        _chk(lib().smplx_cc_attached_positions(self.h, _p(q, _dp), n, _p(out, _dp)))
         return out
 
     # ---- heuristic ----

@@ -180,6 +180,28 @@ enum { SMPLX_BH_NJOINTS = 0, SMPLX_BH_NVARS, SMPLX_BH_NTREES, SMPLX_BH_NNODES, S
        SMPLX_BH_OFF_VARI, SMPLX_BH_STACK, SMPLX_BH_WORDS = 16 };
 #define SMPLX_MAX_BLOB_BYTES (64 + SMPLX_MAX_JOINTS * 144 + SMPLX_MAX_NODES * 48 + 4096)
 
+// Collision bodies attached to robot links (CollisionSpace::attachObject, collision_space.cpp:297-345; their spheres and
+// checks: attached_bodies_collision_model.cpp, self_collision_model.cpp:863-878, 1270-1345).  Per space, in HBM; the
+// kernels read it only when `n` > 0.  A body's sphere tree is built as a link's is (model_compile.cpp TreeBuilder) but
+// stored in PRE-order: the left child follows its parent, `left` = -1 marks a leaf, and `pad` holds the index one past
+// the node's subtree, so that the walks need no stack (a body has up to 1024 nodes and its tree is deeper than the
+// robot's LDS stack).  `thr` is bound to the space's grid and padding as the robot's nodes are.
+#define SMPLX_MAX_BODIES 8
+#define SMPLX_MAX_BODY_NODES 1024
+struct SmplxBodyDev {
+    int32_t joint;                // the body's link is the child link of this joint (depth-first index), -1 = the root link
+    int32_t root, end;            // its nodes are [root, end) of SmplxBodiesDev::nodes, root first
+    uint32_t allow_trees;         // bit t: the robot's tree t is not checked against the body
+    uint32_t allow_bodies;        // bit b: body b is not checked against it (symmetric)
+    int32_t pad[3];
+};
+struct alignas(16) SmplxBodiesDev {
+    int32_t n, nnodes, pad[2];
+    uint64_t ancestors[SMPLX_MAX_JOINTS];         // bit i of [j]: joint i lies on the path from the root to joint j's child link
+    SmplxBodyDev body[SMPLX_MAX_BODIES];
+    SmplxNode nodes[SMPLX_MAX_BODY_NODES];
+};
+
 struct SmplxSearchDev;
 
 // everything one query needs, resident in HBM
@@ -192,6 +214,7 @@ struct SmplxSpaceDev {
     SmplxGoalDev goal;
     SmplxTableDev table;
     SmplxSearchDev* search;       // device-resident ARA* of this query (null until the first device search)
+    const SmplxBodiesDev* bodies; // attached bodies, null while the space has none
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

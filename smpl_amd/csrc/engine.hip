@@ -336,6 +336,19 @@ struct smplx_space {
     // optional per-kernel timing of expand launches (bench.py roofline): 3 events per launch
     std::vector<hipEvent_t> prof_events;
     size_t prof_used = 0;
+    // collision bodies attached to robot links (CollisionSpace::attachObject, collision_space.cpp:297-345), in attach order;
+    // their device image (hs.bodies, null while there are none) is rebuilt at every attach and detach
+    struct Body {
+        std::string id, link;
+        int joint = -1;                    // depth-first joint whose child link carries it, -1 = the root link
+        std::vector<double> xyzr;          // spheres in the link's frame
+        std::vector<std::string> allowed;  // link names and body ids it may touch
+        int first = 0, count = 0;          // its nodes in the device image
+    };
+    std::vector<Body> bodies;
+    SmplxBodiesDev* d_bodies = nullptr;
+    uint64_t body_epoch = 0;           // attaches + detaches so far
+    uint64_t body_epoch_goal = 0;      // ... when the goal was set: the successor caches belong to that set of bodies
 };
 
 namespace {
@@ -1414,6 +1427,7 @@ void smplx_space_destroy(smplx_space* s)
     if (s->d_brick_queued) (void)hipFree(s->d_brick_queued);
     if (s->d_minus_one) (void)hipFree(s->d_minus_one);
     if (s->d_table) (void)hipFree(s->d_table);
+    if (s->d_bodies) (void)hipFree(s->d_bodies);
     (void)search_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1603,6 +1617,189 @@ int smplx_cc_sphere_positions(smplx_space* s, const double* q, int n, double* ou
     return SMPLX_OK;
 }
 
+// ---- attached bodies -------------------------------------------------------------------------------------------------
+
+static const char* const kBodiesChanged = "bodies were attached or detached after the goal was set: cached successors are stale, set the goal again";
+
+namespace {
+
+// the device image of the space's bodies (device_types.h SmplxBodiesDev): trees in pre-order, thresholds bound to the
+// space's grid and padding, allowed masks resolved by name.  Rebuilt whole at every attach and detach (the reference
+// rebuilds its pair lists only when the group or the ACM changes, self_collision_model.cpp:1311).
+int upload_bodies(smplx_space* s)
+{
+    std::unique_ptr<SmplxBodiesDev> img(new SmplxBodiesDev);
+    std::memset(img.get(), 0, sizeof(SmplxBodiesDev));
+    const SmplxModelDev& D = s->model.dev;
+    // ancestors: the transform flow of the chain pass (running / root / saved slot), joint by joint
+    uint64_t slot_anc[SMPLX_MAX_SLOTS] = {};
+    for (int j = 0; j < D.njoints; ++j) {
+        const SmplxJoint& J = D.joints[j];
+        const uint64_t base = J.src == SMPLX_SRC_ROOT ? 0ull : (J.src == SMPLX_SRC_RUNNING ? img->ancestors[j - 1] : slot_anc[J.src]);
+        img->ancestors[j] = base | (1ull << j);
+        if (J.save_slot >= 0) slot_anc[J.save_slot] = img->ancestors[j];
+    }
+    int nn = 0;
+    for (size_t b = 0; b < s->bodies.size(); ++b) {
+        smplx_space::Body& B = s->bodies[b];
+        std::vector<SmplxNode> post;
+        smplx::build_sphere_tree(B.xyzr.data(), (int)(B.xyzr.size() / 4), post);
+        B.first = nn;
+        // post-order (root last, local indices) -> pre-order with the end of each subtree in `pad`
+        std::function<void(int)> emit = [&](int k) {
+            const int at = nn++;
+            SmplxNode n = post[k];
+            n.thr = smplx::sphere_threshold(n.r, s->params.padding, s->grid->res, s->grid->dmax_sqrd);
+            const int l = n.left, r = n.right;
+            img->nodes[at] = n;
+            if (l >= 0) {
+                img->nodes[at].left = at + 1;
+                emit(l);
+                img->nodes[at].right = nn;
+                emit(r);
+            }
+            img->nodes[at].pad = nn;
+        };
+        emit((int)post.size() - 1);
+        B.count = nn - B.first;
+        SmplxBodyDev& o = img->body[b];
+        o.joint = B.joint;
+        o.root = B.first;
+        o.end = nn;
+        for (const std::string& a : B.allowed) {
+            for (int t = 0; t < D.ntrees; ++t)
+                if (s->model.child_links[D.tree_joint[t]] == a) o.allow_trees |= 1u << t;
+            for (size_t c = 0; c < s->bodies.size(); ++c)
+                if (c != b && s->bodies[c].id == a) { o.allow_bodies |= 1u << c; img->body[c].allow_bodies |= 1u << b; }
+        }
+    }
+    img->n = (int)s->bodies.size();
+    img->nnodes = nn;
+    if (!s->d_bodies) HIP_TRY(hipMalloc((void**)&s->d_bodies, sizeof(SmplxBodiesDev)));
+    // kernels in flight may still read the old image, on the space's stream or on a caller's (the _device entry points)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyAsync(s->d_bodies, img.get(), sizeof(SmplxBodiesDev), hipMemcpyHostToDevice, s->stream));
+    s->hs.bodies = s->bodies.empty() ? nullptr : s->d_bodies;
+    HIP_TRY(hipMemcpyAsync((unsigned char*)s->d_space + offsetof(SmplxSpaceDev, bodies), &s->hs.bodies, sizeof(s->hs.bodies),
+                           hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SMPLX_OK;
+}
+
+}  // namespace
+
+int smplx_attach_body(smplx_space* s, const char* id, const char* link, const double* spheres, int n, const char* const* allowed,
+                      int nallowed)
+{
+    if (!s || !id || !link || !spheres || n <= 0 || nallowed < 0 || (nallowed > 0 && !allowed))
+        return set_error(SMPLX_E_ARG, "bad argument");
+    const std::string sid(id);
+    if (sid.empty() || sid.size() > 255 || sid.find_first_of(" \t\r\n") != std::string::npos)
+        return set_error(SMPLX_E_ARG, "a body id is 1 to 255 characters without white space");
+    for (const smplx_space::Body& b : s->bodies)
+        if (b.id == sid) return set_error(SMPLX_E_ARG, "a body with id " + sid + " is attached already");
+    smplx_space::Body B;
+    B.id = sid;
+    B.link = link;
+    const smplx::HostModel& hm = s->model;
+    if (B.link == hm.root_link) B.joint = -1;
+    else {
+        B.joint = -2;
+        for (size_t j = 0; j < hm.child_links.size(); ++j) if (hm.child_links[j] == B.link) B.joint = (int)j;
+        if (B.joint == -2) return set_error(SMPLX_E_ARG, "unknown link " + B.link);
+    }
+    // the reference never checks a body on a link outside the group (attached_bodies_collision_model.cpp:124-135): refused
+    if (std::find(hm.group_links.begin(), hm.group_links.end(), B.link) == hm.group_links.end())
+        return set_error(SMPLX_E_ARG, "link " + B.link + " is outside the collision group: a body there would never be checked");
+    for (int i = 0; i < 4 * n; ++i)
+        if (!std::isfinite(spheres[i]) || std::fabs(spheres[i]) >= 1e6 || (i % 4 == 3 && spheres[i] < 0.0))
+            return set_error(SMPLX_E_ARG, "spheres: finite x y z r with |value| < 1e6 and r >= 0");
+    for (int i = 0; i < nallowed; ++i) {
+        if (!allowed[i]) return set_error(SMPLX_E_ARG, "null name in the allowed list");
+        B.allowed.emplace_back(allowed[i]);
+    }
+    if ((int)s->bodies.size() >= SMPLX_MAX_BODIES) return set_error(SMPLX_E_LIMIT, "more than SMPLX_MAX_BODIES (8) attached bodies");
+    int used = 0;
+    for (const smplx_space::Body& b : s->bodies) used += b.count;
+    if ((long long)used + 2ll * n - 1 > SMPLX_MAX_BODY_NODES)
+        return set_error(SMPLX_E_LIMIT, "the attached bodies need more than SMPLX_MAX_BODY_NODES (1024) tree nodes");
+    B.xyzr.assign(spheres, spheres + 4 * (size_t)n);
+    s->bodies.push_back(std::move(B));
+    if (int e = upload_bodies(s)) { const std::string m = g_error; s->bodies.pop_back(); (void)upload_bodies(s); return set_error(e, m); }
+    ++s->body_epoch;
+    return SMPLX_OK;
+}
+
+int smplx_detach_body(smplx_space* s, const char* id)
+{
+    if (!s || !id) return set_error(SMPLX_E_ARG, "bad argument");
+    for (size_t b = 0; b < s->bodies.size(); ++b) {
+        if (s->bodies[b].id != id) continue;
+        smplx_space::Body keep = s->bodies[b];
+        s->bodies.erase(s->bodies.begin() + b);
+        if (int e = upload_bodies(s)) {
+            const std::string m = g_error;
+            s->bodies.insert(s->bodies.begin() + b, std::move(keep));
+            (void)upload_bodies(s);
+            return set_error(e, m);
+        }
+        ++s->body_epoch;
+        return SMPLX_OK;
+    }
+    return set_error(SMPLX_E_ARG, std::string("no attached body with id ") + id);
+}
+
+int smplx_attached_bodies(const smplx_space* s, char* names, int cap, int32_t* first_node, int32_t* nnodes)
+{
+    if (!s || cap < 0 || (cap > 0 && !names)) return set_error(SMPLX_E_ARG, "bad argument");
+    std::string text;
+    for (size_t b = 0; b < s->bodies.size(); ++b) {
+        text += s->bodies[b].id + " " + s->bodies[b].link + "\n";
+        if (first_node) first_node[b] = s->bodies[b].first;
+        if (nnodes) nnodes[b] = s->bodies[b].count;
+    }
+    if (cap > 0) { std::strncpy(names, text.c_str(), cap - 1); names[cap - 1] = 0; }
+    return (int)s->bodies.size();
+}
+
+int smplx_attached_nodes(const smplx_space* s, double* xyzr, int32_t* left, int32_t* right)
+{
+    if (!s) return set_error(SMPLX_E_ARG, "null space");
+    int nn = 0;
+    for (const smplx_space::Body& b : s->bodies) nn += b.count;
+    if ((xyzr || left || right) && nn > 0) {
+        std::vector<SmplxNode> nodes((size_t)nn);
+        HIP_TRY(hipMemcpy(nodes.data(), s->d_bodies->nodes, sizeof(SmplxNode) * nn, hipMemcpyDeviceToHost));
+        for (int i = 0; i < nn; ++i) {
+            if (xyzr) for (int k = 0; k < 3; ++k) xyzr[4 * i + k] = nodes[i].c[k];
+            if (xyzr) xyzr[4 * i + 3] = nodes[i].r;
+            if (left) left[i] = nodes[i].left;
+            if (right) right[i] = nodes[i].right;
+        }
+    }
+    return nn;
+}
+
+int smplx_cc_attached_positions(smplx_space* s, const double* q, int n, double* out)
+{
+    if (!s || !q || !out || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (!sane_values(q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    int nn = 0;
+    for (const smplx_space::Body& b : s->bodies) nn += b.count;
+    if (n == 0 || nn == 0) return SMPLX_OK;
+    int e;
+    const size_t cnt = (size_t)n * nn * 3;
+    if ((e = s->batch.b_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->b_sq.reserve(cnt))) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    KLAUNCH(s, K_ATTACHED_POSITIONS, k_attached_positions, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes, s->stream,
+            s->d_space, s->batch.b_q.p, n, s->b_sq.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, s->b_sq.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SMPLX_OK;
+}
+
 static int finish_goal(smplx_space* s)
 {
     for (int a = 0; a < 3; ++a) s->hs.goal.xyz[a] = s->goal_xyz[a];
@@ -1620,6 +1817,7 @@ static int finish_goal(smplx_space* s)
     if (int e = run_bfs(s, s->goal_xyz)) return e;
     s->goal_set = true;
     s->grid_epoch = s->grid->epoch;
+    s->body_epoch_goal = s->body_epoch;
     // a new goal starts a new query: the state table restarts (ids are per query)
     reset_lattice(s);
     // heuristic of the goal id = BFS cost at the goal pose's cell (manip_lattice.cpp:1176-1190)
@@ -1949,6 +2147,7 @@ int smplx_get_succs(smplx_space* s, int id, int32_t* succs, int32_t* costs, int 
     if (!s || !n) return set_error(SMPLX_E_ARG, "null argument");
     if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
     if (s->grid->epoch != s->grid_epoch) return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
+    if (s->body_epoch != s->body_epoch_goal) return set_error(SMPLX_E_STATE, kBodiesChanged);
     if (int e = pull_lattice(s)) return e;
     if (!s->plain_mode) {
         // first GetSuccs from outside: start mirroring the caller's g-values (the start has g = 0, arastar.cpp:172-176)
@@ -2618,6 +2817,7 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
         if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
         if (s->start_id < 0) return set_error(SMPLX_E_STATE, "start not set");
         if (s->grid->epoch != s->grid_epoch) return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
+        if (s->body_epoch != s->body_epoch_goal) return set_error(SMPLX_E_STATE, kBodiesChanged);
     }
     // ---- the device-resident search: one persistent workgroup per query, no host round trips.  Taken
     // whenever the kernel fits the robot (search_host.h); SMPLX_SEARCH=host selects the host-driven loop below, which is
@@ -2698,6 +2898,9 @@ static int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p
         for (int q = 0; q < nq; ++q) { spaces[q]->search_side = side; spaces[q]->search_start = spaces[q]->start_id; }
         return SMPLX_OK;
     }
+    // the host loop's cross-query batches check every row against the leading space's attached bodies: a query with
+    // bodies of its own issues its own batches (the device search reads each query's bodies in its own workgroup)
+    for (int q = 0; q < nq && grouped; ++q) grouped = spaces[q]->bodies.empty();
     if (grouped) {
         // the query table of the cross-query batches (per-row query index -> that query's goal and BFS grid), held by
         // the leading space

@@ -68,6 +68,7 @@ __global__ void k_edge_valid(const SmplxSpaceDev* S, const double* Aq, const dou
 __global__ void k_state_valid(const SmplxSpaceDev* S, const double* Q, int n, unsigned char* out, int* out_lookups);
 __global__ void k_heuristic(const SmplxSpaceDev* S, const double* Q, int n, int* out_h, double* out_xyz);
 __global__ void k_sphere_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
+__global__ void k_attached_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
 __global__ void k_table_insert(const SmplxSpaceDev* S, const SmplxSpaceDev* const* stab, const int* items, int n, int nvars);
 __global__ void k_bfs_metric(SmplxGridDev grid, SmplxBfsDev bfs, const double* xyz, int n, double* out);
 __global__ void k_bfs_init(SmplxGridDev g, int wall_thr, int nbx, int nby, int nbz, int* dist);

@@ -395,6 +395,7 @@ bool compile_robot_text(const char* text, HostModel& m)
             J.on_chain = 0;
             dfs_of_file[fj] = D.njoints;
             m.joint_names.push_back(joints[fj].name);
+            m.child_links.push_back(joints[fj].child);
             m.joint_k.push_back(k_file[fj]);
             m.file_joint_index.push_back(fj);
             ++D.njoints;
@@ -403,6 +404,8 @@ bool compile_robot_text(const char* text, HostModel& m)
         }
         if (my_slot >= 0) --free_slot;
     };
+    m.root_link = links[0];
+    m.group_links = group_links;
     visit(0, true);
     if (!ok) return fail("too many joints");
     if (D.njoints != nj) return fail("some joints are not reachable from the root link " + links[0]);
@@ -519,6 +522,20 @@ bool compile_robot_text(const char* text, HostModel& m)
         l = joints[fj].parent_link;
     }
     return true;
+}
+
+void build_sphere_tree(const double* xyzr, int n, std::vector<SmplxNode>& out)
+{
+    std::vector<SphereRow> rows((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        rows[i].c[0] = xyzr[4 * i]; rows[i].c[1] = xyzr[4 * i + 1]; rows[i].c[2] = xyzr[4 * i + 2];
+        rows[i].r = xyzr[4 * i + 3];
+    }
+    out.clear();
+    if (n <= 0) return;
+    TreeBuilder tb(rows);
+    tb.build(0, n);
+    out = tb.out;
 }
 
 int sphere_threshold(double radius, double padding, double res, int dmax_sqrd)

@@ -19,11 +19,18 @@ struct HostModel {
     std::vector<double> joint_k;              // motion-sphere factor per joint (depth-first order)
     std::vector<int> file_joint_index;        // depth-first position -> index in the file's joint list
     std::string planning_link;
+    std::string root_link;                    // the link no joint leads to
+    std::vector<std::string> child_links;     // depth-first order: the child link of each joint ("link j")
+    std::vector<std::string> group_links;     // the collision group, in the file's order
     std::string error;
 };
 
 // returns false and sets m.error on malformed input or when a limit of device_types.h is exceeded
 bool compile_robot_text(const char* text, HostModel& m);
+
+// bounding sphere tree of n spheres (xyzr[4 n], given order) as a link's is built (base_collision_models.cpp:337-444):
+// post-order, root last, tree-local child indices, thresholds unset
+void build_sphere_tree(const double* xyzr, int n, std::vector<SmplxNode>& out);
 
 // smallest squared cell distance i in [0, dmax_sqrd] with (res*sqrt(i))^2 >= (r+pad)^2, else dmax_sqrd+1:
 // the integer form of CheckSphereCollision (collision_operations.h:67-77) over the sqrt table of

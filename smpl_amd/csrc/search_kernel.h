@@ -485,6 +485,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
     constexpr bool RS = false;
 #endif
     ThreadLds L = setup_lds(S, smem, &Mv, book0, !RS);        // per-thread scratch for the config waves only (nobody else walks a chain through LDS)
+    Mv.bodies = Sq->bodies;                                   // attached bodies are the query's own
     const ModelLds* M = &Mv;
     const SmplxGridDev grid = S->grid;
     const SmplxBfsDev bfs = Sq->bfs;

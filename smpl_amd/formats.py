@@ -165,3 +165,17 @@ def urdf_to_robot_text(urdf_xml: str, group_name: str, group_links, planning_joi
     out.append("planning_joints " + " ".join(planning_joints))
     out.append("planning_link " + planning_link)
     return "\n".join(out) + "\n"
+
+
+def box_spheres(center, size, pitch, radius):
+    """Spheres of one radius on a regular grid that spans a box, corners included, at most `pitch` apart (centre and size
+    in a link's frame, metres): n x (x, y, z, r) for Space.attach_body.  Not the reference's mesh voxeliser
+    (attached_bodies_collision_model.cpp:264-313 voxelises the shape's surface): a plain filled box."""
+    import math
+    import numpy as np
+    axes = []
+    for c, s in zip(center, size):
+        k = int(math.ceil(s / pitch - 1e-9)) + 1 if s > 0 else 1     # a flat side: one layer
+        axes.append(c - s / 2 + np.arange(k) * (s / (k - 1)) if k > 1 else np.array([float(c)]))
+    g = np.stack(np.meshgrid(*axes, indexing="ij"), -1).reshape(-1, 3)
+    return np.hstack([g, np.full((len(g), 1), float(radius))])
