@@ -518,6 +518,9 @@ struct ExpandWork {
     int32_t* edge_w;
     int32_t* edge_lookups;
     unsigned char* edge_bad;
+    unsigned long long* succ_eval;   // successor role of k_pipe_configs: heuristic | table id << 32, per edge
+    unsigned char* succ_goal;        // ... its goal bit
+    int32_t* succ_coord;             // ... and its coordinates (out_coord is written by k_pipe_finish, for valid edges only)
     int32_t* work_count;
     unsigned long long* work;   // 64-bit items: edge | waypoint << 32 | waypoint count << 48
     int capacity;
@@ -525,14 +528,14 @@ struct ExpandWork {
 
 inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
-size_t expand_work_bytes(int B, int M)
+size_t expand_work_bytes(int B, int M, int N)
 {
     const size_t b = (size_t)B, bm = (size_t)B * M;
-    return align256(b * 8) + align256(b * 4) + align256(b) + align256(bm * 4) + align256(bm * 4) + align256(bm) + 2048 +
-           align256(bm * 16 * 8);
+    return align256(b * 8) + align256(b * 4) + align256(b) + align256(bm * 4) + align256(bm * 4) + align256(bm) + align256(bm * 8) + align256(bm) + align256(bm * N * 4) +
+           2048 + align256(bm * 16 * 8);
 }
 
-ExpandWork carve_work(void* base, int B, int M)
+ExpandWork carve_work(void* base, int B, int M, int N)
 {
     unsigned char* w = (unsigned char*)base;
     const size_t b = (size_t)B, bm = (size_t)B * M;
@@ -543,6 +546,9 @@ ExpandWork carve_work(void* base, int B, int M)
     k.edge_w = (int32_t*)w; w += align256(bm * 4);
     k.edge_lookups = (int32_t*)w; w += align256(bm * 4);
     k.edge_bad = w; w += align256(bm);
+    k.succ_eval = (unsigned long long*)w; w += align256(bm * 8);
+    k.succ_goal = w; w += align256(bm);
+    k.succ_coord = (int32_t*)w; w += align256(bm * N * 4);
     k.work_count = (int32_t*)w; w += 2048;   // 8 shard counters + deferred count, one 128-byte line each
     k.work = (unsigned long long*)w;
     k.capacity = (int)std::min<size_t>(bm * 16, (size_t)1 << 30) / 8 * 8;
@@ -678,7 +684,7 @@ struct ExpandArgs {
     int32_t* h = nullptr;
     int32_t* cost = nullptr;
     int32_t* lookups = nullptr;
-    void* work = nullptr;                       // expand_work_bytes(B, M)
+    void* work = nullptr;                       // expand_work_bytes(B, M, N)
     unsigned long long* counters = nullptr;     // per-block tallies, or null
     hipStream_t stream = nullptr;
     const SmplxSpaceDev* const* stab = nullptr; // cross-query batch: query table ...
@@ -713,7 +719,7 @@ ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool forc
 int launch_expand(smplx_space* s, const ExpandArgs& a)
 {
     const int B = a.B;
-    ExpandWork k = carve_work(a.work, B, s->M);
+    ExpandWork k = carve_work(a.work, B, s->M, s->N);
     int32_t* d_id = a.k5 ? a.k5->d_id : nullptr;
     SmplxCompactDev cmp;
     std::memset(&cmp, 0, sizeof(cmp));
@@ -764,15 +770,16 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
                            k.work, k.work_count, k.capacity, a.stab, a.state_q);
         if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
+        // behind the bc collision blocks: one successor thread per edge (dense: it leaves at once where setup's flag is not 0)
         const int bc = blocks_for((long long)B + (long long)B * s->M * 3, SMPLX_BLOCK);
-        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, norefs, B,
                            a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
-                           k.capacity);
+                           k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal);
         if (ev) (void)hipEventRecord(ev[1], a.stream);
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
         KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
                            k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, a.flags, a.coord, a.sq, a.h,
-                           a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp);
+                           a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp, k.succ_eval, k.succ_goal, k.succ_coord);
         if (ev) (void)hipEventRecord(ev[2], a.stream);
     }
     HIP_TRY(hipGetLastError());
@@ -784,7 +791,7 @@ int reserve_expand(smplx_space* s, int B)
     const size_t BM = (size_t)B * s->M;
     int e;
     if ((e = s->batch.b_q.reserve((size_t)B * s->N))) return e;
-    if ((e = s->batch.b_work.reserve(expand_work_bytes(B, s->M)))) return e;
+    if ((e = s->batch.b_work.reserve(expand_work_bytes(B, s->M, s->N)))) return e;
     if ((e = s->b_flags.reserve(BM))) return e;
     if ((e = s->b_coord.reserve(BM * s->N))) return e;
     if ((e = s->b_sq.reserve(BM * s->N))) return e;
@@ -953,7 +960,7 @@ int issue_frontier(smplx_space* lead, FrontierBatch& fb, smplx_space* const* spa
     const size_t staged = total * N + (fb.ins_items.size() + 1) / 2;   // doubles: the parents, then the inserts
     const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
     int e;
-    if ((e = fb.b_q.reserve(staged)) || (e = fb.p_q.reserve(staged)) || (e = fb.b_work.reserve(expand_work_bytes(B, M))) ||
+    if ((e = fb.b_q.reserve(staged)) || (e = fb.p_q.reserve(staged)) || (e = fb.b_work.reserve(expand_work_bytes(B, M, (int)N))) ||
         (e = fb.b_cost.reserve(BM)) || (e = fb.b_lookups.reserve(BM)) || (e = fb.b_out.reserve(out_bytes)) ||
         (e = fb.p_out.reserve(out_bytes)))
         return e;
@@ -1964,7 +1971,7 @@ int smplx_expand_batch(smplx_space* s, const double* q, int B, uint8_t* flags, i
 size_t smplx_expand_work_bytes(const smplx_space* s, int B)
 {
     if (!s || B <= 0) return 0;
-    return expand_work_bytes(B, s->M);
+    return expand_work_bytes(B, s->M, s->N);
 }
 
 int smplx_expand_batch_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,

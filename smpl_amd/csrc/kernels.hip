@@ -1567,8 +1567,16 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
 //   k_pipe_setup   per (state, primitive): gating, successor joint values, limits, waypoint count;
 //                  claims a range of the work list with one atomic per wave (ballot + prefix count)
 //   k_pipe_configs per work item: one configuration against the grid and the link pairs;
-//                  items [0, B) are the states themselves (waypoint 0 of every edge)
-//   k_pipe_finish  per (state, primitive): verdict, discretisation, goal test, heuristic, cost
+//                  items [0, B) are the states themselves (waypoint 0 of every edge).
+//                  Behind those blocks, in blocks of their own, one thread per (state, primitive): the
+//                  successor of an edge that passed the limits test -- discretisation, state-table id,
+//                  planning-link FK, goal test, heuristic -- which needs no verdict and so runs beside
+//                  the collision check instead of behind it (results, coordinates included, in the
+//                  caller's work buffer: nothing a caller can see is written before the verdict)
+//   k_pipe_finish  per (state, primitive): verdict from the configurations' results, joined with what
+//                  the successor role left; cost, outputs, compact stream, tallies.  A colliding edge
+//                  keeps nothing of its successor's evaluation.
+//                  Stages the model only for a block that holds a deferred edge.
 // Booleans, coordinates, heuristics and costs are identical to k_expand.  Without the serial
 // early exit a colliding edge has all its waypoints examined, so the lookup tally of an INVALID
 // edge can exceed the reference's; for valid edges it is identical.
@@ -1724,13 +1732,95 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     }
 }
 
+// What the verdict of an edge does not decide: discretisation, state-table id, planning-link FK, goal test, heuristic
+// (manip_lattice.cpp:1496-1535 for a successor that passed the limits test).  Needs the successor's joint values and
+// the query's goal, BFS grid and table only, all final when k_pipe_setup ends.  sc: where the coordinates go.
+__device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, const SmplxSpaceDev* __restrict__ Sq,
+                                               const SmplxGridDev& grid, const double* __restrict__ sq, int* __restrict__ sc,
+                                               bool want_id, int& h, int& id, bool& is_goal)
+{
+    const int nv = MV_NVARS(M);
+    const SmplxBfsDev bfs = Sq->bfs;
+    MV_UNROLL
+    for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
+    // K5: the table lookup only needs the coordinates; issued here, its probe lands behind the planning-link FK
+    id = want_id ? table_lookup<false>(Sq->table, sc, nv) : -1;
+    double p[3];
+    planning_fk(M, sq, p);
+    if (Sq->goal.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
+        is_goal = true;
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v)
+            if (fabs((double)(sc[v] - Sq->goal.coord[v])) > Sq->goal.angle_tol[v]) is_goal = false;
+    } else {                                      // XYZ goal :1672-1687
+        is_goal = fabs(p[0] - Sq->goal.xyz[0]) <= Sq->goal.xyz_tol[0] &&
+                  fabs(p[1] - Sq->goal.xyz[1]) <= Sq->goal.xyz_tol[1] &&
+                  fabs(p[2] - Sq->goal.xyz[2]) <= Sq->goal.xyz_tol[2];
+    }
+    int c[3];
+    world_to_cell(grid, p, c);
+    h = bfs_cost_to_goal(bfs, c);
+}
+
+// Successor role of k_pipe_configs: the blocks behind the cfg_blocks collision blocks, one thread per edge.  An edge whose
+// flag is 0 after k_pipe_setup (active, within limits, not deferred; W == 0 included) has its successor evaluated here,
+// beside the collision check instead of behind it; k_pipe_finish joins the result with the verdict.  A whole wave has
+// this one role, and it is shorter than a configuration wave (no sphere trees, one chain).
+__device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restrict__ S, int B, int cfg_blocks,
+                                                    const unsigned char* __restrict__ out_flags, const double* __restrict__ out_q,
+                                                    int* __restrict__ succ_coord, const SmplxSpaceDev* const* __restrict__ stab,
+                                                    const unsigned short* __restrict__ state_q, bool want_id,
+                                                    unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal,
+                                                    unsigned char* smem)
+{
+    const int nprims = S->actions.nprims;
+    const long long tid = (long long)((int)blockIdx.x - cfg_blocks) * BLOCK + threadIdx.x;
+    // as in the collision blocks: the flag (and, per-robot build, the joint values) are fetched BEFORE the model is staged
+    const bool live = tid < (long long)B * nprims && out_flags[tid] == 0;
+#ifdef SMPLX_CONST_MODEL
+    double qv[CM_NV];
+    if (live) {
+#pragma unroll
+        for (int v = 0; v < CM_NV; ++v) qv[v] = out_q[tid * CM_NV + v];
+    }
+#endif
+    const ModelLds Mv = setup_model_only(S, smem);
+    const ModelLds* M = &Mv;
+    if (!live) return;
+#ifndef ABL_NO_SUCC
+    const int nv = MV_NVARS(M);
+    const int si = (int)(tid / nprims);
+    const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;   // per-query goal, BFS grid and table in a cross-query batch
+    const SmplxGridDev grid = S->grid;
+#ifdef SMPLX_CONST_MODEL
+    const double* sq = qv;
+#else
+    const double* sq = out_q + tid * nv;
+#endif
+    int h, id;
+    bool is_goal;
+    pipe_successor(M, Sq, grid, sq, succ_coord + tid * nv, want_id, h, id, is_goal);
+    succ_eval[tid] = (unsigned long long)(unsigned int)h | ((unsigned long long)(unsigned int)id << 32);   // one 8-byte store
+    succ_goal[tid] = is_goal ? 1 : 0;
+#endif
+}
+
 extern "C" __global__ void __launch_bounds__(BLOCK, 2)   // >= 2 waves per SIMD: at most 256 VGPRs, whichever compiler builds it
 k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
                const double* __restrict__ out_q, const int* __restrict__ edge_w, int* __restrict__ edge_lookups,
                unsigned char* __restrict__ edge_bad, int* __restrict__ state_lookups, unsigned char* __restrict__ state_bad,
-               const unsigned long long* __restrict__ work, const int* __restrict__ work_count, int capacity)
+               const unsigned long long* __restrict__ work, const int* __restrict__ work_count, int capacity, int cfg_blocks,
+               const unsigned char* __restrict__ out_flags, int* __restrict__ succ_coord,
+               const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q, int want_id,
+               unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal)
 {
     extern __shared__ __align__(16) unsigned char smem[];
+    // the grid is cfg_blocks collision blocks, dispatched first (they hold the long waves), then one successor thread
+    // per edge in blocks of their own
+    if ((int)blockIdx.x >= cfg_blocks) {
+        pipe_successor_role(S, B, cfg_blocks, out_flags, out_q, succ_coord, stab, state_q, want_id != 0, succ_eval, succ_goal, smem);
+        return;
+    }
 #ifdef SMPLX_CONST_MODEL
     constexpr bool RS = true;      // saved link transforms in registers (as k_state_valid): LDS per block without the slots, which
                                    // is what several batches in flight, or one large one, share a CU by
@@ -1754,7 +1844,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
     // counts, model header, model bytes, work item, joint values -- in front of ~10 us of work: the item and the joint
     // values of its edge are fetched BEFORE the model is staged, so that they travel together with the model bytes
     // (5 round trips -> 3).
-    if (total <= (long long)gridDim.x * BLOCK) {
+    if (total <= (long long)cfg_blocks * BLOCK) {
         const int nprims = S->actions.nprims;
         constexpr int nv = CM_NV;
         const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
@@ -1813,7 +1903,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
     const SmplxGridDev grid = S->grid;
     const int nprims = S->actions.nprims;
     const int nv = MV_NVARS(M);
-    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (long long)gridDim.x * BLOCK) {
+    for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (long long)cfg_blocks * BLOCK) {
         EdgeRef e;
         int lk = 0;
         if (i < B) {   // the state itself: waypoint 0 of each of its edges
@@ -1852,101 +1942,99 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
               int* __restrict__ out_h, int* __restrict__ out_cost, int* __restrict__ out_lookups,
               unsigned long long* __restrict__ counters, const double* __restrict__ goal_dist,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
-              int* __restrict__ out_id, SmplxCompactDev cmp)
+              int* __restrict__ out_id, SmplxCompactDev cmp, const unsigned long long* __restrict__ succ_eval,
+              const unsigned char* __restrict__ succ_goal, const int* __restrict__ succ_coord)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmplxActionsDev& A = S->actions;
-    const SmplxGridDev grid = S->grid;
     const int nprims = A.nprims;
+#ifdef SMPLX_CONST_MODEL
+    constexpr int nv = CM_NV;
+#else
+    const int nv = S->model.nvars;   // (the model is not staged here)
+#endif
     const long long tid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const bool in_range = tid < (long long)B * nprims;
     int flags = SMPLX_F_INACTIVE, lookups = 0, performed = 0, evaluated = 0;
     int succ_id = -1, succ_h = 0;   // K5: id of the successor's coordinate in the device state table
-    int early_id = -1;
-    bool have_early = false;
     int ncfg = 0, slk = 0;   // configurations k_pipe_configs checked for this edge / lookups of the state's own check
-    if (in_range) flags = out_flags[tid];
-    // the model and the per-thread scratch are only needed by edges that overflowed the work list (normally none)
-    ModelLds Mv;
-    ThreadLds L;
-#if defined(SMPLX_CONST_MODEL) && !CM_NEEDS_JOINTS
-    if (__syncthreads_or(flags & SMPLX_F_DEFERRED)) {
-        L = setup_lds(S, smem, &Mv);
-    } else {
-        Mv = setup_model_only(S, smem);
-        L = ThreadLds();
-    }
+    // everything the verdict needs, in ONE round of independent loads (rows that setup or the successor role did not
+    // write are read and ignored)
+    int si = 0, pi = 0, W = 0, e_lk = 0, e_bad = 0, s_lk = 0, s_bad = 0, s_goal = 0;
+    unsigned long long se = 0;
+#ifdef SMPLX_CONST_MODEL
+    int s_coord[CM_NV];   // the successor's coordinates, fetched with the rest
+#define PIPE_SUCC_COORD(v) s_coord[v]
 #else
-    L = setup_lds(S, smem, &Mv);
+#define PIPE_SUCC_COORD(v) succ_coord[tid * nv + (v)]
 #endif
-    const ModelLds* M = &Mv;
+    bool deferred = false;
     if (in_range) {
-        const int si = (int)(tid / nprims);
-        const int pi = (int)(tid - (long long)si * nprims);
-        const int nv = MV_NVARS(M);
-        const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
-        const SmplxBfsDev bfs = Sq->bfs;
-        if (pi == 0) { slk = state_lookups[si]; ncfg = 1; }
-        int h = 0, cost = 0;
-        bool deferred = false;
+        si = (int)(tid / nprims);
+        pi = (int)(tid - (long long)si * nprims);
+        flags = out_flags[tid];
+        W = edge_w[tid];
+        e_lk = edge_lookups[tid];
+        e_bad = edge_bad[tid];
+        s_lk = state_lookups[si];
+        s_bad = state_bad[si];
+        se = succ_eval[tid];
+        s_goal = succ_goal[tid];
+#ifdef SMPLX_CONST_MODEL
+#pragma unroll
+        for (int v = 0; v < nv; ++v) s_coord[v] = succ_coord[tid * nv + v];
+#endif
+    }
+    if (__syncthreads_or(flags & SMPLX_F_DEFERRED)) {
+        // the model and the per-thread scratch are only needed by edges that overflowed the work list (normally none):
+        // such an edge is walked whole by this thread
+        ModelLds Mv;
+        const ThreadLds L = setup_lds(S, smem, &Mv);
         if (flags & SMPLX_F_DEFERRED) {
-            // the edge's waypoints did not fit the work list (normally none do not): this thread walks the whole edge
-            const EdgeTally t = expand_edge(M, L, S, Sq, grid, Q, refs, tid, goal_dist, state_bad[si] == 0, state_lookups[si],
+            const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
+            const SmplxGridDev grid = S->grid;
+            if (pi == 0) { slk = s_lk; ncfg = 1; }
+            const EdgeTally t = expand_edge(&Mv, L, S, Sq, grid, Q, refs, tid, goal_dist, s_bad == 0, s_lk,
                                             out_flags, out_coord, out_q, out_h, out_cost, out_lookups);
             flags = t.flags; lookups = t.lookups; performed = t.performed; evaluated = t.evaluated;
+            succ_h = out_h[tid];
+            // K5: getHashEntry on the device copy of the state table (manip_lattice.cpp:1302-1316).  The id is only a
+            // hint to the host (it skips its own lookup); ids are still ASSIGNED on the host, in commit order.
+            if (out_id) {
+                if (flags & SMPLX_F_VALID) succ_id = table_lookup<false>(Sq->table, out_coord + tid * nv, nv);
+                out_id[tid] = succ_id;
+            }
             deferred = true;
         }
-        if (!deferred && !(flags & SMPLX_F_INACTIVE)) evaluated = 1;
-        if (!deferred && flags == 0) {
-            const int W = edge_w[tid];
+    }
+    if (in_range && !deferred) {
+        if (pi == 0) { slk = s_lk; ncfg = 1; }
+        int h = 0, cost = 0;
+        if (!(flags & SMPLX_F_INACTIVE)) evaluated = 1;
+        if (flags == 0) {
             if (W > 0) ncfg += W - 1;
-            performed = edge_lookups[tid];
-            const bool ok = (W == 0) || (state_bad[si] == 0 && edge_bad[tid] == 0);
-            lookups = performed + (W > 0 ? state_lookups[si] : 0);
+            performed = e_lk;
+            const bool ok = (W == 0) || (s_bad == 0 && e_bad == 0);
+            lookups = performed + (W > 0 ? s_lk : 0);
             if (!ok) {
                 flags = SMPLX_F_COLLISION;
             } else {
-                const double* sq = out_q + tid * nv;
-                int* sc = out_coord + tid * nv;
+                // the successor role of k_pipe_configs evaluated it beside the collision check; out_coord is written for a
+                // valid edge only, as before (a colliding edge leaves the caller's row alone)
                 MV_UNROLL
-                for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
-                // K5: the table lookup only needs the coordinates; issued here, its probe lands behind the planning-link FK
-                if (out_id) { early_id = table_lookup<false>(Sq->table, sc, nv); have_early = true; }
-                double p[3];
-                planning_fk(M, sq, p);
-                bool is_goal;
-                if (Sq->goal.type == SMPLX_GOAL_JOINT) {
-                    is_goal = true;
-                    MV_UNROLL
-                    for (int v = 0; v < nv; ++v)
-                        if (fabs((double)(sc[v] - Sq->goal.coord[v])) > Sq->goal.angle_tol[v]) is_goal = false;
-                } else {
-                    is_goal = fabs(p[0] - Sq->goal.xyz[0]) <= Sq->goal.xyz_tol[0] &&
-                              fabs(p[1] - Sq->goal.xyz[1]) <= Sq->goal.xyz_tol[1] &&
-                              fabs(p[2] - Sq->goal.xyz[2]) <= Sq->goal.xyz_tol[2];
-                }
-                int c[3];
-                world_to_cell(grid, p, c);
-                h = bfs_cost_to_goal(bfs, c);
+                for (int v = 0; v < nv; ++v) out_coord[tid * nv + v] = PIPE_SUCC_COORD(v);
+                h = (int)(unsigned int)(se & 0xFFFFFFFFull);
+                if (out_id) succ_id = (int)(unsigned int)(se >> 32);
                 cost = A.cost[pi];
-                flags = SMPLX_F_VALID | (is_goal ? SMPLX_F_GOAL : 0);
+                flags = SMPLX_F_VALID | (s_goal ? SMPLX_F_GOAL : 0);
             }
         }
-        if (!deferred) {
-            out_flags[tid] = (unsigned char)flags;
-            out_h[tid] = h;
-            out_cost[tid] = cost;
-            out_lookups[tid] = lookups;
-        } else {
-            h = out_h[tid];
-        }
+        out_flags[tid] = (unsigned char)flags;
+        out_h[tid] = h;
+        out_cost[tid] = cost;
+        out_lookups[tid] = lookups;
         succ_h = h;
-        // K5: getHashEntry on the device copy of the state table (manip_lattice.cpp:1302-1316).  The id is only a
-        // hint to the host (it skips its own lookup); ids are still ASSIGNED on the host, in commit order.
-        if (out_id) {
-            if (flags & SMPLX_F_VALID) succ_id = have_early ? early_id : table_lookup<false>(Sq->table, out_coord + tid * nv, nv);
-            out_id[tid] = succ_id;
-        }
+        if (out_id) out_id[tid] = succ_id;
     }
     // K5: validity compaction with wavefront ballots.  A valid successor leaves 8 bytes in region A; one whose
     // coordinate the table does not know (or a goal successor, whose own joint values extractPath reports) also a full
@@ -1984,7 +2072,6 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
             cmp.rec_a[2 * (size_t)ia] = succ_id;
             cmp.rec_a[2 * (size_t)ia + 1] = pi | ((flags & SMPLX_F_GOAL) ? 0x100 : 0) | (si << 9);
             if (is_b) {
-                const int nv = MV_NVARS(M);
                 unsigned char* rb = cmp.rec_b + (size_t)ib * cmp.rec_b_bytes;
                 int* ri = (int*)rb;
                 double* rq = (double*)(rb + (size_t)((nv + 2) / 2 * 2) * 4);
@@ -1999,6 +2086,7 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
         const unsigned long long m_valid = __ballot((flags & SMPLX_F_VALID) != 0);
         tally_block(counters, __popcll(m_eval), __popcll(m_valid), lookups, performed, ncfg, slk);
     }
+#undef PIPE_SUCC_COORD
 }
 
 // ---------------------------------------------------------------------------------------------
