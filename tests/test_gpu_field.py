@@ -4,24 +4,10 @@ the test scenes at BASELINE sizes, and through a planner query that runs on a GP
 import numpy as np
 import pytest
 
+from noncubic_cases import brute_force as _brute_force
 from smpl_amd import scenes
 
 pytestmark = pytest.mark.gpu
-
-
-def _brute_force(occ, dmax):
-    """Squared distance of every interior cell to the nearest occupied or border cell, capped (O(cells x obstacles))."""
-    nx, ny, nz = occ.shape
-    pad = np.ones((nx + 2, ny + 2, nz + 2), bool)
-    pad[1:-1, 1:-1, 1:-1] = occ
-    obs = np.argwhere(pad).astype(np.int64) - 1          # interior coordinates; the border layer sits at -1 and n
-    out = np.zeros(occ.shape, np.int64)
-    cells = np.argwhere(np.ones(occ.shape, bool)).astype(np.int64)
-    for k in range(0, cells.shape[0], 2048):
-        c = cells[k:k + 2048]
-        d = ((c[:, None, :] - obs[None, :, :]) ** 2).sum(axis=2).min(axis=1)
-        out[c[:, 0], c[:, 1], c[:, 2]] = d
-    return np.minimum(out, dmax * dmax).astype(np.int32)
 
 
 def test_field_equals_bruteforce_on_small_grids():
