@@ -550,6 +550,12 @@ class Space:
         lib().smplx_test_set_search_helper.argtypes = [C.c_void_p, C.c_int]
         _chk(lib().smplx_test_set_search_helper(self.h, 1 if on else 0))
 
+    def set_pipe_prep(self, on):
+        """Test hook (csrc/test_hooks.h): the pipeline with k_pipe_prep in a launch of its own (four launches) or, the
+        default, with the goal distance computed inside k_pipe_setup (three)."""
+        lib().smplx_test_set_pipe_prep.argtypes = [C.c_void_p, C.c_int]
+        _chk(lib().smplx_test_set_pipe_prep(self.h, 1 if on else 0))
+
     def set_search_capacity(self, states):
         """Test hook (csrc/test_hooks.h): first capacity of the device search's buffers."""
         lib().smplx_test_set_search_capacity.argtypes = [C.c_void_p, C.c_int]

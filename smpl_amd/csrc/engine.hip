@@ -272,6 +272,13 @@ struct smplx_space {
     std::string specialize_note;   // why the per-robot build is absent, if it is
     bool fused_mode = false;   // SMPLX_SPACE_FUSED: one thread per edge (reference lookup tallies)
     int work_list_items = 0;   // > 0: test hook (test_hooks.h) -- a work list this small, so that the deferred pass is exercised
+    bool pipe_prep = false;    // test hook (test_hooks.h): k_pipe_prep in a launch of its own in front of k_pipe_setup
+    int three_launch_blocks = 0;   // largest k_pipe_setup grid (edge blocks) that runs the three-launch step; 0: not asked yet
+    // Work-list counters of the pipeline (8 shard counters + deferred count, one 128-byte line each): one set per stream
+    // the space has launched a step on.  A set is all-zero whenever no step is in flight on its stream: k_pipe_finish
+    // clears it behind its last reader.  dirty: a launch sequence on it failed part-way, it is cleared before its next use.
+    struct WorkCounters { hipStream_t stream; int32_t* p; bool dirty; };
+    std::vector<WorkCounters> work_counters;
     int small_batch_max = 512;     // batches up to this many states take the single-launch kernel (SMPLX_SPACE_NO_SMALL_KERNEL disables)
     double small_latency_limit = 70e-6;   // SMPLX_SMALL_KERNEL=always lifts it, =never disables the single-launch kernel
     DevBuf<unsigned long long> b_counters;
@@ -521,7 +528,7 @@ struct ExpandWork {
     unsigned long long* succ_eval;   // successor role of k_pipe_configs: heuristic | table id << 32, per edge
     unsigned char* succ_goal;        // ... its goal bit
     int32_t* succ_coord;             // ... and its coordinates (out_coord is written by k_pipe_finish, for valid edges only)
-    int32_t* work_count;
+    int32_t* work_count;        // NOT in the caller's scratch: the stream's counter set (smplx_space::work_counters)
     unsigned long long* work;   // 64-bit items: edge | waypoint << 32 | waypoint count << 48
     int capacity;
 };
@@ -549,7 +556,7 @@ ExpandWork carve_work(void* base, int B, int M, int N)
     k.succ_eval = (unsigned long long*)w; w += align256(bm * 8);
     k.succ_goal = w; w += align256(bm);
     k.succ_coord = (int32_t*)w; w += align256(bm * N * 4);
-    k.work_count = (int32_t*)w; w += 2048;   // 8 shard counters + deferred count, one 128-byte line each
+    k.work_count = nullptr; w += 2048;       // (where the counters used to live: the size callers allocate stays what it was)
     k.work = (unsigned long long*)w;
     k.capacity = (int)std::min<size_t>(bm * 16, (size_t)1 << 30) / 8 * 8;
     return k;
@@ -716,6 +723,21 @@ ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool forc
     return s->fused_mode ? ExpandPath::Fused : ExpandPath::Pipeline;
 }
 
+// the work-list counters of `stream`: allocated and zeroed, once and synchronously, the first time the stream is seen
+int work_counters_for(smplx_space* s, hipStream_t stream, smplx_space::WorkCounters** out)
+{
+    for (smplx_space::WorkCounters& w : s->work_counters)
+        if (w.stream == stream) { *out = &w; return SMPLX_OK; }
+    int32_t* p = nullptr;
+    HIP_TRY(hipMalloc((void**)&p, 2048));
+    hipError_t e = hipMemsetAsync(p, 0, 2048, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { (void)hipFree(p); return set_error(SMPLX_E_HIP, std::string("work-list counters: ") + hipGetErrorString(e)); }
+    s->work_counters.push_back({stream, p, false});
+    *out = &s->work_counters.back();
+    return SMPLX_OK;
+}
+
 int launch_expand(smplx_space* s, const ExpandArgs& a)
 {
     const int B = a.B;
@@ -763,11 +785,30 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     } else {
         const size_t lm = s->blob_bytes;
         ++s->pipe_launches;
-        KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
-                           k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins);
-        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+        smplx_space::WorkCounters* wc = nullptr;
+        if (int e = work_counters_for(s, a.stream, &wc)) return e;
+        if (wc->dirty) HIP_TRY(hipMemsetAsync(wc->p, 0, 2048, a.stream));
+        wc->dirty = true;   // until the whole sequence is in the stream: k_pipe_finish leaves the set zeroed
+        k.work_count = wc->p;
+        // Three launches.  k_pipe_setup computes the goal distance of the states of each block itself and carries the K5
+        // inserts in extra blocks.  With the test hook, k_pipe_prep does both in a launch of its own, as the step used to.
+        // So it does for a batch whose setup blocks (3 waves each) no longer fit the chip at 4 waves per SIMD in one
+        // round: there the step is bound by throughput, not by the length of the chain, and the goal-distance wave of
+        // every block (one chain per state and block, 50 % more waves) costs more than the launch saves -- measured
+        // at B = 16 384 and 65 536.
+        if (s->three_launch_blocks == 0) {
+            int cus = 0;
+            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) cus = 256;
+            s->three_launch_blocks = cus * 4 * 4 / (SMPLX_SETUP_BLOCK / 64);
+        }
+        const bool pipe_prep = s->pipe_prep || be > s->three_launch_blocks;
+        if (pipe_prep)
+            KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+                               k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins);
+        const int n_ins_setup = pipe_prep ? 0 : n_ins;
+        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be + blocks_for(n_ins_setup, SMPLX_BLOCK)), dim3(pipe_prep ? SMPLX_BLOCK : SMPLX_SETUP_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
                            k.goal_dist, a.flags, a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
-                           k.work, k.work_count, k.capacity, a.stab, a.state_q);
+                           k.work, k.work_count, k.capacity, a.stab, a.state_q, pipe_prep ? 1 : 0, cmp.totals, ins_items, n_ins_setup);
         if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
         // behind the bc collision blocks: one successor thread per edge (dense: it leaves at once where setup's flag is not 0)
@@ -779,7 +820,9 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
         KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
                            k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, a.flags, a.coord, a.sq, a.h,
-                           a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp, k.succ_eval, k.succ_goal, k.succ_coord);
+                           a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp, k.succ_eval, k.succ_goal, k.succ_coord,
+                           k.work_count);
+        wc->dirty = false;
         if (ev) (void)hipEventRecord(ev[2], a.stream);
     }
     HIP_TRY(hipGetLastError());
@@ -1435,6 +1478,7 @@ void smplx_space_destroy(smplx_space* s)
     if (s->d_minus_one) (void)hipFree(s->d_minus_one);
     if (s->d_table) (void)hipFree(s->d_table);
     if (s->d_bodies) (void)hipFree(s->d_bodies);
+    for (smplx_space::WorkCounters& w : s->work_counters) (void)hipFree(w.p);
     (void)search_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
@@ -1451,6 +1495,13 @@ int smplx_test_set_work_list_items(smplx_space* s, int items)
 {
     if (!s || items < 0) return set_error(SMPLX_E_ARG, "bad argument");
     s->work_list_items = items / 8 * 8;
+    return SMPLX_OK;
+}
+
+int smplx_test_set_pipe_prep(smplx_space* s, int on)
+{
+    if (!s) return set_error(SMPLX_E_ARG, "null space");
+    s->pipe_prep = on != 0;
     return SMPLX_OK;
 }
 
@@ -2004,10 +2055,12 @@ int smplx_compact_capacity(const smplx_space* s, int B)
     return SMPLX_CMP_SHARDS * ((nblocks + SMPLX_CMP_SHARDS - 1) / SMPLX_CMP_SHARDS) * SMPLX_BLOCK;   // no sub-region can overflow
 }
 
-int smplx_expand_batch_k5_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,
-                                 int32_t* d_h, int32_t* d_cost, int32_t* d_lookups, int32_t* d_succ_id, int32_t* d_rec_a, int cap_a,
-                                 void* d_rec_b, int cap_b, int32_t* d_block_tab, int32_t* d_totals, void* d_work,
-                                 uint64_t* d_counters, void* stream)
+namespace {
+// smplx_expand_batch_k5_device, plus the states to insert at the head of the step's first kernel (device memory)
+int expand_k5_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,
+                     int32_t* d_h, int32_t* d_cost, int32_t* d_lookups, int32_t* d_succ_id, int32_t* d_rec_a, int cap_a,
+                     void* d_rec_b, int cap_b, int32_t* d_block_tab, int32_t* d_totals, void* d_work,
+                     uint64_t* d_counters, void* stream, const int32_t* d_items, int n_items)
 {
     if (!s || !d_q || !d_flags || !d_coord || !d_succ_q || !d_h || !d_cost || !d_lookups || !d_work || B <= 0)
         return set_error(SMPLX_E_ARG, "bad argument");
@@ -2024,6 +2077,8 @@ int smplx_expand_batch_k5_device(smplx_space* s, const double* d_q, int B, uint8
     K5Out k5;
     k5.d_id = d_succ_id;
     k5.cmp = d_rec_a ? &cmp : nullptr;
+    k5.items = d_items;
+    k5.n_items = n_items;
     ExpandArgs a;
     a.q = d_q; a.B = B;
     a.flags = d_flags; a.coord = d_coord; a.sq = d_succ_q; a.h = d_h; a.cost = d_cost; a.lookups = d_lookups;
@@ -2032,6 +2087,16 @@ int smplx_expand_batch_k5_device(smplx_space* s, const double* d_q, int B, uint8
     a.stream = (hipStream_t)stream;
     a.k5 = &k5;
     return launch_expand(s, a);
+}
+}  // namespace
+
+int smplx_expand_batch_k5_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,
+                                 int32_t* d_h, int32_t* d_cost, int32_t* d_lookups, int32_t* d_succ_id, int32_t* d_rec_a, int cap_a,
+                                 void* d_rec_b, int cap_b, int32_t* d_block_tab, int32_t* d_totals, void* d_work,
+                                 uint64_t* d_counters, void* stream)
+{
+    return expand_k5_device(s, d_q, B, d_flags, d_coord, d_succ_q, d_h, d_cost, d_lookups, d_succ_id, d_rec_a, cap_a, d_rec_b, cap_b,
+                            d_block_tab, d_totals, d_work, d_counters, stream, nullptr, 0);
 }
 
 int smplx_expand_batch_k5(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* coord, double* succ_q, int32_t* h,
@@ -2049,13 +2114,23 @@ int smplx_expand_batch_k5(smplx_space* s, const double* q, int B, uint8_t* flags
     if ((e = s->b_ins.reserve(2 * (size_t)cap_a + 4 * (size_t)nblocks + SMPLX_CMP_TOTALS))) return e;   // A records | block table | totals
     if ((e = s->batch.b_out.reserve(rb * (size_t)cap_b))) return e;                       // B records
     if ((e = table_ensure(s))) return e;
-    if ((e = table_flush(s, s->stream))) return e;
+    // the states committed since the last batch ride with the step's first kernel, behind the parents in the same
+    // buffer, as they do in a search's own batches (issue_frontier)
+    if ((e = table_grow_if_needed(s))) return e;
+    std::vector<int32_t>& items = s->batch.ins_items;   // stays put until the synchronise below
+    items.clear();
+    table_take_pending(s, 0, items);
+    const size_t parent_doubles = (size_t)B * s->N;
+    if ((e = s->batch.b_q.reserve(parent_doubles + (items.size() + 1) / 2))) return e;
     int32_t* d_a = s->b_ins.p;
     int32_t* d_bt = d_a + 2 * (size_t)cap_a;
     int32_t* d_tot = d_bt + 4 * (size_t)nblocks;
-    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * B * s->N, hipMemcpyHostToDevice, s->stream));
-    if ((e = smplx_expand_batch_k5_device(s, s->batch.b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->batch.b_cost.p, s->batch.b_lookups.p,
-                                          s->b_way.p, d_a, cap_a, s->batch.b_out.p, cap_b, d_bt, d_tot, s->batch.b_work.p, nullptr, s->stream))) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * parent_doubles, hipMemcpyHostToDevice, s->stream));
+    if (!items.empty())
+        HIP_TRY(hipMemcpyAsync(s->batch.b_q.p + parent_doubles, items.data(), sizeof(int32_t) * items.size(), hipMemcpyHostToDevice, s->stream));
+    if ((e = expand_k5_device(s, s->batch.b_q.p, B, s->b_flags.p, s->b_coord.p, s->b_sq.p, s->b_h.p, s->batch.b_cost.p, s->batch.b_lookups.p,
+                              s->b_way.p, d_a, cap_a, s->batch.b_out.p, cap_b, d_bt, d_tot, s->batch.b_work.p, nullptr, s->stream,
+                              (const int32_t*)(s->batch.b_q.p + parent_doubles), (int)(items.size() / ((size_t)s->N + 2))))) return e;
     if (flags) HIP_TRY(hipMemcpyAsync(flags, s->b_flags.p, BM, hipMemcpyDeviceToHost, s->stream));
     if (coord) HIP_TRY(hipMemcpyAsync(coord, s->b_coord.p, sizeof(int32_t) * BM * s->N, hipMemcpyDeviceToHost, s->stream));
     if (succ_q) HIP_TRY(hipMemcpyAsync(succ_q, s->b_sq.p, sizeof(double) * BM * s->N, hipMemcpyDeviceToHost, s->stream));

@@ -9,6 +9,7 @@
 #include "device_types.h"
 
 #define SMPLX_BLOCK 128          // 2 waves; per-thread LDS scratch keeps ~4 blocks per CU resident
+#define SMPLX_SETUP_BLOCK (SMPLX_BLOCK + 64)   // threads of a k_pipe_setup block: the edge threads and the goal-distance wave
 #define SMPLX_SEARCH_STATIC_LDS (44 * 1024)   // static LDS of k_search (2 x ExpandLds + SearchLds + header and primitives copies), an upper bound
 #define SMPLX_TALLIES 6           // per-block tallies (tally_block)     // per-thread DFS stack (node indices, one byte each)
 
@@ -40,11 +41,12 @@ __global__ void k_pipe_prep(const SmplxSpaceDev* S, const double* Q, const int64
                             int* work_count,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* cmp_totals,
                             const int* ins_items, int n_ins);
-__global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, const double* goal_dist,
+__global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist,
                              unsigned char* out_flags, double* out_q, int* edge_w, int* edge_lookups,
                              unsigned char* edge_bad, int* state_lookups, unsigned char* state_bad, unsigned long long* work,
                              int* work_count, int capacity,
-                         const SmplxSpaceDev* const* stab, const unsigned short* state_q);
+                         const SmplxSpaceDev* const* stab, const unsigned short* state_q, int have_goal_dist,
+                             int* cmp_totals, const int* ins_items, int n_ins);
 __global__ void k_pipe_configs(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, const double* out_q,
                                const int* edge_w, int* edge_lookups, unsigned char* edge_bad, int* state_lookups,
                                unsigned char* state_bad, const unsigned long long* work, const int* work_count, int capacity,
@@ -57,7 +59,8 @@ __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, const int
                               int* out_h, int* out_cost, int* out_lookups, unsigned long long* counters,
                               const double* goal_dist,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* out_id, SmplxCompactDev cmp,
-                              const unsigned long long* succ_eval, const unsigned char* succ_goal, const int* succ_coord);
+                              const unsigned long long* succ_eval, const unsigned char* succ_goal, const int* succ_coord,
+                              int* work_count);
 __global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist_out,
                               unsigned char* state_bad_out, int* state_lookups_out, unsigned char* out_flags, int* out_coord,
                               double* out_q, int* out_h, int* out_cost, int* out_lookups,

@@ -1319,7 +1319,7 @@ __device__ __forceinline__ ThreadLds setup_lds(const SmplxSpaceDev* __restrict__
 }
 
 // kernels that only need the model (no per-thread scratch)
-__device__ __forceinline__ ModelLds setup_model_only(const SmplxSpaceDev* __restrict__ S, unsigned char* smem)
+__device__ __forceinline__ ModelLds setup_model_only(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, int nthreads = BLOCK)
 {
 #if defined(SMPLX_CONST_MODEL) && !CM_NEEDS_JOINTS
     // per-robot build: the planning-link chain and the per-variable data are literals, nothing is read from LDS
@@ -1327,7 +1327,7 @@ __device__ __forceinline__ ModelLds setup_model_only(const SmplxSpaceDev* __rest
     M.njoints = CM_NJ; M.nvars = CM_NV; M.ntrees = CM_NT;
     return M;
 #else
-    ModelLds M = stage_model(S, smem);
+    ModelLds M = stage_model(S, smem, nthreads);
     __syncthreads();
     return M;
 #endif
@@ -1563,9 +1563,10 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
 // Waypoint-parallel pipeline (default).  The fused k_expand above walks an edge's waypoints one
 // after another inside one thread, which leaves the chip idle at B = 4096 (about 1.6 waves per
 // SIMD, each a serial fp64 chain).  The pipeline spreads the same work over (edge, waypoint) items:
-//   k_pipe_prep    per state: planning-link FK -> metric goal distance
-//   k_pipe_setup   per (state, primitive): gating, successor joint values, limits, waypoint count;
-//                  claims a range of the work list with one atomic per wave (ballot + prefix count)
+//   k_pipe_setup   per block: planning-link FK -> metric goal distance of the (at most BLOCK, 7 at M = 25) states its
+//                  edges belong to, on a wave of its own behind the edge threads, shared through LDS;
+//                  per (state, primitive): gating, successor joint values, limits, waypoint count;
+//                  claims a range of the work list with one atomic per block (prefix count)
 //   k_pipe_configs per work item: one configuration against the grid and the link pairs;
 //                  items [0, B) are the states themselves (waypoint 0 of every edge).
 //                  Behind those blocks, in blocks of their own, one thread per (state, primitive): the
@@ -1580,6 +1581,11 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
 // Booleans, coordinates, heuristics and costs are identical to k_expand.  Without the serial
 // early exit a colliding edge has all its waypoints examined, so the lookup tally of an INVALID
 // edge can exceed the reference's; for valid edges it is identical.
+// k_pipe_prep (per state: the goal distance, in a launch of its own in front of k_pipe_setup) is what the step began
+// with until the distance moved into k_pipe_setup; it stays selectable (test_hooks.h smplx_test_set_pipe_prep) as the
+// reference the three-launch step is compared against.
+// The work-list counters belong to the engine, one set per stream, and are all-zero between steps: block 0 of
+// k_pipe_finish clears them behind their last reader.
 // ---------------------------------------------------------------------------------------------
 
 // work item (64 bits): edge index | waypoint << 32 | waypoint count << 48, so that a configuration thread needs no
@@ -1588,6 +1594,22 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
 #define SMPLX_WORK_BLANK 0xFFFFFFFFFFFFFFFFull
 #define SMPLX_WORK_SHARDS 8
 #define SMPLX_SHARD_STRIDE 32   // ints: one 128-byte line per shard counter
+
+// BfsHeuristic::getMetricGoalDistance of state i (bfs_heuristic.cpp:129-138): one expression for k_pipe_prep and k_pipe_setup
+__device__ __forceinline__ double pipe_goal_dist(const ModelLds* __restrict__ M, const SmplxSpaceDev* __restrict__ S,
+                                                 const SmplxGridDev& grid, const double* __restrict__ Q,
+                                                 const int64_t* __restrict__ refs, int i,
+                                                 const SmplxSpaceDev* const* __restrict__ stab,
+                                                 const unsigned short* __restrict__ state_q)
+{
+    const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;
+    const double* q = Q + (refs ? refs[i] : (int64_t)i) * MV_NVARS(M);
+    double p[3];
+    planning_fk(M, q, p);
+    int c[3];
+    world_to_cell(grid, p, c);
+    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
+}
 
 extern "C" __global__ void __launch_bounds__(BLOCK)
 k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
@@ -1606,86 +1628,133 @@ k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, c
     if (cmp_totals && blockIdx.x == 0)                                   // compaction counters of k_pipe_finish
         for (int k = threadIdx.x; k < SMPLX_CMP_TOTALS; k += BLOCK) cmp_totals[k] = 0;
     if (i >= B) return;
-    const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;
-    const double* q = Q + (refs ? refs[i] : (int64_t)i) * MV_NVARS(M);
-    double p[3];
-    planning_fk(M, q, p);
-    int c[3];
-    world_to_cell(grid, p, c);
-    goal_dist[i] = !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
+    goal_dist[i] = pipe_goal_dist(M, S, grid, Q, refs, i, stab, state_q);
 }
 
-extern "C" __global__ void __launch_bounds__(BLOCK)
+// The part of an edge that the gate does not decide (manip_lattice.cpp:1471-1490 for an active primitive): successor
+// joint values into sq, limits, waypoint count.  Returns the edge's flags (SMPLX_F_INACTIVE: the primitive has no action
+// for this goal type) and W.
+__device__ __forceinline__ int pipe_edge_values(const ModelLds* __restrict__ M, const SmplxActionsDev& A,
+                                                const SmplxSpaceDev* __restrict__ Sq, int pi, int type,
+                                                const double* __restrict__ parent, double* __restrict__ sq, int& W)
+{
+    const int nv = MV_NVARS(M);
+    W = 0;
+    if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
+        double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
+        if (A.xy_rotate_by_var3 && nv > 3) {
+            double s, c;
+            smplx_sincos(parent[3], &s, &c);
+            const double a0 = d0, a1 = d1;
+            d0 = c * a0 + (-s) * a1;
+            d1 = s * a0 + c * a1;
+        }
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) {
+            const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
+            sq[v] = d + parent[v];
+        }
+    } else if (type == SMPLX_MP_SNAP_XYZ_RPY && Sq->goal.type == SMPLX_GOAL_JOINT) {
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) sq[v] = Sq->goal.angles[v];
+    } else {
+        return SMPLX_F_INACTIVE;
+    }
+    if (!check_joint_limits(M, sq)) return SMPLX_F_LIMITS;
+    double motion = 0.0;
+    MV_UNROLL
+    for (int v = 0; v < nv; ++v) {
+        const int ty = MV_TYPE(M, v);
+        const double sv = parent[v], fv = sq[v];
+        if (ty == SMPLX_JT_CONTINUOUS) motion += MV_K(M, v) * fabs(smplx_shortest_angle_diff(fv, sv));
+        else if (ty == SMPLX_JT_REVOLUTE) motion += MV_K(M, v) * fabs(fv - sv);
+        else if (ty == SMPLX_JT_PRISMATIC) motion += fabs(fv - sv);
+    }
+    if (motion != 0.0) {
+        W = (int)ceil(motion / 0.05) + 1;
+        if (W < 2) W = 2;
+    }
+    return 0;
+}
+
+// A block of k_pipe_setup is BLOCK edge threads plus one more wave, which computes the goal distances beside them.
+extern "C" __global__ void __launch_bounds__(SMPLX_SETUP_BLOCK)
 k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
-             const double* __restrict__ goal_dist, unsigned char* __restrict__ out_flags, double* __restrict__ out_q,
+             double* __restrict__ goal_dist, unsigned char* __restrict__ out_flags, double* __restrict__ out_q,
              int* __restrict__ edge_w, int* __restrict__ edge_lookups, unsigned char* __restrict__ edge_bad,
              int* __restrict__ state_lookups, unsigned char* __restrict__ state_bad,
              unsigned long long* __restrict__ work, int* __restrict__ work_count, int capacity,
-        const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q)
+        const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
+             int have_goal_dist, int* __restrict__ cmp_totals, const int* __restrict__ ins_items, int n_ins)
 {
     extern __shared__ __align__(16) unsigned char smem[];
-    const ModelLds Mv = setup_model_only(S, smem);
-    const ModelLds* M = &Mv;
     const SmplxActionsDev& A = S->actions;
     const int nprims = A.nprims;
+    const long long n_edges = (long long)B * nprims;
+    // K5: the states the host committed since the last batch join the device table (createHashEntry) in extra blocks
+    // behind the edge blocks; the table is first read one launch later (successor role of k_pipe_configs)
+    if (n_ins > 0 && table_insert_block(S, stab, ins_items, n_ins, (int)((n_edges + BLOCK - 1) / BLOCK))) return;
+    const ModelLds Mv = setup_model_only(S, smem, (int)blockDim.x);   // BLOCK threads when k_pipe_prep ran in front: no goal-distance wave
+    const ModelLds* M = &Mv;
+    const bool dist_wave = threadIdx.x >= BLOCK;   // the wave behind the edge threads
     const long long tid = (long long)blockIdx.x * BLOCK + threadIdx.x;
-    const bool in_range = tid < (long long)B * nprims;
-    int items = 0;
+    const bool in_range = !dist_wave && tid < n_edges;
+    const int nv = MV_NVARS(M);
+    const int si = in_range ? (int)(tid / nprims) : 0;
+    const int pi = in_range ? (int)(tid - (long long)si * nprims) : 0;
+    const double* parent = Q + (refs ? refs[si] : (int64_t)si) * nv;
+    const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
+    const int type = A.type[pi];
     int W = 0;
     int flags = SMPLX_F_INACTIVE;
+#ifdef SMPLX_CONST_MODEL
+    // per-robot build: what the gate does not decide is worked out in registers BEFORE the gate is known, beside the
+    // goal-distance wave; an edge whose primitive turns out inactive stores none of it
+    // (with k_pipe_prep in front the gate is known here already and, as ever, only an active primitive is worked out)
+    double sqv[CM_NV];
+    if (in_range && (!have_goal_dist || mprim_active(A, goal_dist[si], type)))
+        flags = pipe_edge_values(M, A, Sq, pi, type, parent, sqv, W);
+#endif
+    // have_goal_dist: k_pipe_prep ran in front (test_hooks.h smplx_test_set_pipe_prep) and left goal_dist[] and zeroed
+    // cmp_totals.  Otherwise the block computes the goal distance of the states its edges belong to -- s0 .. s1, at most
+    // BLOCK of them (7 at M = 25) -- on the lanes of its last wave, with k_pipe_prep's own expression.  A state whose
+    // edges straddle two blocks is computed by both: same inputs, same instructions, same bits.
+    __shared__ double block_goal_dist[BLOCK];
+    const long long e0 = (long long)blockIdx.x * BLOCK;
+    const int s0 = (int)(e0 / nprims);
+    if (!have_goal_dist) {
+        if (dist_wave) {
+            if (cmp_totals && blockIdx.x == 0)                               // compaction counters of k_pipe_finish
+                for (int k = threadIdx.x - BLOCK; k < SMPLX_CMP_TOTALS; k += 64) cmp_totals[k] = 0;
+            const long long e1 = e0 + BLOCK - 1 < n_edges ? e0 + BLOCK - 1 : n_edges - 1;   // (e0 < n_edges: this is an edge block)
+            const int s1 = (int)(e1 / nprims);                                               // < B
+            for (int sj = s0 + (int)threadIdx.x - BLOCK; sj <= s1; sj += 64)
+                block_goal_dist[sj - s0] = pipe_goal_dist(M, S, S->grid, Q, refs, sj, stab, state_q);
+        }
+        __syncthreads();
+    }
+    int items = 0;
     if (in_range) {
-        const int si = (int)(tid / nprims);
-        const int pi = (int)(tid - (long long)si * nprims);
-        const int nv = MV_NVARS(M);
-        const double* parent = Q + (refs ? refs[si] : (int64_t)si) * nv;
         double* sq = out_q + tid * nv;
-        const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
-        const int type = A.type[pi];
-        bool have_action = false;
-        if (pi == 0) { state_lookups[si] = 0; state_bad[si] = 0; }
-        if (mprim_active(A, goal_dist[si], type)) {
-            if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
-                double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
-                if (A.xy_rotate_by_var3 && nv > 3) {
-                    double s, c;
-                    smplx_sincos(parent[3], &s, &c);
-                    const double a0 = d0, a1 = d1;
-                    d0 = c * a0 + (-s) * a1;
-                    d1 = s * a0 + c * a1;
-                }
-                MV_UNROLL
-                for (int v = 0; v < nv; ++v) {
-                    const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
-                    sq[v] = d + parent[v];
-                }
-                have_action = true;
-            } else if (type == SMPLX_MP_SNAP_XYZ_RPY && Sq->goal.type == SMPLX_GOAL_JOINT) {
-                MV_UNROLL
-                for (int v = 0; v < nv; ++v) sq[v] = Sq->goal.angles[v];
-                have_action = true;
-            }
+        const double gd = have_goal_dist ? goal_dist[si] : block_goal_dist[si - s0];
+        if (pi == 0) {
+            state_lookups[si] = 0; state_bad[si] = 0;
+            if (!have_goal_dist) goal_dist[si] = gd;   // for the deferred pass of k_pipe_finish (expand_edge): one writer per state
         }
-        if (have_action) {
-            flags = 0;
-            if (!check_joint_limits(M, sq)) {
-                flags = SMPLX_F_LIMITS;
-            } else {
-                double motion = 0.0;
-                MV_UNROLL
-                for (int v = 0; v < nv; ++v) {
-                    const int ty = MV_TYPE(M, v);
-                    const double sv = parent[v], fv = sq[v];
-                    if (ty == SMPLX_JT_CONTINUOUS) motion += MV_K(M, v) * fabs(smplx_shortest_angle_diff(fv, sv));
-                    else if (ty == SMPLX_JT_REVOLUTE) motion += MV_K(M, v) * fabs(fv - sv);
-                    else if (ty == SMPLX_JT_PRISMATIC) motion += fabs(fv - sv);
-                }
-                if (motion != 0.0) {
-                    W = (int)ceil(motion / 0.05) + 1;
-                    if (W < 2) W = 2;
-                }
-                items = W > 0 ? W - 1 : 0;
+        if (!mprim_active(A, gd, type)) {
+            flags = SMPLX_F_INACTIVE;
+            W = 0;
+        } else {
+#ifdef SMPLX_CONST_MODEL
+            if (flags != SMPLX_F_INACTIVE) {
+#pragma unroll
+                for (int v = 0; v < CM_NV; ++v) sq[v] = sqv[v];
             }
+#else
+            flags = pipe_edge_values(M, A, Sq, pi, type, parent, sq, W);
+#endif
         }
+        items = W > 0 ? W - 1 : 0;
         edge_lookups[tid] = 0;
         edge_bad[tid] = 0;
     }
@@ -1700,7 +1769,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
         const int t = __shfl_up(incl, off);
         if (lane >= off) incl += t;
     }
-    if (lane == 63) wave_sum[wv] = incl;
+    if (lane == 63 && !dist_wave) wave_sum[wv] = incl;
     __syncthreads();
     const int shard = blockIdx.x % SMPLX_WORK_SHARDS;
     const int shard_cap = capacity / SMPLX_WORK_SHARDS;
@@ -1943,11 +2012,14 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
               unsigned long long* __restrict__ counters, const double* __restrict__ goal_dist,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
               int* __restrict__ out_id, SmplxCompactDev cmp, const unsigned long long* __restrict__ succ_eval,
-              const unsigned char* __restrict__ succ_goal, const int* __restrict__ succ_coord)
+              const unsigned char* __restrict__ succ_goal, const int* __restrict__ succ_coord, int* __restrict__ work_count)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmplxActionsDev& A = S->actions;
     const int nprims = A.nprims;
+    // the stream's work-list counters (shards + deferred count) go back to zero for the next step's k_pipe_setup: their
+    // last reader, k_pipe_configs, ended a launch ago
+    if (blockIdx.x == 0 && threadIdx.x <= SMPLX_WORK_SHARDS) work_count[threadIdx.x * SMPLX_SHARD_STRIDE] = 0;
 #ifdef SMPLX_CONST_MODEL
     constexpr int nv = CM_NV;
 #else

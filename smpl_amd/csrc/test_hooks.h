@@ -13,6 +13,12 @@ extern "C" {
  * 0 restores the default size. */
 int smplx_test_set_work_list_items(smplx_space* s, int items);
 
+/* on = 1: the expansion pipeline runs as four launches -- k_pipe_prep (goal distance per state, counters, K5 inserts) in a
+ * launch of its own in front of k_pipe_setup, which then takes its gate from what k_pipe_prep left; 0 restores the
+ * default: three launches, where k_pipe_setup computes the goal distance itself, for every batch whose setup blocks fit
+ * the chip in one round (four beyond that).  Same results, bit for bit. */
+int smplx_test_set_pipe_prep(smplx_space* s, int on);
+
 /* The heap primitives of the device-resident search (search_kernel.h) driven by an op sequence in the language of
  * oracle/heap_ref_driver.cpp (pairs code, key; see k_heap_ops): top_after[i] = element at the top after op i, -1 when empty.
  * lds_entries = how many leading heap entries live in LDS (the rest in HBM), 1 .. 4096. */

@@ -6,7 +6,7 @@ import os
 import sys
 from collections import defaultdict
 
-STEP_KERNELS = ["k_pipe_prep", "k_pipe_setup", "k_pipe_configs", "k_pipe_finish"]
+STEP_KERNELS = ["k_pipe_setup", "k_pipe_configs", "k_pipe_finish"]   # (k_pipe_prep runs under its test hook only)
 
 
 def find(out, stem, kind):
