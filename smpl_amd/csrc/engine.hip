@@ -755,7 +755,6 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     if (s->prof_used + 3 <= s->prof_events.size()) { ev = &s->prof_events[s->prof_used]; s->prof_used += 3; }
     const int bs = blocks_for(B, SMPLX_BLOCK);
     const int be = blocks_for((long long)B * s->M, SMPLX_BLOCK);
-    const int64_t* norefs = nullptr;
     if (path == ExpandPath::SmallZeroCopy || path == ExpandPath::Small) {
         ++s->small_launches;
         // a handful of states: ONE launch, all FK chains side by side (kernels.hip k_small_batch)
@@ -763,7 +762,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         const ZeroCopy* zc = path == ExpandPath::SmallZeroCopy ? a.zero_copy : nullptr;
         const int small_block = smplx_small_block(s->M);
         KLAUNCH(s, K_SMALL_BATCH, k_small_batch, dim3(B + blocks_for(n_ins, small_block)), dim3(small_block), small_lds_bytes(s), a.stream, s->d_space,
-                           zc ? zc->q : a.q, norefs, B, k.goal_dist,
+                           zc ? zc->q : a.q, B, k.goal_dist,
                            k.state_bad, k.state_lookups, a.flags, a.coord, a.sq, a.h, a.cost, a.lookups, a.stab, a.state_q,
                            zc ? zc->flags : (unsigned char*)nullptr, zc ? zc->coord : (int32_t*)nullptr,
                            zc ? zc->sq : (double*)nullptr, zc ? zc->h : (int32_t*)nullptr, d_id,
@@ -775,10 +774,10 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
             hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, a.stream, s->d_space, a.stab, ins_items, n_ins, s->N);
         }
         if (ev) (void)hipEventRecord(ev[0], a.stream);
-        KLAUNCH(s, K_STATE_PREP, k_state_prep, dim3(bs), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_STATE_PREP, k_state_prep, dim3(bs), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, B,
                            k.goal_dist, k.state_bad, k.state_lookups, a.stab, a.state_q);
         if (ev) (void)hipEventRecord(ev[1], a.stream);
-        KLAUNCH(s, K_EXPAND, k_expand, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_EXPAND, k_expand, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, B,
                            k.goal_dist, k.state_bad, k.state_lookups, a.flags, a.coord, a.sq, a.h, a.cost, a.lookups,
                            a.counters, (const int*)nullptr, a.stab, a.state_q);
         if (ev) (void)hipEventRecord(ev[2], a.stream);
@@ -803,22 +802,22 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         }
         const bool pipe_prep = s->pipe_prep || be > s->three_launch_blocks;
         if (pipe_prep)
-            KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+            KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, B,
                                k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins);
         const int n_ins_setup = pipe_prep ? 0 : n_ins;
-        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be + blocks_for(n_ins_setup, SMPLX_BLOCK)), dim3(pipe_prep ? SMPLX_BLOCK : SMPLX_SETUP_BLOCK), lm, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be + blocks_for(n_ins_setup, SMPLX_BLOCK)), dim3(pipe_prep ? SMPLX_BLOCK : SMPLX_SETUP_BLOCK), lm, a.stream, s->d_space, a.q, B,
                            k.goal_dist, a.flags, a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
                            k.work, k.work_count, k.capacity, a.stab, a.state_q, pipe_prep ? 1 : 0, cmp.totals, ins_items, n_ins_setup);
         if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
         // behind the bc collision blocks: one successor thread per edge (dense: it leaves at once where setup's flag is not 0)
         const int bc = blocks_for((long long)B + (long long)B * s->M * 3, SMPLX_BLOCK);
-        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, B,
                            a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
                            k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal);
         if (ev) (void)hipEventRecord(ev[1], a.stream);
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
-        KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, norefs, B,
+        KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, B,
                            k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, a.flags, a.coord, a.sq, a.h,
                            a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp, k.succ_eval, k.succ_goal, k.succ_coord,
                            k.work_count);
@@ -1199,8 +1198,8 @@ int get_succs(smplx_space* s, int id, const int32_t** succs, const int32_t** cos
     return SMPLX_OK;
 }
 
-// host mirror of applyMotionPrimitive (kernels.hip; manip_lattice_action_space.cpp:575-621) -- the same expressions in the
-// same order, compiled with -ffp-contract=off like the kernels: bit-identical successor joint values
+// host mirror of the applyMotionPrimitive branch (manip_lattice_action_space.cpp:575-621) of successor_values in kernels.hip,
+// the one device definition: change the two together.  Same expressions, same order, -ffp-contract=off like the kernels.
 void host_apply_prim(const SmplxActionsDev& A, const double* parent, int pi, int nv, double* out)
 {
     double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;

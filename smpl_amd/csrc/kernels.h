@@ -29,31 +29,31 @@ static inline size_t smplx_lds_bytes(size_t blob_bytes, int nroot, int nslots, i
 }
 
 extern "C" {
-__global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist,
+__global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
                              unsigned char* parent_valid, int* parent_lookups,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q);
-__global__ void k_expand(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, const double* goal_dist,
+__global__ void k_expand(const SmplxSpaceDev* S, const double* Q, int B, const double* goal_dist,
                          const unsigned char* parent_valid, const int* parent_lookups, unsigned char* out_flags,
                          int* out_coord, double* out_q, int* out_h, int* out_cost, int* out_lookups,
                          unsigned long long* counters, const int* deferred_count,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q);
-__global__ void k_pipe_prep(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist,
+__global__ void k_pipe_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
                             int* work_count,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* cmp_totals,
                             const int* ins_items, int n_ins);
-__global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist,
+__global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
                              unsigned char* out_flags, double* out_q, int* edge_w, int* edge_lookups,
                              unsigned char* edge_bad, int* state_lookups, unsigned char* state_bad, unsigned long long* work,
                              int* work_count, int capacity,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int have_goal_dist,
                              int* cmp_totals, const int* ins_items, int n_ins);
-__global__ void k_pipe_configs(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, const double* out_q,
+__global__ void k_pipe_configs(const SmplxSpaceDev* S, const double* Q, int B, const double* out_q,
                                const int* edge_w, int* edge_lookups, unsigned char* edge_bad, int* state_lookups,
                                unsigned char* state_bad, const unsigned long long* work, const int* work_count, int capacity,
                                int cfg_blocks, const unsigned char* out_flags, int* succ_coord,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int want_id,
                                unsigned long long* succ_eval, unsigned char* succ_goal);
-__global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, const int* edge_w,
+__global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, int B, const int* edge_w,
                               const int* edge_lookups, const unsigned char* edge_bad, const int* state_lookups,
                               const unsigned char* state_bad, unsigned char* out_flags, int* out_coord, double* out_q,
                               int* out_h, int* out_cost, int* out_lookups, unsigned long long* counters,
@@ -61,7 +61,7 @@ __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, const int
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* out_id, SmplxCompactDev cmp,
                               const unsigned long long* succ_eval, const unsigned char* succ_goal, const int* succ_coord,
                               int* work_count);
-__global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, const int64_t* refs, int B, double* goal_dist_out,
+__global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist_out,
                               unsigned char* state_bad_out, int* state_lookups_out, unsigned char* out_flags, int* out_coord,
                               double* out_q, int* out_h, int* out_cost, int* out_lookups,
                               const SmplxSpaceDev* const* stab, const unsigned short* state_q, unsigned char* host_flags,

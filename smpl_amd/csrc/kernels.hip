@@ -1033,14 +1033,11 @@ __device__ __forceinline__ bool config_valid(const ModelLds* __restrict__ M, con
     return config_valid_staged<RS>(M, L, g, e, lookups);
 }
 
-// CollisionSpace::isStateToStateValid (collision_space.cpp:538-581).  first_wp = 1 skips waypoint 0
-// (the start configuration), whose result the caller already has.
-template <bool RS = false>
-__device__ __forceinline__ bool edge_valid(const ModelLds* __restrict__ M, const ThreadLds& L, const SmplxGridDev& g,
-                                           const double* __restrict__ start, const double* __restrict__ finish,
-                                           bool start_known, bool start_valid, int& lookups, int& waypoints)
+// waypoint count of the edge start -> finish (robot_motion_collision_model.cpp:371-407, .h:352-366, 173-181): 0 for an
+// edge without motion.  The one definition for every path: edge_valid, the pipeline's setup, the block-per-state pieces.
+__device__ __forceinline__ int edge_waypoint_count(const ModelLds* __restrict__ M, const double* __restrict__ start,
+                                                   const double* __restrict__ finish)
 {
-    // robot_motion_collision_model.cpp:371-407, .h:352-366, 173-181
     double motion = 0.0;
     const int nv = MV_NVARS(M);
     MV_UNROLL
@@ -1056,6 +1053,17 @@ __device__ __forceinline__ bool edge_valid(const ModelLds* __restrict__ M, const
         W = (int)ceil(motion / 0.05) + 1;
         if (W < 2) W = 2;
     }
+    return W;
+}
+
+// CollisionSpace::isStateToStateValid (collision_space.cpp:538-581).  first_wp = 1 skips waypoint 0
+// (the start configuration), whose result the caller already has.
+template <bool RS = false>
+__device__ __forceinline__ bool edge_valid(const ModelLds* __restrict__ M, const ThreadLds& L, const SmplxGridDev& g,
+                                           const double* __restrict__ start, const double* __restrict__ finish,
+                                           bool start_known, bool start_valid, int& lookups, int& waypoints)
+{
+    const int W = edge_waypoint_count(M, start, finish);
     waypoints = W;
     if (W == 0) return true;
     if (start_known && !start_valid) return false;
@@ -1127,6 +1135,19 @@ __device__ __forceinline__ int bfs_dist(const SmplxBfsDev& b, const int c[3])
     const int v = dist[brick * SMPLX_BFS_REC + ((c[2] & 7) << 6) + ((c[1] & 7) << 3) + (c[0] & 7)];
     if (v == 0x7FFFFFFF) return v;
     return ((v ^ b.tag_word) & b.tag_mask) != 0 ? -1 : (v & ~b.tag_mask);     // another run's value: UNDISCOVERED
+}
+
+// BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) of the state with joint values q: the gate of its
+// primitives.  The one definition for every path; goal_distance_of_h (search_kernel.h) recovers the same value from a
+// state's heuristic and must keep the same distance for an unreachable cell.
+__device__ __forceinline__ double metric_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
+                                                       const double* __restrict__ q)
+{
+    double p[3];
+    planning_fk(M, q, p);
+    int c[3];
+    world_to_cell(grid, p, c);
+    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
 }
 
 // BfsHeuristic::getBfsCostToGoal (bfs_heuristic.cpp:355-366)
@@ -1338,7 +1359,7 @@ __device__ __forceinline__ ModelLds setup_model_only(const SmplxSpaceDev* __rest
 // ---------------------------------------------------------------------------------------------
 
 extern "C" __global__ void __launch_bounds__(BLOCK, 2)   // >= 2 waves per SIMD: at most 256 VGPRs, whichever compiler builds it
-k_state_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_state_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
              double* __restrict__ goal_dist, unsigned char* __restrict__ parent_valid, int* __restrict__ parent_lookups,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q)
 {
@@ -1350,16 +1371,8 @@ k_state_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= B) return;
     const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;   // per-query data in a cross-query batch
-    const double* q = Q + (refs ? refs[i] : (int64_t)i) * MV_NVARS(M);
-    double p[3];
-    planning_fk(M, q, p);
-    // BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138)
-    int c[3];
-    world_to_cell(grid, p, c);
-    double gd;
-    if (!bfs_in_bounds(bfs, c)) gd = (double)0x7FFFFFFF * grid.res;
-    else gd = (double)bfs_dist(bfs, c) * grid.res;
-    goal_dist[i] = gd;
+    const double* q = Q + (int64_t)i * MV_NVARS(M);
+    goal_dist[i] = metric_goal_distance(M, grid, bfs, q);
     EdgeRef e;
     e.start = q; e.finish = q; e.alpha = 0.0;
     int lk = 0;
@@ -1405,6 +1418,69 @@ __device__ __forceinline__ bool mprim_active(const SmplxActionsDev& A, double go
     return A.enabled[type] && goal_dist <= A.thresh[type];
 }
 
+// can the primitive produce an action at all (a snap needs a joint-space goal: manip_lattice_action_space.cpp:551-559)
+__device__ __forceinline__ bool prim_has_action(const SmplxActionsDev& A, const SmplxGoalDev& G, int p)
+{
+    const int ty = A.type[p];
+    return ty == SMPLX_MP_LONG || ty == SMPLX_MP_SHORT || (ty == SMPLX_MP_SNAP_XYZ_RPY && G.type == SMPLX_GOAL_JOINT);
+}
+
+// Joint values of the successor of `parent` under primitive pi -> sq (global memory, registers or LDS).  Returns
+// prim_has_action: false, with sq untouched, where the primitive has no action for this goal type.  The one definition
+// for every path; host_apply_prim (engine.hip) mirrors its first branch.
+__device__ __forceinline__ bool successor_values(const ModelLds* __restrict__ M, const SmplxActionsDev& A, const SmplxGoalDev& G,
+                                                 int pi, const double* __restrict__ parent, double* __restrict__ sq)
+{
+    const int nv = MV_NVARS(M);
+    const int type = A.type[pi];
+    if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
+        // applyMotionPrimitive (manip_lattice_action_space.cpp:575-621)
+        double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
+        if (A.xy_rotate_by_var3 && nv > 3) {
+            double s, c;
+            smplx_sincos(parent[3], &s, &c);
+            const double a0 = d0, a1 = d1;
+            d0 = c * a0 + (-s) * a1;
+            d1 = s * a0 + c * a1;
+        }
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) {
+            const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
+            sq[v] = d + parent[v];
+        }
+        return true;
+    }
+    if (type == SMPLX_MP_SNAP_XYZ_RPY && G.type == SMPLX_GOAL_JOINT) {
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) sq[v] = G.angles[v];   // :551-559
+        return true;
+    }
+    return false;
+}
+
+// Goal test and heuristic of the successor with joint values sq and coordinates sc: planning-link FK, isGoal, BFS cost of
+// its cell.  Returns h.  The one definition for every path; discretisation and the table probe stay with the callers.
+__device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, const SmplxGoalDev& G, const SmplxBfsDev& bfs,
+                                                const SmplxGridDev& grid, const double* __restrict__ sq, const int* sc,
+                                                bool& is_goal)
+{
+    const int nv = MV_NVARS(M);
+    double p[3];
+    planning_fk(M, sq, p);
+    if (G.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
+        is_goal = true;
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v)
+            if (fabs((double)(sc[v] - G.coord[v])) > G.angle_tol[v]) is_goal = false;
+    } else {                               // XYZ goal :1672-1687
+        is_goal = fabs(p[0] - G.xyz[0]) <= G.xyz_tol[0] && fabs(p[1] - G.xyz[1]) <= G.xyz_tol[1] &&
+                  fabs(p[2] - G.xyz[2]) <= G.xyz_tol[2];
+    }
+    int c[3];
+    world_to_cell(grid, p, c);
+    return bfs_cost_to_goal(bfs, c);
+}
+
 // One (state, primitive) pair through the whole GetSuccs loop body in ONE thread (manip_lattice.cpp:1471-1535):
 // gating, successor joint values, limits, the edge's waypoints in the reference's order, discretisation, goal test,
 // heuristic.  parent_ok / parent_lk: result of the state's own check (waypoint 0 of every edge).
@@ -1412,7 +1488,7 @@ struct EdgeTally { int flags, lookups, performed, evaluated; };
 
 __device__ __forceinline__ EdgeTally expand_edge(const ModelLds* __restrict__ M, const ThreadLds& L, const SmplxSpaceDev* __restrict__ S,
                                                  const SmplxSpaceDev* __restrict__ Sq, const SmplxGridDev& grid,
-                                                 const double* __restrict__ Q, const int64_t* __restrict__ refs, long long tid,
+                                                 const double* __restrict__ Q, long long tid,
                                                  const double* __restrict__ goal_dist, bool parent_ok, int parent_lk,
                                                  unsigned char* __restrict__ out_flags, int* __restrict__ out_coord,
                                                  double* __restrict__ out_q, int* __restrict__ out_h, int* __restrict__ out_cost,
@@ -1428,36 +1504,13 @@ __device__ __forceinline__ EdgeTally expand_edge(const ModelLds* __restrict__ M,
         const int si = (int)(tid / nprims);
         const int pi = (int)(tid - (long long)si * nprims);
         const int nv = MV_NVARS(M);
-        const double* parent = Q + (refs ? refs[si] : (int64_t)si) * nv;
+        const double* parent = Q + (int64_t)si * nv;
         double* sq = out_q + tid * nv;
         int* sc = out_coord + tid * nv;
         const SmplxBfsDev bfs = Sq->bfs;
-        const int type = A.type[pi];
         int h = 0, cost = 0;
         bool have_action = false;
-        if (mprim_active(A, goal_dist[si], type)) {
-            if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
-                // applyMotionPrimitive (manip_lattice_action_space.cpp:575-621)
-                double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
-                if (A.xy_rotate_by_var3 && nv > 3) {
-                    double s, c;
-                    smplx_sincos(parent[3], &s, &c);
-                    const double a0 = d0, a1 = d1;
-                    d0 = c * a0 + (-s) * a1;
-                    d1 = s * a0 + c * a1;
-                }
-                MV_UNROLL
-                for (int v = 0; v < nv; ++v) {
-                    const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
-                    sq[v] = d + parent[v];
-                }
-                have_action = true;
-            } else if (type == SMPLX_MP_SNAP_XYZ_RPY && Sq->goal.type == SMPLX_GOAL_JOINT) {
-                MV_UNROLL
-                for (int v = 0; v < nv; ++v) sq[v] = Sq->goal.angles[v];   // :551-559
-                have_action = true;
-            }
-        }
+        if (mprim_active(A, goal_dist[si], A.type[pi])) have_action = successor_values(M, A, Sq->goal, pi, parent, sq);
         if (have_action) {
             evaluated = 1;
             flags = 0;
@@ -1476,21 +1529,7 @@ __device__ __forceinline__ EdgeTally expand_edge(const ModelLds* __restrict__ M,
                     MV_UNROLL
                     for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
                     bool is_goal;
-                    double p[3];
-                    planning_fk(M, sq, p);
-                    if (Sq->goal.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
-                        is_goal = true;
-                        MV_UNROLL
-                        for (int v = 0; v < nv; ++v)
-                            if (fabs((double)(sc[v] - Sq->goal.coord[v])) > Sq->goal.angle_tol[v]) is_goal = false;
-                    } else {                                      // XYZ goal :1672-1687
-                        is_goal = fabs(p[0] - Sq->goal.xyz[0]) <= Sq->goal.xyz_tol[0] &&
-                                  fabs(p[1] - Sq->goal.xyz[1]) <= Sq->goal.xyz_tol[1] &&
-                                  fabs(p[2] - Sq->goal.xyz[2]) <= Sq->goal.xyz_tol[2];
-                    }
-                    int c[3];
-                    world_to_cell(grid, p, c);
-                    h = bfs_cost_to_goal(bfs, c);
+                    h = successor_goal_h(M, Sq->goal, bfs, grid, sq, sc, is_goal);
                     cost = A.cost[pi];
                     flags = SMPLX_F_VALID | (is_goal ? SMPLX_F_GOAL : 0);
                 }
@@ -1507,7 +1546,7 @@ __device__ __forceinline__ EdgeTally expand_edge(const ModelLds* __restrict__ M,
 }
 
 extern "C" __global__ void __launch_bounds__(BLOCK, 2)   // >= 2 waves per SIMD: at most 256 VGPRs, whichever compiler builds it
-k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
          const double* __restrict__ goal_dist, const unsigned char* __restrict__ parent_valid,
          const int* __restrict__ parent_lookups,
          unsigned char* __restrict__ out_flags, int* __restrict__ out_coord, double* __restrict__ out_q,
@@ -1547,7 +1586,7 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
         const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;   // per-query goal and BFS grid
         // fused mode: parent_valid holds 1 = valid (k_state_prep); deferred pass: the pipeline's state_bad (1 = bad)
         const bool pv = only_deferred ? parent_valid[si] == 0 : parent_valid[si] != 0;
-        const EdgeTally t = expand_edge(M, L, S, Sq, grid, Q, refs, tid, goal_dist, pv, parent_lookups[si], out_flags, out_coord,
+        const EdgeTally t = expand_edge(M, L, S, Sq, grid, Q, tid, goal_dist, pv, parent_lookups[si], out_flags, out_coord,
                                         out_q, out_h, out_cost, out_lookups);
         flags = t.flags; lookups = t.lookups; performed = t.performed; evaluated = t.evaluated;
     }
@@ -1595,24 +1634,8 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, cons
 #define SMPLX_WORK_SHARDS 8
 #define SMPLX_SHARD_STRIDE 32   // ints: one 128-byte line per shard counter
 
-// BfsHeuristic::getMetricGoalDistance of state i (bfs_heuristic.cpp:129-138): one expression for k_pipe_prep and k_pipe_setup
-__device__ __forceinline__ double pipe_goal_dist(const ModelLds* __restrict__ M, const SmplxSpaceDev* __restrict__ S,
-                                                 const SmplxGridDev& grid, const double* __restrict__ Q,
-                                                 const int64_t* __restrict__ refs, int i,
-                                                 const SmplxSpaceDev* const* __restrict__ stab,
-                                                 const unsigned short* __restrict__ state_q)
-{
-    const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;
-    const double* q = Q + (refs ? refs[i] : (int64_t)i) * MV_NVARS(M);
-    double p[3];
-    planning_fk(M, q, p);
-    int c[3];
-    world_to_cell(grid, p, c);
-    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
-}
-
 extern "C" __global__ void __launch_bounds__(BLOCK)
-k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
             double* __restrict__ goal_dist, int* __restrict__ work_count,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q, int* __restrict__ cmp_totals,
             const int* __restrict__ ins_items, int n_ins)
@@ -1628,58 +1651,27 @@ k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, c
     if (cmp_totals && blockIdx.x == 0)                                   // compaction counters of k_pipe_finish
         for (int k = threadIdx.x; k < SMPLX_CMP_TOTALS; k += BLOCK) cmp_totals[k] = 0;
     if (i >= B) return;
-    goal_dist[i] = pipe_goal_dist(M, S, grid, Q, refs, i, stab, state_q);
+    const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;   // per-query data in a cross-query batch
+    goal_dist[i] = metric_goal_distance(M, grid, bfs, Q + (int64_t)i * MV_NVARS(M));
 }
 
 // The part of an edge that the gate does not decide (manip_lattice.cpp:1471-1490 for an active primitive): successor
 // joint values into sq, limits, waypoint count.  Returns the edge's flags (SMPLX_F_INACTIVE: the primitive has no action
 // for this goal type) and W.
 __device__ __forceinline__ int pipe_edge_values(const ModelLds* __restrict__ M, const SmplxActionsDev& A,
-                                                const SmplxSpaceDev* __restrict__ Sq, int pi, int type,
+                                                const SmplxSpaceDev* __restrict__ Sq, int pi,
                                                 const double* __restrict__ parent, double* __restrict__ sq, int& W)
 {
-    const int nv = MV_NVARS(M);
     W = 0;
-    if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
-        double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
-        if (A.xy_rotate_by_var3 && nv > 3) {
-            double s, c;
-            smplx_sincos(parent[3], &s, &c);
-            const double a0 = d0, a1 = d1;
-            d0 = c * a0 + (-s) * a1;
-            d1 = s * a0 + c * a1;
-        }
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v) {
-            const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
-            sq[v] = d + parent[v];
-        }
-    } else if (type == SMPLX_MP_SNAP_XYZ_RPY && Sq->goal.type == SMPLX_GOAL_JOINT) {
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v) sq[v] = Sq->goal.angles[v];
-    } else {
-        return SMPLX_F_INACTIVE;
-    }
+    if (!successor_values(M, A, Sq->goal, pi, parent, sq)) return SMPLX_F_INACTIVE;
     if (!check_joint_limits(M, sq)) return SMPLX_F_LIMITS;
-    double motion = 0.0;
-    MV_UNROLL
-    for (int v = 0; v < nv; ++v) {
-        const int ty = MV_TYPE(M, v);
-        const double sv = parent[v], fv = sq[v];
-        if (ty == SMPLX_JT_CONTINUOUS) motion += MV_K(M, v) * fabs(smplx_shortest_angle_diff(fv, sv));
-        else if (ty == SMPLX_JT_REVOLUTE) motion += MV_K(M, v) * fabs(fv - sv);
-        else if (ty == SMPLX_JT_PRISMATIC) motion += fabs(fv - sv);
-    }
-    if (motion != 0.0) {
-        W = (int)ceil(motion / 0.05) + 1;
-        if (W < 2) W = 2;
-    }
+    W = edge_waypoint_count(M, parent, sq);
     return 0;
 }
 
 // A block of k_pipe_setup is BLOCK edge threads plus one more wave, which computes the goal distances beside them.
 extern "C" __global__ void __launch_bounds__(SMPLX_SETUP_BLOCK)
-k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
              double* __restrict__ goal_dist, unsigned char* __restrict__ out_flags, double* __restrict__ out_q,
              int* __restrict__ edge_w, int* __restrict__ edge_lookups, unsigned char* __restrict__ edge_bad,
              int* __restrict__ state_lookups, unsigned char* __restrict__ state_bad,
@@ -1702,7 +1694,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     const int nv = MV_NVARS(M);
     const int si = in_range ? (int)(tid / nprims) : 0;
     const int pi = in_range ? (int)(tid - (long long)si * nprims) : 0;
-    const double* parent = Q + (refs ? refs[si] : (int64_t)si) * nv;
+    const double* parent = Q + (int64_t)si * nv;
     const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
     const int type = A.type[pi];
     int W = 0;
@@ -1713,7 +1705,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     // (with k_pipe_prep in front the gate is known here already and, as ever, only an active primitive is worked out)
     double sqv[CM_NV];
     if (in_range && (!have_goal_dist || mprim_active(A, goal_dist[si], type)))
-        flags = pipe_edge_values(M, A, Sq, pi, type, parent, sqv, W);
+        flags = pipe_edge_values(M, A, Sq, pi, parent, sqv, W);
 #endif
     // have_goal_dist: k_pipe_prep ran in front (test_hooks.h smplx_test_set_pipe_prep) and left goal_dist[] and zeroed
     // cmp_totals.  Otherwise the block computes the goal distance of the states its edges belong to -- s0 .. s1, at most
@@ -1728,8 +1720,10 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
                 for (int k = threadIdx.x - BLOCK; k < SMPLX_CMP_TOTALS; k += 64) cmp_totals[k] = 0;
             const long long e1 = e0 + BLOCK - 1 < n_edges ? e0 + BLOCK - 1 : n_edges - 1;   // (e0 < n_edges: this is an edge block)
             const int s1 = (int)(e1 / nprims);                                               // < B
-            for (int sj = s0 + (int)threadIdx.x - BLOCK; sj <= s1; sj += 64)
-                block_goal_dist[sj - s0] = pipe_goal_dist(M, S, S->grid, Q, refs, sj, stab, state_q);
+            for (int sj = s0 + (int)threadIdx.x - BLOCK; sj <= s1; sj += 64) {
+                const SmplxBfsDev bfs = (stab ? stab[state_q[sj]] : S)->bfs;   // a copy: its loads travel in front of the FK chain
+                block_goal_dist[sj - s0] = metric_goal_distance(M, S->grid, bfs, Q + (int64_t)sj * nv);
+            }
         }
         __syncthreads();
     }
@@ -1751,7 +1745,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
                 for (int v = 0; v < CM_NV; ++v) sq[v] = sqv[v];
             }
 #else
-            flags = pipe_edge_values(M, A, Sq, pi, type, parent, sq, W);
+            flags = pipe_edge_values(M, A, Sq, pi, parent, sq, W);
 #endif
         }
         items = W > 0 ? W - 1 : 0;
@@ -1814,21 +1808,7 @@ __device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, c
     for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
     // K5: the table lookup only needs the coordinates; issued here, its probe lands behind the planning-link FK
     id = want_id ? table_lookup<false>(Sq->table, sc, nv) : -1;
-    double p[3];
-    planning_fk(M, sq, p);
-    if (Sq->goal.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
-        is_goal = true;
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v)
-            if (fabs((double)(sc[v] - Sq->goal.coord[v])) > Sq->goal.angle_tol[v]) is_goal = false;
-    } else {                                      // XYZ goal :1672-1687
-        is_goal = fabs(p[0] - Sq->goal.xyz[0]) <= Sq->goal.xyz_tol[0] &&
-                  fabs(p[1] - Sq->goal.xyz[1]) <= Sq->goal.xyz_tol[1] &&
-                  fabs(p[2] - Sq->goal.xyz[2]) <= Sq->goal.xyz_tol[2];
-    }
-    int c[3];
-    world_to_cell(grid, p, c);
-    h = bfs_cost_to_goal(bfs, c);
+    h = successor_goal_h(M, Sq->goal, bfs, grid, sq, sc, is_goal);
 }
 
 // Successor role of k_pipe_configs: the blocks behind the cfg_blocks collision blocks, one thread per edge.  An edge whose
@@ -1875,7 +1855,7 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
 }
 
 extern "C" __global__ void __launch_bounds__(BLOCK, 2)   // >= 2 waves per SIMD: at most 256 VGPRs, whichever compiler builds it
-k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
                const double* __restrict__ out_q, const int* __restrict__ edge_w, int* __restrict__ edge_lookups,
                unsigned char* __restrict__ edge_bad, int* __restrict__ state_lookups, unsigned char* __restrict__ state_bad,
                const unsigned long long* __restrict__ work, const int* __restrict__ work_count, int capacity, int cfg_blocks,
@@ -1932,7 +1912,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
         double qs[CM_NV], qf[CM_NV];
         if (is_state || is_item) {
             const long long si = is_state ? i : edge / nprims;
-            const double* ps = Q + (refs ? refs[si] : (int64_t)si) * nv;
+            const double* ps = Q + si * nv;
             const double* pf = is_state ? ps : out_q + edge * nv;
 #pragma unroll
             for (int v = 0; v < nv; ++v) { qs[v] = ps[v]; qf[v] = pf[v]; }
@@ -1976,7 +1956,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
         EdgeRef e;
         int lk = 0;
         if (i < B) {   // the state itself: waypoint 0 of each of its edges
-            e.start = Q + (refs ? refs[i] : i) * nv;
+            e.start = Q + i * nv;
             e.finish = e.start;
             e.alpha = 0.0;
             const bool ok = config_valid<RS>(M, L, grid, e, lk);
@@ -1993,7 +1973,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
             const int wp = (int)((it >> 32) & 0xFFFF);
             const int W = (int)(it >> 48);
             const int si = (int)(edge / nprims);
-            e.start = Q + (refs ? refs[si] : (int64_t)si) * nv;
+            e.start = Q + (int64_t)si * nv;
             e.finish = out_q + edge * nv;
             e.alpha = (double)wp * (1.0 / (double)(W - 1));
             const bool ok = config_valid<RS>(M, L, grid, e, lk);
@@ -2004,7 +1984,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
 }
 
 extern "C" __global__ void __launch_bounds__(BLOCK, 2)   // holds the whole-edge walk for overflowed edges: keep it at 2 waves per SIMD
-k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
               const int* __restrict__ edge_w, const int* __restrict__ edge_lookups, const unsigned char* __restrict__ edge_bad,
               const int* __restrict__ state_lookups, const unsigned char* __restrict__ state_bad,
               unsigned char* __restrict__ out_flags, int* __restrict__ out_coord, double* __restrict__ out_q,
@@ -2066,7 +2046,7 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
             const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
             const SmplxGridDev grid = S->grid;
             if (pi == 0) { slk = s_lk; ncfg = 1; }
-            const EdgeTally t = expand_edge(&Mv, L, S, Sq, grid, Q, refs, tid, goal_dist, s_bad == 0, s_lk,
+            const EdgeTally t = expand_edge(&Mv, L, S, Sq, grid, Q, tid, goal_dist, s_bad == 0, s_lk,
                                             out_flags, out_coord, out_q, out_h, out_cost, out_lookups);
             flags = t.flags; lookups = t.lookups; performed = t.performed; evaluated = t.evaluated;
             succ_h = out_h[tid];
@@ -2193,73 +2173,6 @@ struct ExpandLds {
 // ---- the GetSuccs loop body (manip_lattice.cpp:254-305) in lane-sized pieces; expand_state_block (k_small_batch) and
 // k_search (search_kernel.h) put them together around their own barriers ----
 
-// can the primitive produce an action at all (a snap needs a joint-space goal: manip_lattice_action_space.cpp:551-559)
-__device__ __forceinline__ bool prim_has_action(const SmplxActionsDev& A, const SmplxGoalDev& G, int p)
-{
-    const int ty = A.type[p];
-    return ty == SMPLX_MP_LONG || ty == SMPLX_MP_SHORT || (ty == SMPLX_MP_SNAP_XYZ_RPY && G.type == SMPLX_GOAL_JOINT);
-}
-
-// bookkeeping lane of primitive p, first half: the successor's joint values -> X.sq[p] (applyMotionPrimitive,
-// manip_lattice_action_space.cpp:575-621)
-__device__ __forceinline__ void expand_successor_values(const ModelLds* __restrict__ M, const SmplxActionsDev& A,
-                                                        const SmplxGoalDev& G, ExpandLds& X, int p)
-{
-    const int nv = MV_NVARS(M);
-    const double* parent = X.parent;
-    const int type = A.type[p];
-    if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
-        double d0 = A.delta[p][0], d1 = nv > 1 ? A.delta[p][1] : 0.0;
-        if (A.xy_rotate_by_var3 && nv > 3) {
-            double sn, cs;
-            smplx_sincos(parent[3], &sn, &cs);
-            const double a0 = d0, a1 = d1;
-            d0 = cs * a0 + (-sn) * a1;
-            d1 = sn * a0 + cs * a1;
-        }
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v) {
-            const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[p][v]);
-            X.sq[p][v] = d + parent[v];
-        }
-    } else {
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v) X.sq[p][v] = G.angles[v];   // :551-559
-    }
-}
-
-// metric goal distance of the state in X.parent (bfs_heuristic.cpp:129-138): the gate of its primitives
-__device__ __forceinline__ double expand_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
-                                                       const ExpandLds& X)
-{
-    double pw[3];
-    planning_fk(M, X.parent, pw);
-    int c[3];
-    world_to_cell(grid, pw, c);
-    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
-}
-
-// waypoint count of the edge parent -> sq (robot_motion_collision_model.cpp:371-407, .h:352-366, 173-181)
-__device__ __forceinline__ int expand_waypoint_count(const ModelLds* __restrict__ M, const double* parent, const double* sq)
-{
-    const int nv = MV_NVARS(M);
-    double motion = 0.0;
-    MV_UNROLL
-    for (int v = 0; v < nv; ++v) {
-        const int vt = MV_TYPE(M, v);
-        const double sv = parent[v], fv = sq[v];
-        if (vt == SMPLX_JT_CONTINUOUS) motion += MV_K(M, v) * fabs(smplx_shortest_angle_diff(fv, sv));
-        else if (vt == SMPLX_JT_REVOLUTE) motion += MV_K(M, v) * fabs(fv - sv);
-        else if (vt == SMPLX_JT_PRISMATIC) motion += fabs(fv - sv);
-    }
-    int W = 0;
-    if (motion != 0.0) {
-        W = (int)ceil(motion / 0.05) + 1;
-        if (W < 2) W = 2;
-    }
-    return W;
-}
-
 // config lane c of the block: c < ncfg - 1: lane (p, slot) checks waypoints slot+1, slot+8, ... of edge p (an edge longer
 // than 7 waypoints wraps around its lanes); c == ncfg - 1: the state itself (waypoint 0 of every edge)
 template <bool RS = false>
@@ -2272,7 +2185,7 @@ __device__ __forceinline__ void expand_config_lane(const ModelLds* __restrict__ 
         if (prim_has_action(A, G, p) && mprim_active(A, X.goal_dist, A.type[p])) {
             const double* sq = X.sq[p];
             if (check_joint_limits(M, sq)) {
-                const int Wc = expand_waypoint_count(M, parent, sq);
+                const int Wc = edge_waypoint_count(M, parent, sq);
                 int my_bad = 0, my_lk = 0;
                 for (int wp = slot + 1; wp < Wc && !my_bad; wp += SMPLX_SMALL_LANES) {
                     EdgeRef e;
@@ -2295,7 +2208,7 @@ __device__ __forceinline__ void expand_config_lane(const ModelLds* __restrict__ 
     }
 }
 
-// bookkeeping lane of primitive p, second half, in two steps: (i) limits, waypoint count, coordinates (-> X.coord[p]);
+// bookkeeping lane of primitive p, behind successor_values, in two steps: (i) limits, waypoint count, coordinates (-> X.coord[p]);
 // (ii) planning-link FK, goal test, heuristic.  (k_search starts the state-table probe of the coordinate between the two.)
 struct BookLane { bool limits_ok; int W, h, is_goal; };
 __device__ __forceinline__ void expand_book_coords(const ModelLds* __restrict__ M, ExpandLds& X, int p, BookLane& r)
@@ -2305,7 +2218,7 @@ __device__ __forceinline__ void expand_book_coords(const ModelLds* __restrict__ 
     const double* sq = X.sq[p];
     r.limits_ok = check_joint_limits(M, sq);
     if (r.limits_ok) {
-        r.W = expand_waypoint_count(M, X.parent, sq);
+        r.W = edge_waypoint_count(M, X.parent, sq);
         MV_UNROLL
         for (int v = 0; v < nv; ++v) X.coord[p][v] = var_to_coord(M, v, sq[v]);
     }
@@ -2314,21 +2227,9 @@ __device__ __forceinline__ void expand_book_goal(const ModelLds* __restrict__ M,
                                                  const SmplxGoalDev& G, const ExpandLds& X, int p, BookLane& r)
 {
     if (!r.limits_ok) return;
-    const int nv = MV_NVARS(M);
-    double pw[3];
-    planning_fk(M, X.sq[p], pw);
-    if (G.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
-        r.is_goal = 1;
-        MV_UNROLL
-        for (int v = 0; v < nv; ++v)
-            if (fabs((double)(X.coord[p][v] - G.coord[v])) > G.angle_tol[v]) r.is_goal = 0;
-    } else {                                      // XYZ goal :1672-1687
-        r.is_goal = fabs(pw[0] - G.xyz[0]) <= G.xyz_tol[0] && fabs(pw[1] - G.xyz[1]) <= G.xyz_tol[1] &&
-                    fabs(pw[2] - G.xyz[2]) <= G.xyz_tol[2];
-    }
-    int c[3];
-    world_to_cell(grid, pw, c);
-    r.h = bfs_cost_to_goal(bfs, c);
+    bool is_goal;
+    r.h = successor_goal_h(M, G, bfs, grid, X.sq[p], X.coord[p], is_goal);
+    r.is_goal = is_goal;
 }
 __device__ __forceinline__ BookLane expand_book_lane(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
                                                      const SmplxGoalDev& G, ExpandLds& X, int p)
@@ -2379,9 +2280,8 @@ __device__ __forceinline__ void expand_state_block(const ModelLds* __restrict__ 
         if (bp < nv) X.parent[bp] = parent_src[bp];
         SMPLX_WAVE_SYNC();
     }
-    const bool have_action = book && prim_has_action(A, Sq->goal, bp);
-    if (have_action) expand_successor_values(M, A, Sq->goal, X, bp);
-    if (bp == nprims) X.goal_dist = expand_goal_distance(M, grid, bfs, X);
+    const bool have_action = book && successor_values(M, A, Sq->goal, bp, X.parent, X.sq[bp]);
+    if (bp == nprims) X.goal_dist = metric_goal_distance(M, grid, bfs, X.parent);
     __syncthreads();   // every lane of every edge can read its successor's joint values and the gate from LDS
     BookLane b;
     b.limits_ok = false; b.W = 0; b.h = 0; b.is_goal = 0;
@@ -2399,7 +2299,7 @@ __device__ __forceinline__ void expand_state_block(const ModelLds* __restrict__ 
 }
 
 extern "C" __global__ void __launch_bounds__(512)
-k_small_batch(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, const int64_t* __restrict__ refs, int B,
+k_small_batch(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
               double* __restrict__ goal_dist_out, unsigned char* __restrict__ state_bad_out, int* __restrict__ state_lookups_out,
               unsigned char* __restrict__ out_flags, int* __restrict__ out_coord, double* __restrict__ out_q,
               int* __restrict__ out_h, int* __restrict__ out_cost, int* __restrict__ out_lookups,
@@ -2423,8 +2323,7 @@ k_small_batch(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
     const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
     const int nprims = A.nprims, nv = MV_NVARS(M);
     const int t = threadIdx.x;
-    const long long parent_at = refs ? refs[si] : (int64_t)si;      // where the parent's joint values sit in Q (units of nv)
-    expand_state_block(M, L, S, Sq, grid, X, Q + parent_at * nv);
+    expand_state_block(M, L, S, Sq, grid, X, Q + si * nv);
     if (t == 0) { goal_dist_out[si] = X.goal_dist; state_bad_out[si] = (unsigned char)X.state_bad; state_lookups_out[si] = X.state_lookups; }
     if (t < nprims) {
         const long long eid = si * nprims + t;

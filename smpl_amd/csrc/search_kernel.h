@@ -398,6 +398,14 @@ struct SearchRegs {
     long long committed_evals, gpu_evals, lookups;
 };
 
+// getMetricGoalDistance recovered from a state's heuristic h = cost_per_cell * BFS distance (bfs_heuristic.cpp:129-138 /
+// 355-366: both read the BFS cell of the same planning-link position); the caller knows that the product is invertible.
+// The distance of an unreachable cell must stay the one metric_goal_distance (kernels.hip) gives.
+__device__ __forceinline__ double goal_distance_of_h(int h, int cpc, const SmplxGridDev& grid)
+{
+    return h == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(h / cpc) * grid.res;
+}
+
 // getOrCreateState's table side (manip_lattice.cpp:1302-1354) for the successors of one expansion, by a whole wave (lane =
 // primitive; every lane calls): hash and probe of each candidate's coordinate, the search state of a coordinate the table
 // knows, and among the unknown ones the pairs that share a coordinate (the lower primitive creates the state) or whose
@@ -800,15 +808,14 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     double gd;
                     if (gd_from_h) {
                         const int hh = (int)sm.h;
-                        gd = hh == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(hh / cpc) * grid.res;
+                        gd = goal_distance_of_h(hh, cpc, grid);
                     } else {
                         double g1 = 0.0;
-                        if (lane == 0) g1 = expand_goal_distance(M, grid, bfs, X);
+                        if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, X.parent);
                         const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
                         gd = __longlong_as_double((long long)bits);
                     }
-                    act = in && prim_has_action(A, G, lane) && mprim_active(A, gd, A.type[lane]);
-                    if (act) expand_successor_values(M, A, G, X, lane);
+                    act = in && mprim_active(A, gd, A.type[lane]) && successor_values(M, A, G, lane, X.parent, X.sq[lane]);
                     if (pend >= 0) { __syncthreads(); pend = -1; }   // B of the round that guessed wrong
                     if (in) X.lookups[lane] = act ? 1 : 0;
                     ++round_seq;
@@ -839,15 +846,14 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     double gd2;
                     if (gd_from_h) {
                         const int hh = (int)top_h;
-                        gd2 = hh == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(hh / cpc) * grid.res;
+                        gd2 = goal_distance_of_h(hh, cpc, grid);
                     } else {
                         double g1 = 0.0;
-                        if (lane == 0) g1 = expand_goal_distance(M, grid, bfs, Y);
+                        if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, Y.parent);
                         const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
                         gd2 = __longlong_as_double((long long)bits);
                     }
-                    top_act = in && prim_has_action(A, G, lane) && mprim_active(A, gd2, A.type[lane]);
-                    if (top_act) expand_successor_values(M, A, G, Y, lane);
+                    top_act = in && mprim_active(A, gd2, A.type[lane]) && successor_values(M, A, G, lane, Y.parent, Y.sq[lane]);
                     if (in) Y.lookups[lane] = top_act ? 1 : 0;
                     if (lane == 0) Y.goal_dist = gd2;
                     top_ready = true;
@@ -984,15 +990,14 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                         double gd2;
                         if (gd_from_h) {
                             const int hh = guess_succ ? wave_rl((int)ss.h, jbest) : (int)top_h;
-                            gd2 = hh == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(hh / cpc) * grid.res;
+                            gd2 = goal_distance_of_h(hh, cpc, grid);
                         } else {
                             double g1 = 0.0;
-                            if (lane == 0) g1 = expand_goal_distance(M, grid, bfs, Y);
+                            if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, Y.parent);
                             const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
                             gd2 = __longlong_as_double((long long)bits);
                         }
-                        p_act = in && prim_has_action(A, G, lane) && mprim_active(A, gd2, A.type[lane]);
-                        if (p_act) expand_successor_values(M, A, G, Y, lane);
+                        p_act = in && mprim_active(A, gd2, A.type[lane]) && successor_values(M, A, G, lane, Y.parent, Y.sq[lane]);
                         if (in) Y.lookups[lane] = p_act ? 1 : 0;
                         ++round_seq;
                         if (lane == 0) { Y.goal_dist = gd2; W.action = SA_EVAL; W.buf = nxt; W.seq = round_seq; }
