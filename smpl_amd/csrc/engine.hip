@@ -789,6 +789,9 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         if (wc->dirty) HIP_TRY(hipMemsetAsync(wc->p, 0, 2048, a.stream));
         wc->dirty = true;   // until the whole sequence is in the stream: k_pipe_finish leaves the set zeroed
         k.work_count = wc->p;
+        // Every kernel of the step takes nprims (s->M) and nvars (s->N) as arguments: a thread's state index is tid / nprims,
+        // and with the divisor in the kernel's arguments its first indexed load does not wait for one from the space record
+        // (a cross-query batch uses the lead space's actions for every row: one value per launch).
         // Three launches.  k_pipe_setup computes the goal distance of the states of each block itself and carries the K5
         // inserts in extra blocks.  With the test hook, k_pipe_prep does both in a launch of its own, as the step used to.
         // So it does for a batch whose setup blocks (3 waves each) no longer fit the chip at 4 waves per SIMD in one
@@ -807,20 +810,25 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         const int n_ins_setup = pipe_prep ? 0 : n_ins;
         KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be + blocks_for(n_ins_setup, SMPLX_BLOCK)), dim3(pipe_prep ? SMPLX_BLOCK : SMPLX_SETUP_BLOCK), lm, a.stream, s->d_space, a.q, B,
                            k.goal_dist, a.flags, a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
-                           k.work, k.work_count, k.capacity, a.stab, a.state_q, pipe_prep ? 1 : 0, cmp.totals, ins_items, n_ins_setup);
+                           k.work, k.work_count, k.capacity, a.stab, a.state_q, pipe_prep ? 1 : 0, cmp.totals, ins_items, n_ins_setup,
+                           s->M, s->N);
         if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
         // behind the bc collision blocks: one successor thread per edge (dense: it leaves at once where setup's flag is not 0)
         const int bc = blocks_for((long long)B + (long long)B * s->M * 3, SMPLX_BLOCK);
+        // the model image (inside the space record) and its size go to the collision blocks as arguments: their copy of
+        // it starts beside the shard counters, not behind a load of the header's size field
+        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space) + offsetof(SmplxSpaceDev, model_blob);
         KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, B,
                            a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
-                           k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal);
+                           k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal,
+                           s->M, s->N, blob, (int)s->blob_bytes);
         if (ev) (void)hipEventRecord(ev[1], a.stream);
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
         KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, B,
                            k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, a.flags, a.coord, a.sq, a.h,
                            a.cost, a.lookups, a.counters, k.goal_dist, a.stab, a.state_q, d_id, cmp, k.succ_eval, k.succ_goal, k.succ_coord,
-                           k.work_count);
+                           k.work_count, s->M, s->N);
         wc->dirty = false;
         if (ev) (void)hipEventRecord(ev[2], a.stream);
     }

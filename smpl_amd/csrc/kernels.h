@@ -46,13 +46,14 @@ __global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, int B, dou
                              unsigned char* edge_bad, int* state_lookups, unsigned char* state_bad, unsigned long long* work,
                              int* work_count, int capacity,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int have_goal_dist,
-                             int* cmp_totals, const int* ins_items, int n_ins);
+                             int* cmp_totals, const int* ins_items, int n_ins, int nprims, int nvars);
 __global__ void k_pipe_configs(const SmplxSpaceDev* S, const double* Q, int B, const double* out_q,
                                const int* edge_w, int* edge_lookups, unsigned char* edge_bad, int* state_lookups,
                                unsigned char* state_bad, const unsigned long long* work, const int* work_count, int capacity,
                                int cfg_blocks, const unsigned char* out_flags, int* succ_coord,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int want_id,
-                               unsigned long long* succ_eval, unsigned char* succ_goal);
+                               unsigned long long* succ_eval, unsigned char* succ_goal, int nprims, int nvars,
+                               const unsigned char* blob, int blob_bytes);
 __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, int B, const int* edge_w,
                               const int* edge_lookups, const unsigned char* edge_bad, const int* state_lookups,
                               const unsigned char* state_bad, unsigned char* out_flags, int* out_coord, double* out_q,
@@ -60,7 +61,7 @@ __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, int B, co
                               const double* goal_dist,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* out_id, SmplxCompactDev cmp,
                               const unsigned long long* succ_eval, const unsigned char* succ_goal, const int* succ_coord,
-                              int* work_count);
+                              int* work_count, int nprims, int nvars);
 __global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist_out,
                               unsigned char* state_bad_out, int* state_lookups_out, unsigned char* out_flags, int* out_coord,
                               double* out_q, int* out_h, int* out_cost, int* out_lookups,

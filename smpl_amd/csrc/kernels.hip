@@ -67,6 +67,7 @@ __device__ __forceinline__ LDS_AS unsigned char& lds_b(const ThreadLds& L, int e
 #ifdef SMPLX_CONST_MODEL
 #include SMPLX_CONST_MODEL
 #define MV_NVARS(M) CM_NV
+#define ARG_NVARS(nvars) CM_NV     // the variable count where a kernel has it as an argument (index arithmetic in front of the model)
 #define MV_TYPE(M, v) CM_VAR_TYPE[v]
 #define MV_MIN(M, v) CM_VAR_MIN[v]
 #define MV_MAX(M, v) CM_VAR_MAX[v]
@@ -77,6 +78,7 @@ __device__ __forceinline__ LDS_AS unsigned char& lds_b(const ThreadLds& L, int e
 #define MV_UNROLL _Pragma("unroll")
 #else
 #define MV_NVARS(M) (M)->nvars
+#define ARG_NVARS(nvars) (nvars)
 #define MV_TYPE(M, v) (M)->var_type[v]
 #define MV_MIN(M, v) (M)->var_min[v]
 #define MV_MAX(M, v) (M)->var_max[v]
@@ -1270,26 +1272,40 @@ k_table_insert(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* 
     table_insert_items(S, stab, items, n, nvars);
 }
 
-// Cooperative copy of the packed model (a few KB) into LDS in 16-byte pieces, all loads of a thread issued before
-// its first store; every later read of the model is a uniform-address LDS broadcast instead of a dependent
-// global load.  Returns the view.
-__device__ __forceinline__ ModelLds stage_model(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, int nthreads = BLOCK)
+// The first pieces of the packed model a thread copies (stage_model), in registers: all loads of a thread are issued
+// before its first store.  A kernel that has the image and its size as arguments starts them at its very top, beside
+// whatever else it reads first, and hands them to stage_model later.
+typedef double __attribute__((ext_vector_type(2))) model_piece_t;
+struct ModelFetch { model_piece_t v[4]; };
+__device__ __forceinline__ ModelFetch model_fetch(const unsigned char* __restrict__ blob, int blob_bytes, int nthreads = BLOCK)
 {
-    typedef double __attribute__((ext_vector_type(2))) d2_t;
-    const int* hdr = reinterpret_cast<const int*>(S->model_blob);
-    const d2_t* src = reinterpret_cast<const d2_t*>(S->model_blob);
-    d2_t* dst = reinterpret_cast<d2_t*>(smem);
-    const int total = hdr[SMPLX_BH_BYTES] / 16;
-    d2_t v[4];
+    const model_piece_t* src = reinterpret_cast<const model_piece_t*>(blob);
+    const int total = blob_bytes / 16;
+    ModelFetch f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = threadIdx.x + k * nthreads;
-        if (i < total) v[k] = src[i];
+        if (i < total) f.v[k] = src[i];
     }
+    return f;
+}
+
+// Cooperative copy of the packed model (a few KB) into LDS in 16-byte pieces; every later read of the model is a
+// uniform-address LDS broadcast instead of a dependent global load.  Returns the view.
+// blob, blob_bytes: the image (the space's model_blob) and its size; f: model_fetch(blob, blob_bytes, nthreads).  The
+// header fields that become offsets are read from the image; the copy waits for none of them.
+__device__ __forceinline__ ModelLds stage_model(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, int nthreads,
+                                                const unsigned char* __restrict__ blob, int blob_bytes, const ModelFetch& f)
+{
+    typedef model_piece_t d2_t;
+    const int* hdr = reinterpret_cast<const int*>(blob);
+    const d2_t* src = reinterpret_cast<const d2_t*>(blob);
+    d2_t* dst = reinterpret_cast<d2_t*>(smem);
+    const int total = blob_bytes / 16;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = threadIdx.x + k * nthreads;
-        if (i < total) dst[i] = v[k];
+        if (i < total) dst[i] = f.v[k];
     }
     for (int i = threadIdx.x + 4 * nthreads; i < total; i += nthreads) dst[i] = src[i];
     ModelLds M;
@@ -1313,17 +1329,24 @@ __device__ __forceinline__ ModelLds stage_model(const SmplxSpaceDev* __restrict_
     M.bodies = S->bodies;
     return M;
 }
+// ... for a kernel that learns the size from the image's header
+__device__ __forceinline__ ModelLds stage_model(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, int nthreads = BLOCK)
+{
+    const int bytes = reinterpret_cast<const int*>(S->model_blob)[SMPLX_BH_BYTES];
+    return stage_model(S, smem, nthreads, S->model_blob, bytes, model_fetch(S->model_blob, bytes, nthreads));
+}
 
 // model + per-thread scratch (root-position slots, saved transforms, DFS stack)
+// (blob, blob_bytes, f: as stage_model)
 __device__ __forceinline__ ThreadLds setup_lds(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, ModelLds* Mv,
-                                               int nthreads = BLOCK, bool slots_in_lds = true)
+                                               int nthreads, bool slots_in_lds,
+                                               const unsigned char* __restrict__ blob, int blob_bytes, const ModelFetch& f)
 {
     ThreadLds L;
-    *Mv = stage_model(S, smem, nthreads);
+    *Mv = stage_model(S, smem, nthreads, blob, blob_bytes, f);
     L.stride = nthreads;
-    const int* hdr = reinterpret_cast<const int*>(S->model_blob);
     L.nodes = Mv->nodes;
-    L.d = (LDS_AS double*)((LDS_AS unsigned char*)smem + hdr[SMPLX_BH_BYTES]);
+    L.d = (LDS_AS double*)((LDS_AS unsigned char*)smem + blob_bytes);
 #ifdef SMPLX_CONST_MODEL
     const int nroot = 0;   // per-robot build: the root positions that lead a checked pair live in registers (ChainState::roots)
 #else
@@ -1337,6 +1360,12 @@ __device__ __forceinline__ ThreadLds setup_lds(const SmplxSpaceDev* __restrict__
     L.stk = (LDS_AS unsigned char*)(L.d + nd * nthreads);
     __syncthreads();
     return L;
+}
+__device__ __forceinline__ ThreadLds setup_lds(const SmplxSpaceDev* __restrict__ S, unsigned char* smem, ModelLds* Mv,
+                                               int nthreads = BLOCK, bool slots_in_lds = true)
+{
+    const int bytes = reinterpret_cast<const int*>(S->model_blob)[SMPLX_BH_BYTES];
+    return setup_lds(S, smem, Mv, nthreads, slots_in_lds, S->model_blob, bytes, model_fetch(S->model_blob, bytes, nthreads));
 }
 
 // kernels that only need the model (no per-thread scratch)
@@ -1625,6 +1654,11 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int 
 // reference the three-launch step is compared against.
 // The work-list counters belong to the engine, one set per stream, and are all-zero between steps: block 0 of
 // k_pipe_finish clears them behind their last reader.
+// What the host knows comes in as kernel arguments, so that no thread's first indexed load waits for a load from the
+// space record: nprims (every thread's state index is tid / nprims; a cross-query batch uses the lead space's actions for
+// every row, so one value per launch is right), nvars (generic build: row strides in front of the staged model) and, for
+// the collision blocks of k_pipe_configs, the model image and its byte count (its copy starts beside the shard counters
+// instead of behind the header's size field).  S->actions stays the source of the action table's contents.
 // ---------------------------------------------------------------------------------------------
 
 // work item (64 bits): edge index | waypoint << 32 | waypoint count << 48, so that a configuration thread needs no
@@ -1677,11 +1711,11 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
              int* __restrict__ state_lookups, unsigned char* __restrict__ state_bad,
              unsigned long long* __restrict__ work, int* __restrict__ work_count, int capacity,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
-             int have_goal_dist, int* __restrict__ cmp_totals, const int* __restrict__ ins_items, int n_ins)
+             int have_goal_dist, int* __restrict__ cmp_totals, const int* __restrict__ ins_items, int n_ins,
+             int nprims, int nvars)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmplxActionsDev& A = S->actions;
-    const int nprims = A.nprims;
     const long long n_edges = (long long)B * nprims;
     // K5: the states the host committed since the last batch join the device table (createHashEntry) in extra blocks
     // behind the edge blocks; the table is first read one launch later (successor role of k_pipe_configs)
@@ -1691,7 +1725,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     const bool dist_wave = threadIdx.x >= BLOCK;   // the wave behind the edge threads
     const long long tid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const bool in_range = !dist_wave && tid < n_edges;
-    const int nv = MV_NVARS(M);
+    const int nv = ARG_NVARS(nvars);
     const int si = in_range ? (int)(tid / nprims) : 0;
     const int pi = in_range ? (int)(tid - (long long)si * nprims) : 0;
     const double* parent = Q + (int64_t)si * nv;
@@ -1820,9 +1854,8 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
                                                     int* __restrict__ succ_coord, const SmplxSpaceDev* const* __restrict__ stab,
                                                     const unsigned short* __restrict__ state_q, bool want_id,
                                                     unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal,
-                                                    unsigned char* smem)
+                                                    unsigned char* smem, int nprims, int nvars)
 {
-    const int nprims = S->actions.nprims;
     const long long tid = (long long)((int)blockIdx.x - cfg_blocks) * BLOCK + threadIdx.x;
     // as in the collision blocks: the flag (and, per-robot build, the joint values) are fetched BEFORE the model is staged
     const bool live = tid < (long long)B * nprims && out_flags[tid] == 0;
@@ -1837,7 +1870,7 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
     const ModelLds* M = &Mv;
     if (!live) return;
 #ifndef ABL_NO_SUCC
-    const int nv = MV_NVARS(M);
+    const int nv = ARG_NVARS(nvars);
     const int si = (int)(tid / nprims);
     const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;   // per-query goal, BFS grid and table in a cross-query batch
     const SmplxGridDev grid = S->grid;
@@ -1861,15 +1894,19 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
                const unsigned long long* __restrict__ work, const int* __restrict__ work_count, int capacity, int cfg_blocks,
                const unsigned char* __restrict__ out_flags, int* __restrict__ succ_coord,
                const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q, int want_id,
-               unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal)
+               unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal, int nprims, int nvars,
+               const unsigned char* __restrict__ blob, int blob_bytes)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     // the grid is cfg_blocks collision blocks, dispatched first (they hold the long waves), then one successor thread
     // per edge in blocks of their own
     if ((int)blockIdx.x >= cfg_blocks) {
-        pipe_successor_role(S, B, cfg_blocks, out_flags, out_q, succ_coord, stab, state_q, want_id != 0, succ_eval, succ_goal, smem);
+        pipe_successor_role(S, B, cfg_blocks, out_flags, out_q, succ_coord, stab, state_q, want_id != 0, succ_eval, succ_goal, smem,
+                            nprims, nvars);
         return;
     }
+    // the model image is known from the arguments: its first pieces travel beside the shard counters
+    const ModelFetch fetched = model_fetch(blob, blob_bytes);
 #ifdef SMPLX_CONST_MODEL
     constexpr bool RS = true;      // saved link transforms in registers (as k_state_valid): LDS per block without the slots, which
                                    // is what several batches in flight, or one large one, share a CU by
@@ -1894,7 +1931,6 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
     // values of its edge are fetched BEFORE the model is staged, so that they travel together with the model bytes
     // (5 round trips -> 3).
     if (total <= (long long)cfg_blocks * BLOCK) {
-        const int nprims = S->actions.nprims;
         constexpr int nv = CM_NV;
         const long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
         unsigned long long it = SMPLX_WORK_BLANK;
@@ -1918,7 +1954,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
             for (int v = 0; v < nv; ++v) { qs[v] = ps[v]; qf[v] = pf[v]; }
         }
         ModelLds Mv;
-        ThreadLds L = setup_lds(S, smem, &Mv, BLOCK, !RS);
+        ThreadLds L = setup_lds(S, smem, &Mv, BLOCK, !RS, blob, blob_bytes, fetched);
         const ModelLds* M = &Mv;
         const SmplxGridDev grid = S->grid;
         if (!(is_state || is_item)) return;
@@ -1947,11 +1983,10 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
     }
 #endif
     ModelLds Mv;
-    ThreadLds L = setup_lds(S, smem, &Mv, BLOCK, !RS);
+    ThreadLds L = setup_lds(S, smem, &Mv, BLOCK, !RS, blob, blob_bytes, fetched);
     const ModelLds* M = &Mv;
     const SmplxGridDev grid = S->grid;
-    const int nprims = S->actions.nprims;
-    const int nv = MV_NVARS(M);
+    const int nv = ARG_NVARS(nvars);
     for (long long i = (long long)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (long long)cfg_blocks * BLOCK) {
         EdgeRef e;
         int lk = 0;
@@ -1992,19 +2027,15 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
               unsigned long long* __restrict__ counters, const double* __restrict__ goal_dist,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
               int* __restrict__ out_id, SmplxCompactDev cmp, const unsigned long long* __restrict__ succ_eval,
-              const unsigned char* __restrict__ succ_goal, const int* __restrict__ succ_coord, int* __restrict__ work_count)
+              const unsigned char* __restrict__ succ_goal, const int* __restrict__ succ_coord, int* __restrict__ work_count,
+              int nprims, int nvars)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmplxActionsDev& A = S->actions;
-    const int nprims = A.nprims;
     // the stream's work-list counters (shards + deferred count) go back to zero for the next step's k_pipe_setup: their
     // last reader, k_pipe_configs, ended a launch ago
     if (blockIdx.x == 0 && threadIdx.x <= SMPLX_WORK_SHARDS) work_count[threadIdx.x * SMPLX_SHARD_STRIDE] = 0;
-#ifdef SMPLX_CONST_MODEL
-    constexpr int nv = CM_NV;
-#else
-    const int nv = S->model.nvars;   // (the model is not staged here)
-#endif
+    const int nv = ARG_NVARS(nvars);   // (the model is not staged here)
     const long long tid = (long long)blockIdx.x * BLOCK + threadIdx.x;
     const bool in_range = tid < (long long)B * nprims;
     int flags = SMPLX_F_INACTIVE, lookups = 0, performed = 0, evaluated = 0;
@@ -2119,8 +2150,6 @@ k_pipe_finish(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q,
         if (c_base[0] >= 0 && is_a) {
             int ia = c_base[0] + __popcll(m_a & below), ib = c_base[1] + __popcll(m_b & below);
             for (int k = 0; k < wv; ++k) { ia += c_cnt[k][0]; ib += c_cnt[k][1]; }
-            const int si = (int)(tid / nprims);
-            const int pi = (int)(tid - (long long)si * nprims);
             cmp.rec_a[2 * (size_t)ia] = succ_id;
             cmp.rec_a[2 * (size_t)ia + 1] = pi | ((flags & SMPLX_F_GOAL) ? 0x100 : 0) | (si << 9);
             if (is_b) {
