@@ -1,11 +1,26 @@
 // smpl_amd/csrc/search_host.h -- host side of the device-resident ARA* (kernel: search_kernel.h).
-// Included by engine.hip inside its anonymous namespace, after smplx_space is complete.
 //
 // The host launches k_search (one workgroup per query), enlarges a query's buffers when its workgroup asks
 // (SMPLX_SS_GROW), and reads results.  The lattice the device builds -- coordinates, joint values, heuristics, committed
 // successor lists, expansion log -- stays in HBM until somebody asks for it through the C-ABI (smplx_get_state,
 // smplx_expansion_log, smplx_get_succs ...): pull_lattice() then brings the host's arrays up to date, so that every entry
 // point sees one lattice whichever side created a state.
+#pragma once
+
+#include <algorithm>
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "device_table.h"
+#include "kernels.h"
+#include "space.h"
+#include "step.h"
+
+namespace {
 
 // one allocation per query, carved into the buffers of SmplxSearchDev
 typedef DevSearch::Caps SearchCaps;
@@ -61,7 +76,7 @@ bool search_on_device(const smplx_space* s)
 {
     const char* e = getenv("SMPLX_SEARCH");
     if (e && !std::strcmp(e, "host")) return false;
-    if (s->fused_mode || s->work_list_items > 0 || s->small_batch_max == 0) return false;   // spaces set up to exercise a particular host path
+    if (s->step.fused_mode || s->step.work_list_items > 0 || s->small.batch_max == 0) return false;   // spaces set up to exercise a particular host path
     return search_heap_cache_entries(s, nullptr) > 0;
 }
 
@@ -114,13 +129,13 @@ int search_reserve(smplx_space* s, const SearchCaps& want)
         ++D.grows;
     }
     // the state table: at most half full with cap_states states
-    size_t tcap = s->table_cap ? s->table_cap : ((size_t)1 << 16);
+    size_t tcap = s->dt.cap ? s->dt.cap : ((size_t)1 << 16);
     while (tcap < 2 * (size_t)c.states) tcap *= 2;
-    if (!s->d_table || tcap != s->table_cap) {
+    if (!s->dt.d_table || tcap != s->dt.cap) {
         HIP_TRY(hipStreamSynchronize(s->stream));
         if (int e = table_alloc(s, tcap)) return e;
         D.table_fresh = true;   // empty: every state is inserted again (k_search_table_fill)
-        s->pending_ins.clear();
+        s->dt.pending_ins.clear();
     }
     if (s->hs.search != D.d_hdr || grow || D.table_fresh) {
         s->hs.search = D.d_hdr;
@@ -134,16 +149,16 @@ int search_push_lattice(smplx_space* s)
 {
     DevSearch& D = s->ds;
     const int N = s->N;
-    const int have = (int)s->h_of_id.size();
+    const int have = (int)s->lat.h_of_id.size();
     if (D.dev_states < have) {
         const int first = D.dev_states, n = have - first;
-        HIP_TRY(hipMemcpyAsync(D.h.coord + (size_t)first * N, &s->coords[(size_t)first * N], sizeof(int32_t) * (size_t)n * N, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(D.h.q + (size_t)first * N, &s->qs[(size_t)first * N], sizeof(double) * (size_t)n * N, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(D.h.coord + (size_t)first * N, &s->lat.coords[(size_t)first * N], sizeof(int32_t) * (size_t)n * N, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(D.h.q + (size_t)first * N, &s->lat.qs[(size_t)first * N], sizeof(double) * (size_t)n * N, hipMemcpyHostToDevice, s->stream));
         std::vector<SmplxSState> st(n);
         std::vector<int32_t> off(n, -1), cnt(n, 0);
         for (int i = 0; i < n; ++i) {
             std::memset(&st[i], 0, sizeof(SmplxSState));
-            st[i].h = (uint32_t)s->h_of_id[first + i];
+            st[i].h = (uint32_t)s->lat.h_of_id[first + i];
             st[i].bp = -1;
         }
         HIP_TRY(hipMemcpyAsync(D.h.st + first, st.data(), sizeof(SmplxSState) * n, hipMemcpyHostToDevice, s->stream));
@@ -162,8 +177,8 @@ int search_fill_table(smplx_space* s, int first_missing, int nstates)
     DevSearch& D = s->ds;
     const int first = D.table_fresh ? 0 : first_missing;
     D.table_fresh = false;
-    s->pending_ins.clear();
-    s->table_count = nstates > 0 ? (size_t)nstates - 1 : 0;
+    s->dt.pending_ins.clear();
+    s->dt.count = nstates > 0 ? (size_t)nstates - 1 : 0;
     if (first >= nstates) return SMPLX_OK;
     hipLaunchKernelGGL(k_search_table_fill, dim3(std::max(1, std::min(1024, blocks_for(nstates - first, 256)))), dim3(256), 0, s->stream,
                        s->d_space, (const int32_t*)D.h.coord, first, nstates, s->N);
@@ -181,25 +196,17 @@ int pull_lattice(smplx_space* s)
     HIP_TRY(hipStreamSynchronize(s->stream));
     SmplxSearchDev h;
     HIP_TRY(hipMemcpy(&h, D.d_hdr, sizeof(h), hipMemcpyDeviceToHost));
-    const int have = (int)s->h_of_id.size(), total = h.nstates;
+    const int have = (int)s->lat.h_of_id.size(), total = h.nstates;
     if (total > have) {
         const int n = total - have;
-        s->coords.resize((size_t)total * N);
-        s->qs.resize((size_t)total * N);
-        HIP_TRY(hipMemcpy(&s->coords[(size_t)have * N], h.coord + (size_t)have * N, sizeof(int32_t) * (size_t)n * N, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&s->qs[(size_t)have * N], h.q + (size_t)have * N, sizeof(double) * (size_t)n * N, hipMemcpyDeviceToHost));
+        s->lat.extend(total);
+        HIP_TRY(hipMemcpy(&s->lat.coords[(size_t)have * N], h.coord + (size_t)have * N, sizeof(int32_t) * (size_t)n * N, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&s->lat.qs[(size_t)have * N], h.q + (size_t)have * N, sizeof(double) * (size_t)n * N, hipMemcpyDeviceToHost));
         std::vector<SmplxSState> st(n);
         HIP_TRY(hipMemcpy(st.data(), h.st + have, sizeof(SmplxSState) * n, hipMemcpyDeviceToHost));
-        s->h_of_id.resize(total);
-        for (int i = 0; i < n; ++i) s->h_of_id[have + i] = (int32_t)st[i].h;
-        s->cache_off.resize(total, -1);
-        s->cache_cnt.resize(total, 0);
-        s->done_off.resize(total, -1);
-        s->done_cnt.resize(total, 0);
-        s->eval_count.resize(total, 0);
-        if (s->plain_mode) s->g_est.resize(total, 1000000000u);
-        for (int id = have; id < total; ++id) s->table.insert(id, s->coords);
-        s->table_count = (size_t)total - 1;
+        for (int i = 0; i < n; ++i) s->lat.h_of_id[have + i] = (int32_t)st[i].h;
+        s->lat.index_from(have);
+        s->dt.count = (size_t)total - 1;
     }
     // committed successor lists
     {
@@ -209,16 +216,16 @@ int pull_lattice(smplx_space* s)
         std::vector<SmplxSucc> succ((size_t)h.n_succ);
         if (h.n_succ) HIP_TRY(hipMemcpy(succ.data(), h.succ, sizeof(SmplxSucc) * (size_t)h.n_succ, hipMemcpyDeviceToHost));
         for (int id = 1; id < total; ++id) {
-            if (off[id] < 0 || s->done_off[id] >= 0) continue;
+            if (off[id] < 0 || s->lat.done_off[id] >= 0) continue;
             const int c = cnt[id] & 0xFF;
-            s->done_off[id] = (int64_t)s->done_succ.size();
-            s->done_cnt[id] = c;
-            s->eval_count[id] = cnt[id] >> 8;
+            s->lat.done_off[id] = (int64_t)s->lat.done_succ.size();
+            s->lat.done_cnt[id] = c;
+            s->lat.eval_count[id] = cnt[id] >> 8;
             for (int k = 0; k < c; ++k) {
                 const SmplxSucc& e = succ[(size_t)off[id] + k];
-                s->done_succ.push_back(e.id);
-                s->done_cost.push_back(e.cost_prim & 0xFFFFFF);
-                s->done_prim.push_back((int32_t)((uint32_t)e.cost_prim >> 24));
+                s->lat.done_succ.push_back(e.id);
+                s->lat.done_cost.push_back(e.cost_prim & 0xFFFFFF);
+                s->lat.done_prim.push_back((int32_t)((uint32_t)e.cost_prim >> 24));
             }
         }
     }
@@ -261,7 +268,7 @@ int search_begin(smplx_space* s, const smplx_time_params* p, bool resume, double
 {
     DevSearch& D = s->ds;
     if (resume) {
-        const int have = (int)s->h_of_id.size();
+        const int have = (int)s->lat.h_of_id.size();
         if (!D.host_behind && have > D.h.nstates) {
             // states the host created since (smplx_get_succs of a state the search never expanded): the device takes them
             SearchCaps c = D.caps;
@@ -281,7 +288,7 @@ int search_begin(smplx_space* s, const smplx_time_params* p, bool resume, double
         return SMPLX_OK;
     }
     if (int e = pull_lattice(s)) return e;       // a search the device ran earlier on this goal: one lattice
-    const int have = (int)s->h_of_id.size();
+    const int have = (int)s->lat.h_of_id.size();
     SearchCaps c;
     // a bounded search creates at most `bound * primitives` states; sized for ~10 per expansion so that the ordinary query
     // never has to stop for an enlargement (each costs its workgroup the rest of a launch)
@@ -297,11 +304,11 @@ int search_begin(smplx_space* s, const smplx_time_params* p, bool resume, double
     c.path = 1 << 16;
     if (int e = search_reserve(s, c)) return e;
     if (int e = search_push_lattice(s)) return e;
-    if (int e = search_fill_table(s, have - (int)(s->pending_ins.size() / ((size_t)s->N + 2)), have)) return e;
+    if (int e = search_fill_table(s, have - (int)(s->dt.pending_ins.size() / ((size_t)s->N + 2)), have)) return e;
     SmplxSearchDev& h = D.h;
     h.initial_eps = p->initial_eps;
     search_set_budget(h, p, ticks_per_s);
-    h.start_id = s->start_id;
+    h.start_id = s->lat.start_id;
     h.curr_eps = p->initial_eps; h.satisfied_eps = std::numeric_limits<double>::infinity();
     h.nstates = have;
     h.heap_size = 0; h.n_incons = 0; h.n_log = 0; h.n_path = 0;
@@ -372,7 +379,7 @@ int search_run_launches(smplx_space** spaces, int nq, const smplx_time_params* p
         if (int e = lead->b_stab.reserve(nq)) return e;
         HIP_TRY(hipMemcpy(lead->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
     }
-    PinBuf<int32_t>& status = lead->p_ins;      // nq ints the workgroups write when they leave
+    PinBuf<int32_t>& status = lead->dt.p_ins;      // nq ints the workgroups write when they leave
     if (int e = status.reserve((size_t)nq)) return e;
     size_t lds = 0;
     const int lh = search_heap_cache_entries(lead, &lds);
@@ -479,3 +486,5 @@ int search_run(smplx_space** spaces, int nq, const smplx_time_params* p, const c
     }
     return rc;
 }
+
+}  // namespace
