@@ -209,6 +209,28 @@ int smplx_cc_attached_positions(smplx_space* s, const double* q, int n, double* 
 int smplx_set_goal_joint(smplx_space* s, const double* angles, const double* tolerances);
 /* XYZ_GOAL (manip_lattice.cpp:1672-1687) */
 int smplx_set_goal_xyz(smplx_space* s, const double xyz[3], const double tol[3]);
+/* The goals of nq spaces in ONE call: smplx_set_goal_joint / smplx_set_goal_xyz for spaces[q] with row q of the arrays
+ * (angles, tolerances: nq rows of the spaces' number of variables; xyz, tol: nq rows of 3).  The BFS runs of all goals
+ * share one sequence of launches on the leading space's stream -- in every pass each goal's queued bricks are visited
+ * side by side, each goal in its own space's grid -- where the single calls run about 45 narrow launches per goal one
+ * goal after the other; the goal poses of joint goals come from one FK launch when the spaces run the same kernels
+ * on the same model image.
+ * Contract: afterwards every space is in exactly the state the single-goal call would have left it in -- goal record,
+ * goal pose (bit-equal), BFS grid, metric distances, smplx_get_goal_heuristic(0), the lattice reset, the grid and
+ * attached-body epochs -- so smplx_set_start, smplx_plan*, smplx_replan* and smplx_get_succs follow as usual, and a later
+ * smplx_set_goal_* on any of the spaces is right as well.  The brick sweep is label-correcting: its fixed point, the exact
+ * 26-connected hop counts, does not depend on the order or the launch in which bricks are visited.  The one visible
+ * difference: smplx_bfs_levels returns the number of passes of the SHARED sequence, the same for every space of the call
+ * (the longest goal's passes plus the empty pass that ends the sequence).
+ * The spaces must live on one device and have the same number of 8x8x8 bricks per axis (and, for joint goals, of
+ * variables); they need not share a grid handle, walls (a space keeps the walls of the grid as it was when the space
+ * was created), robot or primitives.  nq = 1 is allowed and equals the single call.  The call allocates nothing that
+ * grows with nq x grid size: every goal uses the buffers its space already holds.
+ * All arguments are checked before any space is touched.  SMPLX_E_ARG: a null pointer, nq < 1, the same space twice
+ * (checked on the handles alone), a non-finite value (|v| >= 1e6 for angles), spaces on different devices or with
+ * different bricks per axis.  After a HIP error no space of the call has a goal: set the goals again. */
+int smplx_set_goals_joint_multi(smplx_space** spaces, int nq, const double* angles /* nq x nvars */, const double* tolerances /* nq x nvars */);
+int smplx_set_goals_xyz_multi(smplx_space** spaces, int nq, const double* xyz /* nq x 3 */, const double* tol /* nq x 3 */);
 int smplx_goal_pose(const smplx_space* s, double xyz[3]);
 /* GetGoalHeuristic for arbitrary states (bfs_heuristic.cpp:148-163); xyz (n*3) may be NULL */
 int smplx_heuristic_batch(smplx_space* s, const double* q, int n, int32_t* h, double* xyz);
@@ -222,7 +244,8 @@ int smplx_bfs_metric_start_distance(smplx_space* s, const double* xyz, int n, do
 /* the padded (nx+2)(ny+2)(nz+2) BFS_3D distance grid, node order of bfs3d.h:213-220 */
 int64_t smplx_bfs_size(const smplx_space* s);
 int smplx_bfs_copy(smplx_space* s, int32_t* out);
-/* passes the last BFS took: sweeps over the queued 8x8x8 bricks (the device keeps the grid in brick-major records) */
+/* passes the last BFS took: sweeps over the queued 8x8x8 bricks (the device keeps the grid in brick-major records); after
+ * smplx_set_goals_*_multi the passes of the shared sequence, the same for every space of the call */
 int smplx_bfs_levels(const smplx_space* s);
 
 /* ---- ManipLattice (smpl/include/smpl/graph/manip_lattice.h:63-307) ---- */

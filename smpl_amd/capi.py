@@ -36,7 +36,7 @@ SYMBOLS = [
     "smplx_compact_totals_len", "smplx_compact_capacity",
     "smplx_grid_create_empty", "smplx_grid_add_boxes", "smplx_grid_add_points", "smplx_grid_remove_points", "smplx_grid_copy_d2",
     "smplx_search_counters", "smplx_grid_set_ref_counted", "smplx_grid_update_points", "smplx_grid_copy_counts", "smplx_grid_last_edit_cells",
-    "smplx_replan", "smplx_replan_multi",
+    "smplx_replan", "smplx_replan_multi", "smplx_set_goals_joint_multi", "smplx_set_goals_xyz_multi",
     "smplx_attach_body", "smplx_detach_body", "smplx_attached_bodies", "smplx_attached_nodes", "smplx_cc_attached_positions",
 ]
 
@@ -406,6 +406,25 @@ class Space:
     def set_goal_xyz(self, xyz, tol):
         a = _f64(xyz); t = _f64(tol)
         _chk(lib().smplx_set_goal_xyz(self.h, _p(a, _dp), _p(t, _dp)))
+
+    @staticmethod
+    def set_goals_joint_multi(spaces, angles, tols):
+        """set_goal_joint for spaces[q] with row q of angles / tols, the BFS runs of all goals in one shared
+        sequence of launches (smplx_set_goals_joint_multi)."""
+        nq = len(spaces)
+        a = _f64(angles).reshape(nq, -1); t = _f64(tols).reshape(nq, -1)
+        H = (C.c_void_p * max(nq, 1))(*[sp.h for sp in spaces])
+        lib().smplx_set_goals_joint_multi.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        _chk(lib().smplx_set_goals_joint_multi(H, nq, _p(a, _dp), _p(t, _dp)))
+
+    @staticmethod
+    def set_goals_xyz_multi(spaces, xyz, tols):
+        """set_goal_xyz for spaces[q] with row q of xyz / tols in one call (smplx_set_goals_xyz_multi)."""
+        nq = len(spaces)
+        a = _f64(xyz).reshape(nq, 3); t = _f64(tols).reshape(nq, 3)
+        H = (C.c_void_p * max(nq, 1))(*[sp.h for sp in spaces])
+        lib().smplx_set_goals_xyz_multi.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        _chk(lib().smplx_set_goals_xyz_multi(H, nq, _p(a, _dp), _p(t, _dp)))
 
     def goal_pose(self):
         x = np.zeros(3)

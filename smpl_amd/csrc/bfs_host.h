@@ -1,6 +1,7 @@
 // smpl_amd/csrc/bfs_host.h -- host driver of the BFS heuristic's distance field (BfsHost in space.h; kernels.hip
 // k_bfs_brick_seed / k_bfs_brick_wave): from the goal cell, passes over the queued 8x8x8 bricks until none is queued,
-// with launch sizes taken from the queue sizes of the previous goal's run.
+// with launch sizes taken from the queue sizes of the previous goal's run.  run_bfs does it for one space, run_bfs_multi
+// for the goals of several spaces in one shared sequence of launches (k_bfs_brick_seed_multi / k_bfs_brick_wave_multi).
 #pragma once
 
 #include <chrono>
@@ -18,13 +19,20 @@ namespace {
 
 constexpr int kBfsHistory = 2048;   // passes whose queue sizes are kept behind the counters (d_counts)
 
+// the cell of a goal position in the space's grid (BFS_3D::run's argument); false: outside the grid (bfs3d.cpp:169-171)
+bool bfs_goal_cell(const smplx_space* s, const double xyz[3], int c[3])
+{
+    const smplx_grid* g = s->grid;
+    for (int a = 0; a < 3; ++a) c[a] = (int)(g->dev.inv_res * (xyz[a] - g->dev.origin_minus_res[a]) + 0.5) - 1;
+    return !(c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= g->n[0] || c[1] >= g->n[1] || c[2] >= g->n[2]);
+}
+
 // BFS_3D::run to completion on the device (bfs3d.cpp:156-201, 507-547): passes over the queued 8x8x8 bricks until none is
 // queued (kernels.hip k_bfs_brick_wave)
 int run_bfs(smplx_space* s, const double xyz[3])
 {
-    const smplx_grid* g = s->grid;
     int c[3];
-    for (int a = 0; a < 3; ++a) c[a] = (int)(g->dev.inv_res * (xyz[a] - g->dev.origin_minus_res[a]) + 0.5) - 1;
+    const bool in_bounds = bfs_goal_cell(s, xyz, c);
     // BFS_3D::run's reset (bfs3d.cpp:162-166): the run's tag makes every other run's distances UNDISCOVERED; a pass over
     // the records only when the tags wrap (finish_goal chose the tag and uploaded it)
     if (s->bfs.reset_due) {
@@ -34,7 +42,6 @@ int run_bfs(smplx_space* s, const double xyz[3])
     }
     const int tag_word = s->hs.bfs.tag_word, tag_mask = s->hs.bfs.tag_mask;
     s->bfs.levels = 0;
-    const bool in_bounds = !(c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= g->n[0] || c[1] >= g->n[1] || c[2] >= g->n[2]);
     if (!in_bounds) {   // bfs3d.cpp:169-171: nothing is labelled
         HIP_TRY(hipStreamSynchronize(s->stream));
         return SMPLX_OK;
@@ -113,6 +120,99 @@ int run_bfs(smplx_space* s, const double xyz[3])
     }
     s->bfs.queue_sizes.assign(cnt.begin() + 3 * kShards * 32, cnt.begin() + 3 * kShards * 32 + std::min(pass, kBfsHistory));
     s->bfs.levels = pass;
+    return SMPLX_OK;
+}
+
+// run_bfs for the goals of nq spaces at once (smplx_set_goals_*_multi): one seed launch, then passes in which every goal's
+// queued bricks are visited side by side (k_bfs_brick_wave_multi: blockIdx.y = goal), on the leading space's stream.  Each
+// goal works on its own space's records, lists, counters and queued words under its own tag, so nothing here grows with
+// nq x nbricks, and each goal's records reach the fixed point of the label-correcting sweep -- the exact hop counts --
+// whatever passes the other goals need.  The caller has checked that the spaces live on one device and have the same
+// bricks per axis, and has chosen and uploaded each space's tag.  The sequence ends when a pass found nothing queued for
+// any goal; its length is every space's `levels`.
+int run_bfs_multi(smplx_space* const* spaces, int nq)
+{
+    smplx_space* lead = spaces[0];
+    hipStream_t stream = lead->stream;
+    const int nbx = lead->bfs.bricks[0], nby = lead->bfs.bricks[1], nbz = lead->bfs.bricks[2];
+    const int nbricks = nbx * nby * nbz;
+    for (int q = 1; q < nq; ++q) HIP_TRY(hipStreamSynchronize(spaces[q]->stream));   // once: their work so far is behind us
+    std::vector<SmplxBfsGoalDev> goals((size_t)nq);
+    for (int q = 0; q < nq; ++q) {
+        smplx_space* s = spaces[q];
+        if (s->bfs.reset_due) {     // this space's tags wrapped (run_bfs)
+            hipLaunchKernelGGL(k_bfs_reset, dim3(2048), dim3(256), 0, stream, s->bfs.d_dist, (size_t)s->bfs.ints);
+            HIP_TRY(hipGetLastError());
+            s->bfs.reset_due = false;
+        }
+        s->bfs.levels = 0;
+        SmplxBfsGoalDev& G = goals[q];
+        G.dist = s->bfs.d_dist; G.lists = s->bfs.d_queue; G.counts = s->bfs.d_counts; G.queued = s->bfs.d_brick_queued;
+        G.tag_word = s->hs.bfs.tag_word; G.tag_mask = s->hs.bfs.tag_mask;
+        int c[3];
+        const bool in_bounds = bfs_goal_cell(s, s->goal_xyz, c);
+        for (int a = 0; a < 3; ++a) G.cell[a] = in_bounds ? c[a] : -1;
+        G.pad = 0;
+    }
+    // per pass {sum, largest} of the goals' queue sizes, and one more slot for a pass beyond the history
+    const int n_stats = kBfsHistory + 1;
+    if (int e = lead->bfs.b_goals.reserve((size_t)nq)) return e;
+    if (int e = lead->bfs.b_pass_stats.reserve((size_t)2 * n_stats)) return e;
+    const SmplxBfsGoalDev* d_goals = lead->bfs.b_goals.p;
+    int32_t* d_stats = lead->bfs.b_pass_stats.p;
+    HIP_TRY(hipMemcpyAsync(lead->bfs.b_goals.p, goals.data(), sizeof(SmplxBfsGoalDev) * nq, hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_bfs_brick_seed_multi, dim3(nq), dim3(64), 0, stream, d_goals, nq, nbx, nby, nbz, d_stats, n_stats);
+    HIP_TRY(hipGetLastError());
+    // Launch sizes, as in run_bfs: the x width of a pass is sized by the LARGEST queue any goal had around that pass in the
+    // spaces' last runs (the per-pass maxima over their queue_sizes); every block reads its goal's counters even when it has
+    // no brick, and here there are nq rows of them, so the floor is lower than for one goal.  Without a plan, or past it:
+    // chunks of 16 passes, 4 once fewer than 256 bricks are queued over all goals.
+    std::vector<int32_t> plan;
+    for (int q = 0; q < nq; ++q) {
+        const std::vector<int32_t>& h = spaces[q]->bfs.queue_sizes;
+        if (h.size() > plan.size()) plan.resize(h.size(), 0);
+        for (size_t k = 0; k < h.size(); ++k) plan[k] = std::max(plan[k], h[k]);
+    }
+    int planned = 0;
+    for (size_t k = 0; k < plan.size(); ++k) if (plan[k] > 0) planned = (int)k + 1;
+    const int wave_grid_max = 16384, wave_grid_tail = 2048, wave_grid_min = 64;
+    int chunk = planned > 0 ? planned + 2 : 16;
+    const bool dbg = getenv("SMPLX_DEBUG_TIMING") != nullptr;
+    if (dbg) chunk = 1;
+    auto grid_of = [&](int p) {
+        if (p >= planned) return wave_grid_tail;
+        int m = 0;
+        for (int k = std::max(0, p - 1); k <= std::min(planned - 1, p + 1); ++k) m = std::max(m, plan[k]);
+        return std::min(wave_grid_max, std::max(wave_grid_min, 2 * m));
+    };
+    std::vector<int32_t> stats((size_t)2 * n_stats);
+    int pass = 0;
+    while (true) {
+        const auto tp0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < chunk; ++k, ++pass) {
+            // a pass beyond the history keeps no queue sizes; the last of a chunk leaves its totals in the spare slot
+            int32_t* slot = pass < kBfsHistory ? d_stats + 2 * pass : (k == chunk - 1 ? d_stats + 2 * kBfsHistory : (int32_t*)nullptr);
+            if (pass >= kBfsHistory && slot) HIP_TRY(hipMemsetAsync(slot, 0, 2 * sizeof(int32_t), stream));
+            hipLaunchKernelGGL(k_bfs_brick_wave_multi, dim3(std::min(nbricks, grid_of(pass)), nq), dim3(64), 0, stream, d_goals, nbx, nby, nbz, pass,
+                               pass < kBfsHistory ? pass : -1, slot);
+        }
+        HIP_TRY(hipGetLastError());
+        const int last = std::min(pass - 1, kBfsHistory);     // the slot of the last pass enqueued
+        HIP_TRY(hipMemcpyAsync(stats.data(), d_stats, sizeof(int32_t) * 2 * ((size_t)last + 1), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        const long visited = stats[(size_t)2 * last];     // bricks the last pass had queued, over all goals
+        if (dbg)
+            fprintf(stderr, "[smplx bfs multi] pass %d: %.1f us (launch + sync), %ld bricks queued over %d goals, at most %d for one\n", pass - 1,
+                    1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count(), visited, nq, (int)stats[(size_t)2 * last + 1]);
+        if (visited == 0) break;      // it queued nothing either: every goal's front has died out
+        if (!dbg) chunk = visited < 256 ? 4 : 16;
+        // (a label-correcting brick sweep can legitimately need on the order of nbricks passes on maze-like free space)
+        if (pass > 4 * nbricks + 1024) return set_error(SMPLX_E_HIP, "BFS did not terminate");
+    }
+    // the launch-size hint of each space's next run, single or shared: the per-pass maxima of this one
+    std::vector<int32_t> sizes((size_t)std::min(pass, kBfsHistory));
+    for (size_t k = 0; k < sizes.size(); ++k) sizes[k] = stats[2 * k + 1];
+    for (int q = 0; q < nq; ++q) { spaces[q]->bfs.queue_sizes = sizes; spaces[q]->bfs.levels = pass; }
     return SMPLX_OK;
 }
 

@@ -120,6 +120,21 @@ struct SmplxBfsDev {
     const int32_t* dist;                      // nbx * nby * nbz records
 };
 
+// One goal of a BFS run that sets the goals of several spaces in shared launches (k_bfs_brick_seed_multi,
+// k_bfs_brick_wave_multi; bfs_host.h run_bfs_multi): what a single-goal run passes to its kernels as arguments, all of it
+// the space's own memory.  The launch's blockIdx.y picks the record.
+#define SMPLX_BFS_SHARDS 16      // the brick list of a pass is cut into sub-lists with their counters on separate 128-byte lines
+#define SMPLX_BFS_COUNTERS (3 * SMPLX_BFS_SHARDS * 32)   // three counter sets, one counter per 128-byte line; the history follows
+struct SmplxBfsGoalDev {
+    int32_t* dist;                // the space's records (SmplxBfsDev::dist)
+    int32_t* lists;               // two brick lists of SMPLX_BFS_SHARDS * nbricks entries each
+    int32_t* counts;              // SMPLX_BFS_COUNTERS counters, then one history slot per pass
+    int32_t* queued;              // two "queued for the next pass" arrays of nbricks words each
+    int32_t tag_word, tag_mask;   // of this space's run: every space counts its own
+    int32_t cell[3];              // the goal cell; cell[0] < 0: outside the grid, the goal takes no part
+    int32_t pad;
+};
+
 struct SmplxActionsDev {
     int32_t nprims, use_long_and_short, xy_rotate_by_var3, pad;
     int32_t enabled[4];

@@ -736,7 +736,10 @@ int smplx_cc_attached_positions(smplx_space* s, const double* q, int n, double* 
     return SMPLX_OK;
 }
 
-static int finish_goal(smplx_space* s)
+// A goal is set in three steps, shared by the single-goal entry points (finish_goal) and the multi-goal ones
+// (finish_goals_multi): begin_goal -- the goal position into the device record, the tag of this goal's BFS run, the
+// upload; the BFS (run_bfs / run_bfs_multi); end_goal -- the goal stands, the query starts over.
+static int begin_goal(smplx_space* s)
 {
     for (int a = 0; a < 3; ++a) s->hs.goal.xyz[a] = s->goal_xyz[a];
     // the tag of this goal's BFS run (device_types.h SmplxBfsDev): 1..7, a reset of the records when they wrap
@@ -749,30 +752,50 @@ static int finish_goal(smplx_space* s)
         s->bfs.tag = 1;
         s->hs.bfs.tag_word = 0;
     }
-    if (int e = upload_space(s)) return e;
-    if (int e = run_bfs(s, s->goal_xyz)) return e;
+    return upload_space(s);
+}
+
+static void end_goal(smplx_space* s)
+{
     s->goal_set = true;
     s->grid_epoch = s->grid->epoch;
     s->att.epoch_goal = s->att.epoch;
     // a new goal starts a new query: the state table restarts (ids are per query)
     reset_lattice(s);
     // heuristic of the goal id = BFS cost at the goal pose's cell (manip_lattice.cpp:1176-1190)
-    const smplx_grid* g = s->grid;
     int c[3];
-    for (int a = 0; a < 3; ++a) c[a] = (int)(g->dev.inv_res * (s->goal_xyz[a] - g->dev.origin_minus_res[a]) + 0.5) - 1;
-    const bool in_bounds = !(c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= g->n[0] || c[1] >= g->n[1] || c[2] >= g->n[2]);
-    s->lat.h_of_id[0] = in_bounds ? 0 : 32767;   // the seeded cell has distance 0 (bfs3d.cpp:178)
+    s->lat.h_of_id[0] = bfs_goal_cell(s, s->goal_xyz, c) ? 0 : 32767;   // the seeded cell has distance 0 (bfs3d.cpp:178)
+}
+
+static int finish_goal(smplx_space* s)
+{
+    if (int e = begin_goal(s)) return e;
+    if (int e = run_bfs(s, s->goal_xyz)) return e;
+    end_goal(s);
     return SMPLX_OK;
+}
+
+// the goal record of a joint goal, all but the goal pose (planner_interface.cpp:1232-1235 takes it from the FK)
+static void joint_goal_record(smplx_space* s, const double* angles, const double* tolerances)
+{
+    SmplxGoalDev& G = s->hs.goal;
+    G.type = SMPLX_GOAL_JOINT;
+    for (int v = 0; v < s->N; ++v) { G.angles[v] = angles[v]; G.angle_tol[v] = tolerances[v]; }
+    state_to_coord(s->model.dev, angles, G.coord);
+}
+
+static void xyz_goal_record(smplx_space* s, const double xyz[3], const double tol[3])
+{
+    SmplxGoalDev& G = s->hs.goal;
+    G.type = SMPLX_GOAL_XYZ;
+    for (int a = 0; a < 3; ++a) { s->goal_xyz[a] = xyz[a]; G.xyz_tol[a] = tol[a]; }
 }
 
 int smplx_set_goal_joint(smplx_space* s, const double* angles, const double* tolerances)
 {
     if (!s || !angles || !tolerances) return set_error(SMPLX_E_ARG, "null argument");
     if (!sane_values(angles, s->N)) return set_error(SMPLX_E_ARG, "goal angles must be finite (|q| < 1e6)");
-    SmplxGoalDev& G = s->hs.goal;
-    G.type = SMPLX_GOAL_JOINT;
-    for (int v = 0; v < s->N; ++v) { G.angles[v] = angles[v]; G.angle_tol[v] = tolerances[v]; }
-    state_to_coord(s->model.dev, angles, G.coord);
+    joint_goal_record(s, angles, tolerances);
     // goal pose = planning-link FK of the goal angles (planner_interface.cpp:1232-1235)
     int32_t h;
     if (int e = run_heuristic(s, angles, 1, &h, s->goal_xyz)) return e;
@@ -783,10 +806,84 @@ int smplx_set_goal_xyz(smplx_space* s, const double xyz[3], const double tol[3])
 {
     if (!s || !xyz || !tol) return set_error(SMPLX_E_ARG, "null argument");
     if (!sane_values(xyz, 3)) return set_error(SMPLX_E_ARG, "goal position must be finite");
-    SmplxGoalDev& G = s->hs.goal;
-    G.type = SMPLX_GOAL_XYZ;
-    for (int a = 0; a < 3; ++a) { s->goal_xyz[a] = xyz[a]; G.xyz_tol[a] = tol[a]; }
+    xyz_goal_record(s, xyz, tol);
     return finish_goal(s);
+}
+
+// what the multi-goal entry points check before they touch a space: the array, no space twice (on the handles alone)
+static int check_goal_spaces(smplx_space* const* spaces, int nq)
+{
+    if (!spaces || nq < 1) return set_error(SMPLX_E_ARG, "bad argument");
+    for (int q = 0; q < nq; ++q) if (!spaces[q]) return set_error(SMPLX_E_ARG, "null space");
+    for (int q = 0; q < nq; ++q)
+        for (int r = 0; r < q; ++r)
+            if (spaces[q] == spaces[r]) return set_error(SMPLX_E_ARG, "a space appears twice");
+    return SMPLX_OK;
+}
+
+// ... and on the spaces: one device, the same bricks per axis (the goals share the launches of run_bfs_multi)
+static int check_goal_spaces_match(smplx_space* const* spaces, int nq)
+{
+    for (int q = 1; q < nq; ++q) {
+        if (spaces[q]->device != spaces[0]->device) return set_error(SMPLX_E_ARG, "the spaces live on different devices");
+        for (int a = 0; a < 3; ++a)
+            if (spaces[q]->bfs.bricks[a] != spaces[0]->bfs.bricks[a]) return set_error(SMPLX_E_ARG, "the spaces' grids differ in bricks per axis");
+    }
+    return SMPLX_OK;
+}
+
+// finish_goal for nq spaces whose goal records and goal poses are in place: one shared BFS
+static int finish_goals_multi(smplx_space* const* spaces, int nq)
+{
+    int e = SMPLX_OK;
+    for (int q = 0; q < nq && e == SMPLX_OK; ++q) e = begin_goal(spaces[q]);
+    if (e == SMPLX_OK) e = run_bfs_multi(spaces, nq);
+    if (e != SMPLX_OK) {
+        for (int q = 0; q < nq; ++q) spaces[q]->goal_set = false;   // some grids are half written: no space keeps a goal
+        return e;
+    }
+    for (int q = 0; q < nq; ++q) end_goal(spaces[q]);
+    return SMPLX_OK;
+}
+
+int smplx_set_goals_joint_multi(smplx_space** spaces, int nq, const double* angles, const double* tolerances)
+{
+    if (int e = check_goal_spaces(spaces, nq)) return e;
+    if (!angles || !tolerances) return set_error(SMPLX_E_ARG, "null argument");
+    const int N = spaces[0]->N;
+    for (int q = 1; q < nq; ++q) if (spaces[q]->N != N) return set_error(SMPLX_E_ARG, "the spaces differ in their number of variables");
+    if (!sane_values(angles, (size_t)nq * N)) return set_error(SMPLX_E_ARG, "goal angles must be finite (|q| < 1e6)");
+    if (int e = check_goal_spaces_match(spaces, nq)) return e;
+    HIP_TRY(hipSetDevice(spaces[0]->device));
+    for (int q = 0; q < nq; ++q) joint_goal_record(spaces[q], angles + (size_t)q * N, tolerances + (size_t)q * N);
+    // goal poses = planning-link FK of the goal angles: one launch of the leading space's kernel when all run the same
+    // kernel on the same model image (the same code on the same values: bit-equal to each space's own), else one each
+    bool shared = true;
+    for (int q = 1; q < nq && shared; ++q) shared = same_scene_and_robot(spaces[0], spaces[q]) && spaces[q]->ks.specialized == spaces[0]->ks.specialized;
+    int e = SMPLX_OK;
+    if (shared) {
+        std::vector<double> xyz((size_t)nq * 3);
+        e = run_heuristic(spaces[0], angles, nq, nullptr, xyz.data());
+        for (int q = 0; q < nq && e == SMPLX_OK; ++q) for (int a = 0; a < 3; ++a) spaces[q]->goal_xyz[a] = xyz[(size_t)q * 3 + a];
+    } else {
+        for (int q = 0; q < nq && e == SMPLX_OK; ++q) e = run_heuristic(spaces[q], angles + (size_t)q * N, 1, nullptr, spaces[q]->goal_xyz);
+    }
+    if (e != SMPLX_OK) {
+        for (int q = 0; q < nq; ++q) spaces[q]->goal_set = false;
+        return e;
+    }
+    return finish_goals_multi(spaces, nq);
+}
+
+int smplx_set_goals_xyz_multi(smplx_space** spaces, int nq, const double* xyz, const double* tol)
+{
+    if (int e = check_goal_spaces(spaces, nq)) return e;
+    if (!xyz || !tol) return set_error(SMPLX_E_ARG, "null argument");
+    if (!sane_values(xyz, (size_t)nq * 3)) return set_error(SMPLX_E_ARG, "goal position must be finite");
+    if (int e = check_goal_spaces_match(spaces, nq)) return e;
+    HIP_TRY(hipSetDevice(spaces[0]->device));
+    for (int q = 0; q < nq; ++q) xyz_goal_record(spaces[q], xyz + (size_t)q * 3, tol + (size_t)q * 3);
+    return finish_goals_multi(spaces, nq);
 }
 
 int smplx_goal_pose(const smplx_space* s, double xyz[3])

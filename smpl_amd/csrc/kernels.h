@@ -85,4 +85,6 @@ __global__ void k_bfs_export(SmplxBfsDev b, int* out);
 __global__ void k_bfs_brick_seed(int* dist, int cx, int cy, int cz, int nbx, int nby, int nbz, int* list0, int* counts, int tag_word);
 __global__ void k_bfs_brick_wave(int* dist, int nbx, int nby, int nbz, const int* list_in, const int* counts_in, int* list_next,
                                  int* counts_next, int* counts_after, int shard_cap, int* queued_mine, int* queued_next, int* queue_size_out, int tag_word, int tag_mask);
+__global__ void k_bfs_brick_seed_multi(const SmplxBfsGoalDev* goals, int nq, int nbx, int nby, int nbz, int* pass_stats, int n_stats);
+__global__ void k_bfs_brick_wave_multi(const SmplxBfsGoalDev* goals, int nbx, int nby, int nbz, int pass, int history_slot, int* stats);
 }

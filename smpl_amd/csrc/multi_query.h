@@ -307,6 +307,13 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     return SMPLX_OK;
 }
 
+// two spaces that can share launches: the same scene (grid handle), model image, primitives and expansion mode
+bool same_scene_and_robot(const smplx_space* a, const smplx_space* b)
+{
+    return a->grid == b->grid && a->blob_bytes == b->blob_bytes && std::memcmp(a->hs.model_blob, b->hs.model_blob, a->blob_bytes) == 0 &&
+           std::memcmp(&a->hs.actions, &b->hs.actions, sizeof(SmplxActionsDev)) == 0 && a->step.fused_mode == b->step.fused_mode;
+}
+
 int read_counters(smplx_space* s, size_t cw, unsigned long long counters[4])
 {
     std::vector<unsigned long long> part(cw);
@@ -387,13 +394,7 @@ int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32
     // gathered into ONE cross-query frontier batch per sweep (per-state query index -> that query's goal and BFS
     // grid).  Otherwise each query issues its own batches on its own stream.
     bool grouped = nq > 1;
-    for (int q = 1; q < nq && grouped; ++q) {
-        const smplx_space* a = spaces[0];
-        const smplx_space* b = spaces[q];
-        grouped = a->grid == b->grid && a->blob_bytes == b->blob_bytes &&
-                  std::memcmp(a->hs.model_blob, b->hs.model_blob, a->blob_bytes) == 0 &&
-                  std::memcmp(&a->hs.actions, &b->hs.actions, sizeof(SmplxActionsDev)) == 0 && a->step.fused_mode == b->step.fused_mode;
-    }
+    for (int q = 1; q < nq && grouped; ++q) grouped = same_scene_and_robot(spaces[0], spaces[q]);
     const auto t0 = std::chrono::steady_clock::now();
     if (device) {
         if (grouped || nq == 1) {

@@ -89,6 +89,9 @@ struct BfsHost {
     std::vector<int32_t> queue_sizes;           // bricks queued in every pass of the last BFS: sizes the next goal's launches
     int levels = 0;
     int wall_thr = -1;
+    // of the leading space of a multi-goal run (run_bfs_multi): the goals' records and the per-pass queue totals
+    DevBuf<SmplxBfsGoalDev> b_goals;
+    DevBuf<int32_t> b_pass_stats;
 };
 
 // Speculation for callers that only know GetSuccs (an unchanged SBPL planner never calls smplx_hint_frontier): the
