@@ -231,7 +231,27 @@ int smplx_set_goal_xyz(smplx_space* s, const double xyz[3], const double tol[3])
  * different bricks per axis.  After a HIP error no space of the call has a goal: set the goals again. */
 int smplx_set_goals_joint_multi(smplx_space** spaces, int nq, const double* angles /* nq x nvars */, const double* tolerances /* nq x nvars */);
 int smplx_set_goals_xyz_multi(smplx_space** spaces, int nq, const double* xyz /* nq x 3 */, const double* tol /* nq x 3 */);
+/* XYZ_RPY_GOAL (ManipLattice::isGoal, manip_lattice.cpp:1614-1671): the XYZ goal's position box, and inside it the angle
+ * theta between the planning link's rotation and Rz(yaw) Ry(pitch) Rx(roll) of rpy must be below rpy_tol (the reference
+ * reads rpy_tolerance[0] alone).  theta lies in [0, pi]: rpy_tol > pi admits every orientation (the goal then equals
+ * the XYZ goal), rpy_tol <= 0 none.  The kernels test 1 + trace(Rg^T R) > 4 cos^2(rpy_tol / 2), the same predicate
+ * without inverse trigonometry; smplx_rpy_angle is the reference's formula for callers.  Everything else is the XYZ
+ * goal's: the BFS is seeded at xyz, snap primitives stay inactive, smplx_goal_pose returns xyz.  xyz is the pose the
+ * reference calls tgt_off_pose: a GoalConstraint::xyz_offset is the caller's to apply.
+ * SMPLX_E_ARG: a null pointer, a non-finite pose value (|xyz| >= 1e6, |rpy| >= 1e6), a NaN tolerance. */
+int smplx_set_goal_pose(smplx_space* s, const double xyz[3], const double rpy[3], const double xyz_tol[3], double rpy_tol);
+/* smplx_set_goal_pose for nq spaces in one call: contract and checks of smplx_set_goals_xyz_multi */
+int smplx_set_goals_pose_multi(smplx_space** spaces, int nq, const double* xyz /* nq x 3 */, const double* rpy /* nq x 3 */,
+                               const double* xyz_tol /* nq x 3 */, const double* rpy_tol /* nq */);
 int smplx_goal_pose(const smplx_space* s, double xyz[3]);
+/* roll, pitch, yaw and tolerance of a pose goal as they were given; SMPLX_E_STATE unless the goal is one */
+int smplx_goal_orientation(const smplx_space* s, double rpy[3], double* rpy_tol);
+/* the reference's orientation distance between two roll/pitch/yaw triples (manip_lattice.cpp:1652-1665: ZYX quaternions,
+ * sign flip, 2 acos of the dot product), in [0, pi]; host arithmetic, needs no space */
+int smplx_rpy_angle(const double a[3], const double b[3], double* theta);
+/* computePlanningLinkFK for n states: the planning link's transform, row-major 3x4 each, by the FK the goal test and
+ * the heuristic run (column 3 is bit-equal to smplx_heuristic_batch's xyz) */
+int smplx_planning_pose_batch(smplx_space* s, const double* q, int n, double* T /* n x 12 */);
 /* GetGoalHeuristic for arbitrary states (bfs_heuristic.cpp:148-163); xyz (n*3) may be NULL */
 int smplx_heuristic_batch(smplx_space* s, const double* q, int n, int32_t* h, double* xyz);
 /* BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) for n workspace points xyz[n*3]:

@@ -337,13 +337,18 @@ class GpuManipLattice : public RobotPlanningSpace {
 public:
     using Extension::getExtension;   // keep the typed lookup visible next to the override
     explicit GpuManipLattice(GpuPlanningContext* ctx) : ctx_(ctx) {}
-    // GoalConstraint with JOINT_STATE_GOAL / XYZ_GOAL (manip_lattice.cpp:1982-1997); observers (the BFS
+    // GoalConstraint with JOINT_STATE_GOAL / XYZ_GOAL / XYZ_RPY_GOAL (manip_lattice.cpp:1982-1997); observers (the BFS
     // heuristic) are notified inside the engine: BFS_3D::run completes before this returns
     bool setGoalConfiguration(const RobotState& angles, const RobotState& tolerances)
     {
         return smplx_set_goal_joint(ctx_->space(), angles.data(), tolerances.data()) == SMPLX_OK;
     }
     bool setGoalPosition(const double xyz[3], const double tol[3]) { return smplx_set_goal_xyz(ctx_->space(), xyz, tol) == SMPLX_OK; }
+    // XYZ_RPY_GOAL: isGoal (manip_lattice.cpp:1614-1671) reads rpy_tolerance[0] alone; smplx_rpy_angle is its distance
+    bool setGoalPose(const double xyz[3], const double rpy[3], const double xyz_tol[3], double rpy_tol)
+    {
+        return smplx_set_goal_pose(ctx_->space(), xyz, rpy, xyz_tol, rpy_tol) == SMPLX_OK;
+    }
     // ManipLattice::setGoal (manip_lattice.cpp:1982-1997): dispatch on the goal type, then notify the observers
     // (the heuristic; its BFS has already been run to completion inside the engine)
     bool setGoal(const GoalConstraint& goal) override
@@ -360,11 +365,24 @@ public:
             if ((int)goal.angles.size() != ctx_->nvars() || goal.angle_tolerances.size() != goal.angles.size()) return false;
             ok = setGoalConfiguration(goal.angles, goal.angle_tolerances);
             break;
+        case XYZ_RPY_GOAL: {
+            // the pose is the reference's tgt_off_pose; getTargetOffsetPose (manip_lattice.cpp:2297-2312) is not applied
+            // here, so a goal that asks for an offset is refused rather than planned to the wrong pose
+            if (goal.xyz_offset[0] != 0.0 || goal.xyz_offset[1] != 0.0 || goal.xyz_offset[2] != 0.0) return false;
+            const std::vector<double>& p = goal.tgt_off_pose.size() >= 6 ? goal.tgt_off_pose : goal.pose;
+            if (p.size() < 6) return false;
+            ok = setGoalPose(&p[0], &p[3], goal.xyz_tolerance, goal.rpy_tolerance[0]);
+        } break;
         default:
-            return false;   // XYZ_RPY_GOAL needs IK (out of this path's scope)
+            return false;
         }
         if (ok) notifyGoalChanged(goal);
         return ok;
+    }
+    // the planning link's transform at a state, row-major 3x4 (what computePlanningLinkFK gives the reference's callers)
+    bool planningLinkTransform(const RobotState& state, double T[12])
+    {
+        return (int)state.size() == ctx_->nvars() && smplx_planning_pose_batch(ctx_->space(), state.data(), 1, T) == SMPLX_OK;
     }
     bool setStart(const RobotState& state) override
     {

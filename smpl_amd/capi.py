@@ -38,6 +38,7 @@ SYMBOLS = [
     "smplx_search_counters", "smplx_grid_set_ref_counted", "smplx_grid_update_points", "smplx_grid_copy_counts", "smplx_grid_last_edit_cells",
     "smplx_replan", "smplx_replan_multi", "smplx_set_goals_joint_multi", "smplx_set_goals_xyz_multi",
     "smplx_attach_body", "smplx_detach_body", "smplx_attached_bodies", "smplx_attached_nodes", "smplx_cc_attached_positions",
+    "smplx_set_goal_pose", "smplx_set_goals_pose_multi", "smplx_goal_orientation", "smplx_planning_pose_batch", "smplx_rpy_angle",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -115,6 +116,11 @@ def lib():
         L.smplx_bfs_metric_start_distance.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
         L.smplx_space_clear_status.argtypes = [C.c_void_p]
         L.smplx_space_clear_status.restype = None
+        L.smplx_set_goal_pose.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_double]
+        L.smplx_set_goals_pose_multi.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+        L.smplx_goal_orientation.argtypes = [C.c_void_p, _dp, _dp]
+        L.smplx_planning_pose_batch.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
+        L.smplx_rpy_angle.argtypes = [_dp, _dp, _dp]
         _lib = L
     return _lib
 
@@ -136,6 +142,14 @@ def _p(a, t):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def rpy_angle(a, b):
+    """The pose goal's orientation distance between two roll/pitch/yaw triples, in [0, pi] (smplx_rpy_angle): what
+    set_goal_pose compares with rpy_tol.  Host arithmetic, needs no GPU."""
+    x = _f64(a); y = _f64(b); t = C.c_double(0.0)
+    _chk(lib().smplx_rpy_angle(_p(x, _dp), _p(y, _dp), C.byref(t)))
+    return t.value
 
 
 class Grid:
@@ -426,10 +440,38 @@ class Space:
         lib().smplx_set_goals_xyz_multi.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         _chk(lib().smplx_set_goals_xyz_multi(H, nq, _p(a, _dp), _p(t, _dp)))
 
+    def set_goal_pose(self, xyz, rpy, xyz_tol, rpy_tol):
+        """XYZ_RPY goal: the XYZ goal's position box and, inside it, rpy_angle(link, rpy) < rpy_tol (smplx_set_goal_pose)."""
+        a = _f64(xyz); r = _f64(rpy); t = _f64(xyz_tol)
+        _chk(lib().smplx_set_goal_pose(self.h, _p(a, _dp), _p(r, _dp), _p(t, _dp), float(rpy_tol)))
+
+    @staticmethod
+    def set_goals_pose_multi(spaces, xyz, rpy, xyz_tols, rpy_tols):
+        """set_goal_pose for spaces[q] with row q of the arrays in one call (smplx_set_goals_pose_multi)."""
+        nq = len(spaces)
+        a = _f64(xyz).reshape(nq, 3); r = _f64(rpy).reshape(nq, 3); t = _f64(xyz_tols).reshape(nq, 3); rt = _f64(rpy_tols).reshape(nq)
+        H = (C.c_void_p * max(nq, 1))(*[sp.h for sp in spaces])
+        _chk(lib().smplx_set_goals_pose_multi(H, nq, _p(a, _dp), _p(r, _dp), _p(t, _dp), _p(rt, _dp)))
+
     def goal_pose(self):
         x = np.zeros(3)
         _chk(lib().smplx_goal_pose(self.h, _p(x, _dp)))
         return x
+
+    rpy_angle = staticmethod(rpy_angle)
+
+    def goal_orientation(self):
+        """(rpy, rpy_tol) of a pose goal; raises (SMPLX_E_STATE) for any other goal"""
+        r = np.zeros(3); t = C.c_double(0.0)
+        _chk(lib().smplx_goal_orientation(self.h, _p(r, _dp), C.byref(t)))
+        return r, t.value
+
+    def planning_pose_batch(self, q):
+        """planning-link transforms of n states, [n][3][4] (computePlanningLinkFK)"""
+        q = _f64(q).reshape(-1, self.N); n = q.shape[0]
+        T = np.zeros((n, 3, 4))
+        _chk(lib().smplx_planning_pose_batch(self.h, _p(q, _dp), n, _p(T, _dp)))
+        return T
 
     def heuristic_batch(self, q):
         q = _f64(q).reshape(-1, self.N); n = q.shape[0]

@@ -183,6 +183,11 @@ struct SmplxGoalDev {
     int32_t coord[SMPLX_MAX_VARS];
     double xyz[3];
     double xyz_tol[3];
+    // SMPLX_GOAL_XYZ_RPY (manip_lattice.cpp:1614-1671), worked out by the host once per goal: the goal rotation
+    // Rz(yaw) Ry(pitch) Rx(roll), row-major, and the bound of the orientation test 1 + sum(rot .* R) > rpy_c4
+    // (rpy_c4 = 4 cos^2(tol / 2); -1: every orientation passes, +inf: none)
+    double rot[9];
+    double rpy_c4;
 };
 
 static_assert(sizeof(SmplxModelDev) % 16 == 0 && sizeof(SmplxJoint) % 16 == 0 && sizeof(SmplxNode) % 16 == 0,

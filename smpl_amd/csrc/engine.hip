@@ -791,6 +791,50 @@ static void xyz_goal_record(smplx_space* s, const double xyz[3], const double to
     for (int a = 0; a < 3; ++a) { s->goal_xyz[a] = xyz[a]; G.xyz_tol[a] = tol[a]; }
 }
 
+// the bound of the device's orientation test (device_types.h SmplxGoalDev::rpy_c4): theta < tol, theta in [0, pi], is
+// 4 cos^2(theta / 2) > 4 cos^2(tol / 2) for 0 < tol <= pi; a wider tolerance admits every orientation, tol <= 0 none
+static double rpy_bound(double tol)
+{
+    if (!(tol > 0.0)) return std::numeric_limits<double>::infinity();
+    if (tol > SMPLX_PI) return -1.0;
+    const double c = std::cos(0.5 * tol);
+    return 4.0 * c * c;
+}
+
+// Rz(yaw) Ry(pitch) Rx(roll), row-major 3x3: origin_matrix (model_compile.cpp) without the translation
+static void rpy_matrix(const double rpy[3], double r[9])
+{
+    double sr, cr, sp, cp, sy, cy;
+    smplx_sincos(rpy[0], &sr, &cr);
+    smplx_sincos(rpy[1], &sp, &cp);
+    smplx_sincos(rpy[2], &sy, &cy);
+    r[0] = cy * cp; r[1] = (cy * sp) * sr - sy * cr; r[2] = (cy * sp) * cr + sy * sr;
+    r[3] = sy * cp; r[4] = (sy * sp) * sr + cy * cr; r[5] = (sy * sp) * cr - cy * sr;
+    r[6] = -sp;     r[7] = cp * sr;                  r[8] = cp * cr;
+}
+
+// XYZ_RPY_GOAL (manip_lattice.cpp:1614-1671): the XYZ goal's record plus the goal rotation and the bound of its test
+static void pose_goal_record(smplx_space* s, const double xyz[3], const double rpy[3], const double xyz_tol[3], double rpy_tol)
+{
+    xyz_goal_record(s, xyz, xyz_tol);
+    SmplxGoalDev& G = s->hs.goal;
+    G.type = SMPLX_GOAL_XYZ_RPY;
+    rpy_matrix(rpy, G.rot);
+    G.rpy_c4 = rpy_bound(rpy_tol);
+    for (int a = 0; a < 3; ++a) s->goal_rpy[a] = rpy[a];
+    s->goal_rpy_tol = rpy_tol;
+}
+
+// what the pose-goal entry points refuse in n goals: a non-finite pose, |xyz| >= 1e6 or |rpy| >= 1e6 (smplx_sincos reduces
+// its argument through an int: the bound of the joint values), a NaN tolerance
+static bool sane_pose_goals(const double* xyz, const double* rpy, const double* xyz_tol, const double* rpy_tol, size_t n)
+{
+    if (!sane_values(xyz, 3 * n) || !sane_values(rpy, 3 * n)) return false;
+    for (size_t i = 0; i < 3 * n; ++i) if (std::isnan(xyz_tol[i])) return false;
+    for (size_t i = 0; i < n; ++i) if (std::isnan(rpy_tol[i])) return false;
+    return true;
+}
+
 int smplx_set_goal_joint(smplx_space* s, const double* angles, const double* tolerances)
 {
     if (!s || !angles || !tolerances) return set_error(SMPLX_E_ARG, "null argument");
@@ -807,6 +851,15 @@ int smplx_set_goal_xyz(smplx_space* s, const double xyz[3], const double tol[3])
     if (!s || !xyz || !tol) return set_error(SMPLX_E_ARG, "null argument");
     if (!sane_values(xyz, 3)) return set_error(SMPLX_E_ARG, "goal position must be finite");
     xyz_goal_record(s, xyz, tol);
+    return finish_goal(s);
+}
+
+int smplx_set_goal_pose(smplx_space* s, const double xyz[3], const double rpy[3], const double xyz_tol[3], double rpy_tol)
+{
+    if (!xyz || !rpy || !xyz_tol) return set_error(SMPLX_E_ARG, "null argument");
+    if (!sane_pose_goals(xyz, rpy, xyz_tol, &rpy_tol, 1)) return set_error(SMPLX_E_ARG, "goal pose must be finite (|xyz|, |rpy| < 1e6), tolerances not NaN");
+    if (!s) return set_error(SMPLX_E_ARG, "null space");
+    pose_goal_record(s, xyz, rpy, xyz_tol, rpy_tol);
     return finish_goal(s);
 }
 
@@ -884,6 +937,67 @@ int smplx_set_goals_xyz_multi(smplx_space** spaces, int nq, const double* xyz, c
     HIP_TRY(hipSetDevice(spaces[0]->device));
     for (int q = 0; q < nq; ++q) xyz_goal_record(spaces[q], xyz + (size_t)q * 3, tol + (size_t)q * 3);
     return finish_goals_multi(spaces, nq);
+}
+
+int smplx_set_goals_pose_multi(smplx_space** spaces, int nq, const double* xyz, const double* rpy, const double* xyz_tol, const double* rpy_tol)
+{
+    if (int e = check_goal_spaces(spaces, nq)) return e;
+    if (!xyz || !rpy || !xyz_tol || !rpy_tol) return set_error(SMPLX_E_ARG, "null argument");
+    if (!sane_pose_goals(xyz, rpy, xyz_tol, rpy_tol, (size_t)nq)) return set_error(SMPLX_E_ARG, "goal poses must be finite (|xyz|, |rpy| < 1e6), tolerances not NaN");
+    if (int e = check_goal_spaces_match(spaces, nq)) return e;
+    HIP_TRY(hipSetDevice(spaces[0]->device));
+    for (int q = 0; q < nq; ++q) pose_goal_record(spaces[q], xyz + (size_t)q * 3, rpy + (size_t)q * 3, xyz_tol + (size_t)q * 3, rpy_tol[q]);
+    return finish_goals_multi(spaces, nq);
+}
+
+int smplx_goal_orientation(const smplx_space* s, double rpy[3], double* rpy_tol)
+{
+    if (!s || !rpy || !rpy_tol) return set_error(SMPLX_E_ARG, "null argument");
+    if (!s->goal_set || s->hs.goal.type != SMPLX_GOAL_XYZ_RPY) return set_error(SMPLX_E_STATE, "the goal is not a pose goal");
+    for (int a = 0; a < 3; ++a) rpy[a] = s->goal_rpy[a];
+    *rpy_tol = s->goal_rpy_tol;
+    return SMPLX_OK;
+}
+
+// The reference's orientation distance (manip_lattice.cpp:1652-1665) literally: the ZYX-Euler quaternions of the two
+// orientations, the sign flip, 2 acos of their dot product.  Rounding can put the dot product of two unit quaternions a
+// few ulp above 1, where acos has no value: it counts as 1.
+int smplx_rpy_angle(const double a[3], const double b[3], double* theta)
+{
+    if (!a || !b || !theta) return set_error(SMPLX_E_ARG, "null argument");
+    for (int i = 0; i < 3; ++i) if (!std::isfinite(a[i]) || !std::isfinite(b[i])) return set_error(SMPLX_E_ARG, "angles must be finite");
+    auto quat = [](const double rpy[3], double q[4]) {
+        const double sr = std::sin(0.5 * rpy[0]), cr = std::cos(0.5 * rpy[0]), sp = std::sin(0.5 * rpy[1]), cp = std::cos(0.5 * rpy[1]);
+        const double sy = std::sin(0.5 * rpy[2]), cy = std::cos(0.5 * rpy[2]);
+        q[0] = cr * cp * cy + sr * sp * sy;   // w of AngleAxis(yaw, Z) * AngleAxis(pitch, Y) * AngleAxis(roll, X)
+        q[1] = sr * cp * cy - cr * sp * sy;
+        q[2] = cr * sp * cy + sr * cp * sy;
+        q[3] = cr * cp * sy - sr * sp * cy;
+    };
+    double qa[4], qb[4];
+    quat(a, qa);
+    quat(b, qb);
+    double d = qa[0] * qb[0] + qa[1] * qb[1] + qa[2] * qb[2] + qa[3] * qb[3];
+    if (d < 0.0) d = -d;                      // qg negated (:1660-1662)
+    if (d > 1.0) d = 1.0;
+    *theta = smplx_normalize_angle(2.0 * std::acos(d));
+    return SMPLX_OK;
+}
+
+int smplx_planning_pose_batch(smplx_space* s, const double* q, int n, double* T)
+{
+    if (!s || !q || !T || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (!sane_values(q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    if (int e = s->batch.b_q.reserve((size_t)n * s->N)) return e;
+    if (int e = s->b_sq.reserve((size_t)n * 12)) return e;
+    HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    KLAUNCH(s, K_PLANNING_POSE, k_planning_pose, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space,
+            s->batch.b_q.p, n, s->b_sq.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(T, s->b_sq.p, sizeof(double) * n * 12, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SMPLX_OK;
 }
 
 int smplx_goal_pose(const smplx_space* s, double xyz[3])

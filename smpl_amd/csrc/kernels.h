@@ -75,6 +75,7 @@ __global__ void k_edge_valid(const SmplxSpaceDev* S, const double* Aq, const dou
                              int* out_lookups, int* out_waypoints);
 __global__ void k_state_valid(const SmplxSpaceDev* S, const double* Q, int n, unsigned char* out, int* out_lookups);
 __global__ void k_heuristic(const SmplxSpaceDev* S, const double* Q, int n, int* out_h, double* out_xyz);
+__global__ void k_planning_pose(const SmplxSpaceDev* S, const double* Q, int n, double* out_T);
 __global__ void k_sphere_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
 __global__ void k_attached_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
 __global__ void k_table_insert(const SmplxSpaceDev* S, const SmplxSpaceDev* const* stab, const int* items, int n, int nvars);

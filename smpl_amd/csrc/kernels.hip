@@ -9,6 +9,7 @@
 //   k_edge_valid      CollisionChecker::isStateToStateValid for a batch of edges
 //   k_state_valid     CollisionChecker::isStateValid for a batch of states
 //   k_heuristic       BfsHeuristic::GetGoalHeuristic for a batch of states
+//   k_planning_pose   computePlanningLinkFK for a batch of states
 //   k_bfs_*           level-synchronous 26-connected BFS (bfs3d.cpp:507-547)
 //
 // No MFMA: the path is integer/byte gathers from the voxel grid plus a short serial FK chain in fp64.
@@ -1090,18 +1091,18 @@ __device__ __forceinline__ bool edge_valid(const ModelLds* __restrict__ M, const
     return true;
 }
 
-// planning-link position ("KDL" FK restated as the same serial chain; kdl_robot_model.cpp:400-423,
-// continuous joints normalised first :191-198)
-__device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, const double* __restrict__ q, double p[3])
+// planning-link position and rotation (row-major 3x3) ("KDL" FK restated as the same serial chain;
+// kdl_robot_model.cpp:400-423, continuous joints normalised first :191-198): what a pose goal tests and
+// smplx_planning_pose_batch reports.  The chain and its T stay in this one function, the rotation an optional output:
+// with T handed in by a caller, k_pipe_setup, k_pipe_prep and k_heuristic of the generic build lose an occupancy step
+__device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, const double* __restrict__ q, double p[3], double* R)
 {
     double T[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) T[i] = 0.0;
 #ifdef SMPLX_CONST_MODEL
     const_planning_chain<0, true>(M, q, T);
-    p[0] = T[3]; p[1] = T[7]; p[2] = T[11];
-    return;
-#endif
+#else
     bool first = true;
     const int nj = M->njoints;
     for (int j = 0; j < nj; ++j) {
@@ -1115,7 +1116,18 @@ __device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, cons
         apply_joint(jt, qv, T, first);
         first = false;
     }
+#endif
     p[0] = T[3]; p[1] = T[7]; p[2] = T[11];
+    if (R) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { R[3 * i] = T[4 * i]; R[3 * i + 1] = T[4 * i + 1]; R[3 * i + 2] = T[4 * i + 2]; }
+    }
+}
+
+// ... its position alone: the same chain (the last joint's rotation is dead code)
+__device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, const double* __restrict__ q, double p[3])
+{
+    planning_fk(M, q, p, nullptr);
 }
 
 __device__ __forceinline__ void world_to_cell(const SmplxGridDev& g, const double p[3], int c[3])
@@ -1494,16 +1506,24 @@ __device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, 
                                                 bool& is_goal)
 {
     const int nv = MV_NVARS(M);
-    double p[3];
-    planning_fk(M, sq, p);
+    double p[3], R[9];
+    planning_fk(M, sq, p, R);
     if (G.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
         is_goal = true;
         MV_UNROLL
         for (int v = 0; v < nv; ++v)
             if (fabs((double)(sc[v] - G.coord[v])) > G.angle_tol[v]) is_goal = false;
-    } else {                               // XYZ goal :1672-1687
+    } else {                               // the position box of both pose goals :1632-1637, :1682-1684
         is_goal = fabs(p[0] - G.xyz[0]) <= G.xyz_tol[0] && fabs(p[1] - G.xyz[1]) <= G.xyz_tol[1] &&
                   fabs(p[2] - G.xyz[2]) <= G.xyz_tol[2];
+        // XYZ_RPY :1652-1667: the angle theta between the link's rotation and the goal's is below the tolerance iff
+        // 4 cos^2(theta / 2) = 1 + trace(Rg^T R) is above the goal's rpy_c4 (device_types.h SmplxGoalDev)
+        if (G.type == SMPLX_GOAL_XYZ_RPY && is_goal) {
+            double t = 1.0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) t += G.rot[i] * R[i];
+            is_goal = t > G.rpy_c4;
+        }
     }
     int c[3];
     world_to_cell(grid, p, c);
@@ -2447,6 +2467,22 @@ k_heuristic(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, i
     world_to_cell(S->grid, p, c);
     out_h[i] = bfs_cost_to_goal(S->bfs, c);
     if (out_xyz) { out_xyz[3 * i] = p[0]; out_xyz[3 * i + 1] = p[1]; out_xyz[3 * i + 2] = p[2]; }
+}
+
+// planning-link transforms (computePlanningLinkFK) of a batch of states, row-major 3x4 each
+extern "C" __global__ void __launch_bounds__(BLOCK)
+k_planning_pose(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int n, double* __restrict__ out_T)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const ModelLds Mv = setup_model_only(S, smem);
+    const ModelLds* M = &Mv;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    double p[3], R[9];
+    planning_fk(M, Q + (size_t)i * MV_NVARS(M), p, R);
+    double* T = out_T + (size_t)i * 12;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { T[4 * r] = R[3 * r]; T[4 * r + 1] = R[3 * r + 1]; T[4 * r + 2] = R[3 * r + 2]; T[4 * r + 3] = p[r]; }
 }
 
 // BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) for a batch of workspace points

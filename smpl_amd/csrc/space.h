@@ -198,6 +198,8 @@ struct smplx_space {
     bool goal_set = false;
     uint64_t grid_epoch = 0;         // the grid's edit count when the goal was set: the successor caches belong to that field
     double goal_xyz[3] = {0, 0, 0};
+    double goal_rpy[3] = {0, 0, 0};   // of a pose goal (SMPLX_GOAL_XYZ_RPY), as the caller gave them
+    double goal_rpy_tol = 0;
     double start_xyz[3] = {0, 0, 0};   // planning-link position of the start state (getMetricStartDistance)
     int status = SMPLX_OK;            // sticky: first error of a call that has no way to report one (smplx_space_status)
     std::string status_msg;

@@ -29,7 +29,7 @@ namespace {
 
 const char* const kNames[K_COUNT] = {"k_state_prep", "k_expand", "k_pipe_prep", "k_pipe_setup", "k_pipe_configs",
                                      "k_pipe_finish", "k_small_batch", "k_edge_valid", "k_state_valid", "k_heuristic",
-                                     "k_sphere_positions", "k_search", "k_attached_positions"};
+                                     "k_sphere_positions", "k_search", "k_attached_positions", "k_planning_pose"};
 
 uint64_t fnv1a(uint64_t h, const std::string& s)
 {
@@ -142,7 +142,7 @@ void generic_kernels(KernelSet& ks)
                               (const void*)k_pipe_setup, (const void*)k_pipe_configs, (const void*)k_pipe_finish,
                               (const void*)k_small_batch, (const void*)k_edge_valid, (const void*)k_state_valid,
                               (const void*)k_heuristic, (const void*)k_sphere_positions, (const void*)k_search,
-                              (const void*)k_attached_positions};
+                              (const void*)k_attached_positions, (const void*)k_planning_pose};
     for (int i = 0; i < K_COUNT; ++i) { ks.k[i].fn = nullptr; ks.k[i].generic = g[i]; }
     ks.specialized = false;
 }
