@@ -1,4 +1,4 @@
-// smpl_amd/csrc/bfs_host.h -- host driver of the BFS heuristic's distance field (BfsHost in space.h; kernels.hip
+// smpl_amd/csrc/bfs_host.h -- host driver of the BFS heuristic's distance field (BfsHost in space.h; bfs_kernels.h
 // k_bfs_brick_seed / k_bfs_brick_wave): from the goal cell, passes over the queued 8x8x8 bricks until none is queued,
 // with launch sizes taken from the queue sizes of the previous goal's run.  run_bfs does it for one space, run_bfs_multi
 // for the goals of several spaces in one shared sequence of launches (k_bfs_brick_seed_multi / k_bfs_brick_wave_multi).
@@ -28,7 +28,7 @@ bool bfs_goal_cell(const smplx_space* s, const double xyz[3], int c[3])
 }
 
 // BFS_3D::run to completion on the device (bfs3d.cpp:156-201, 507-547): passes over the queued 8x8x8 bricks until none is
-// queued (kernels.hip k_bfs_brick_wave)
+// queued (bfs_kernels.h k_bfs_brick_wave)
 int run_bfs(smplx_space* s, const double xyz[3])
 {
     int c[3];

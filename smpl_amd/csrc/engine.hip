@@ -83,7 +83,7 @@ int run_heuristic(smplx_space* s, const double* q, int n, int32_t* h, double* xy
     return SMPLX_OK;
 }
 
-// host mirror of the applyMotionPrimitive branch (manip_lattice_action_space.cpp:575-621) of successor_values in kernels.hip,
+// host mirror of the applyMotionPrimitive branch (manip_lattice_action_space.cpp:575-621) of successor_values in lattice_steps.h,
 // the one device definition: change the two together.  Same expressions, same order, -ffp-contract=off like the kernels.
 void host_apply_prim(const SmplxActionsDev& A, const double* parent, int pi, int nv, double* out)
 {

@@ -1,4 +1,4 @@
-// smpl_amd/csrc/kernels.h -- launch geometry and prototypes of the gfx950 kernels (kernels.hip)
+// smpl_amd/csrc/kernels.h -- launch geometry and prototypes of the gfx950 kernels (kernels.hip and the headers it includes)
 #pragma once
 
 #ifndef __HIPCC_RTC__   // hiprtc (per-robot specialisation, specialize.cpp) brings its own runtime declarations
@@ -11,6 +11,7 @@
 #define SMPLX_BLOCK 128          // 2 waves; per-thread LDS scratch keeps ~4 blocks per CU resident
 #define SMPLX_SETUP_BLOCK (SMPLX_BLOCK + 64)   // threads of a k_pipe_setup block: the edge threads and the goal-distance wave
 #define SMPLX_SEARCH_STATIC_LDS (44 * 1024)   // static LDS of k_search (2 x ExpandLds + SearchLds + header and primitives copies), an upper bound
+#define SMPLX_GLOBAL_AS __attribute__((address_space(1)))   // device code: a pointer known to be device memory (model_lds.h as_global)
 #define SMPLX_TALLIES 6           // per-block tallies (tally_block)     // per-thread DFS stack (node indices, one byte each)
 
 // dynamic LDS bytes: the packed model, plus (collision kernels) per-thread scratch
@@ -27,6 +28,14 @@ static inline size_t smplx_lds_bytes(size_t blob_bytes, int nroot, int nslots, i
 {
     return smplx_lds_bytes_n(blob_bytes, nroot, nslots, nvars, stack_bytes, SMPLX_BLOCK);
 }
+
+// The kernels that have a per-robot build, stated once as X(id, kernel): enum KernelId (K_<id>, specialize.h), the names
+// asked of the per-robot code object and the generic kernels beside them (specialize.cpp) all come from this list.
+#define SMPLX_PER_ROBOT_KERNELS(X) \
+    X(STATE_PREP, k_state_prep) X(EXPAND, k_expand) X(PIPE_PREP, k_pipe_prep) X(PIPE_SETUP, k_pipe_setup) \
+    X(PIPE_CONFIGS, k_pipe_configs) X(PIPE_FINISH, k_pipe_finish) X(SMALL_BATCH, k_small_batch) X(EDGE_VALID, k_edge_valid) \
+    X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
+    X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,

@@ -1,0 +1,277 @@
+// smpl_amd/csrc/lattice_steps.h -- the steps of ManipLattice::GetSuccs that are not collision checks, one definition
+// each for every expansion kernel.
+// Owns: planning_fk, world_to_cell, metric_goal_distance, bfs_cost_to_goal, check_joint_limits, var_to_coord;
+// the device copy of the state table (table_lookup, the insert functions and k_table_insert); mprim_active,
+// prim_has_action, successor_values, successor_goal_h.
+// Restates: kdl_robot_model.cpp:173-235, 400-423; bfs_heuristic.cpp:129-138, 355-366;
+// manip_lattice.cpp:1263-1354, 1596-1684; manip_lattice_action_space.cpp:551-621, 662-691.
+#pragma once
+
+#include "bfs_record.h"
+#include "model_lds.h"
+#include "sphere_checks.h"   // const_planning_chain
+
+// planning-link position and rotation (row-major 3x3) ("KDL" FK restated as the same serial chain;
+// kdl_robot_model.cpp:400-423, continuous joints normalised first :191-198): what a pose goal tests and
+// smplx_planning_pose_batch reports.  The chain and its T stay in this one function, the rotation an optional output:
+// with T handed in by a caller, k_pipe_setup, k_pipe_prep and k_heuristic of the generic build lose an occupancy step
+__device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, const double* __restrict__ q, double p[3], double* R)
+{
+    double T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = 0.0;
+#ifdef SMPLX_CONST_MODEL
+    const_planning_chain<0, true>(M, q, T);
+#else
+    bool first = true;
+    const int nj = M->njoints;
+    for (int j = 0; j < nj; ++j) {
+        JointPtr jt = &M->joints[j];
+        if (!jt->on_chain) continue;
+        double qv = 0.0;
+        if (jt->var >= 0) {
+            qv = q[jt->var];
+            if (MV_TYPE(M, jt->var) == SMPLX_JT_CONTINUOUS) qv = smplx_normalize_angle(qv);
+        }
+        apply_joint(jt, qv, T, first);
+        first = false;
+    }
+#endif
+    p[0] = T[3]; p[1] = T[7]; p[2] = T[11];
+    if (R) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { R[3 * i] = T[4 * i]; R[3 * i + 1] = T[4 * i + 1]; R[3 * i + 2] = T[4 * i + 2]; }
+    }
+}
+
+// ... its position alone: the same chain (the last joint's rotation is dead code)
+__device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, const double* __restrict__ q, double p[3])
+{
+    planning_fk(M, q, p, nullptr);
+}
+
+__device__ __forceinline__ void world_to_cell(const SmplxGridDev& g, const double p[3], int c[3])
+{
+    c[0] = (int)(g.inv_res * (p[0] - g.origin_minus_res[0]) + 0.5) - 1;
+    c[1] = (int)(g.inv_res * (p[1] - g.origin_minus_res[1]) + 0.5) - 1;
+    c[2] = (int)(g.inv_res * (p[2] - g.origin_minus_res[2]) + 0.5) - 1;
+}
+
+// BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) of the state with joint values q: the gate of its
+// primitives.  The one definition for every path; goal_distance_of_h (search_kernel.h) recovers the same value from a
+// state's heuristic and must keep the same distance for an unreachable cell.
+__device__ __forceinline__ double metric_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
+                                                       const double* __restrict__ q)
+{
+    double p[3];
+    planning_fk(M, q, p);
+    int c[3];
+    world_to_cell(grid, p, c);
+    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
+}
+
+// BfsHeuristic::getBfsCostToGoal (bfs_heuristic.cpp:355-366)
+__device__ __forceinline__ int bfs_cost_to_goal(const SmplxBfsDev& b, const int c[3])
+{
+    if (!bfs_in_bounds(b, c)) return 32767;
+    const int d = bfs_dist(b, c);
+    if (d == 0x7FFFFFFF) return 32767;
+    return b.cost_per_cell * d;
+}
+
+// KDLRobotModel::checkJointLimits (kdl_robot_model.cpp:173-189, 210-235)
+__device__ __forceinline__ bool check_joint_limits(const ModelLds* __restrict__ M, const double* __restrict__ q)
+{
+    const int nv = MV_NVARS(M);
+    MV_UNROLL
+    for (int v = 0; v < nv; ++v) {
+        const double a_min = MV_MIN(M, v), a_max = MV_MIN_NORM(M, v);
+        double a = q[v];
+        if (fabs(a) > SMPLX_2PI) a = fmod(a, SMPLX_2PI);
+        while (a > a_max) a -= SMPLX_2PI;
+        while (a < a_min) a += SMPLX_2PI;
+        if (a < MV_MIN(M, v) || a > MV_MAX(M, v)) return false;
+    }
+    return true;
+}
+
+// ManipLattice::stateToCoord for one variable (manip_lattice.cpp:1263-1289)
+__device__ __forceinline__ int var_to_coord(const ModelLds* __restrict__ M, int v, double x)
+{
+    const double delta = MV_COORD_DELTA(M, v);
+    const int ty = MV_TYPE(M, v);
+    if (ty == SMPLX_JT_CONTINUOUS) {
+        const double pos = smplx_normalize_angle_positive(x);
+        int c = (int)((pos + delta * 0.5) / delta);
+        if (c == MV_COORD_VALS(M, v)) c = 0;
+        return c;
+    }
+    // bounded variables (every non-continuous variable of the plain-text model has limits)
+    return (int)(((x - MV_MIN(M, v)) / delta) + 0.5);
+}
+
+// ManipLattice::getHashEntry (manip_lattice.cpp:1302-1316) against the device copy of the state table: state id of a
+// discretised coordinate, -1 if the host has not committed it (yet)
+// Inserts of the same launch may still be running (they ride at the head of the batch's first kernel): a slot whose tag
+// is negative is being filled.  No slot between a coordinate's home and its own slot can have been empty since it was
+// inserted, so meeting an empty or a busy slot first means the coordinate was not in the table before this launch.
+// ConcurrentInserts: inserts may run in other workgroups of the SAME launch (k_small_batch: the extra blocks of
+// table_insert_block).  In the pipeline the inserts ride with the first kernel and the lookups run in the last one, a
+// kernel boundary later, where plain loads do (acquires there cost k_pipe_finish 15 -> 33 us, measured).
+template <bool ConcurrentInserts>
+__device__ __forceinline__ int table_lookup(const SmplxTableDev& T, const int* __restrict__ c, int nv)
+{
+    if (!T.slots) return -1;
+    unsigned int i = smplx_coord_hash(c, nv) & T.mask;
+    while (true) {
+        const SMPLX_GLOBAL_AS int* sl = as_global(T.slots) + (size_t)i * T.stride;
+        // ConcurrentInserts (k_small_batch): table_insert_item publishes the tag with a release after the coordinates, from
+        // another workgroup; the tag is read with an acquire and the coordinates with loads that bypass this CU's L1, which is
+        // never refreshed by another CU's stores -- a plain load could compare against a stale line (zeros, or half a
+        // coordinate) and return another state's id
+        const int tag = ConcurrentInserts ? __atomic_load_n(&sl[0], __ATOMIC_ACQUIRE) : __atomic_load_n(&sl[0], __ATOMIC_RELAXED);
+        if (tag <= 0) return -1;          // free, or being filled: a miss (the host resolves misses)
+        bool same = true;
+        for (int v = 0; v < nv; ++v) same = same && (ConcurrentInserts ? __atomic_load_n(&sl[1 + v], __ATOMIC_RELAXED) : sl[1 + v]) == c[v];
+        if (same) return tag - 1;
+        i = (i + 1) & T.mask;
+    }
+}
+
+// ManipLattice::createHashEntry (manip_lattice.cpp:1318-1354), device side: the host assigns ids in commit order and
+// sends the (query, id, coordinate) triples of the states created since the last batch; a slot is claimed with one CAS
+// on its tag and filled afterwards (lookups run in later launches of the same stream).  items: n x (nvars + 2) int32.
+__device__ __forceinline__ void table_insert_item(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* __restrict__ stab,
+                                                  const int* __restrict__ it, int nvars)
+{
+    const SmplxTableDev T = (stab ? stab[it[0]] : S)->table;
+    if (!T.slots) return;
+    const int id = it[1];
+    int c[SMPLX_MAX_VARS];
+    for (int v = 0; v < nvars; ++v) c[v] = it[2 + v];   // the items may live in pinned host memory: read them once
+    unsigned int k = smplx_coord_hash(c, nvars) & T.mask;
+    while (true) {
+        SMPLX_GLOBAL_AS int* sl = as_global(T.slots) + (size_t)k * T.stride;
+        // claim with a negative ("busy") tag, fill, publish: a concurrent lookup never sees a half-written slot as a hit
+        if (atomicCAS((int*)&sl[0], 0, -(id + 1)) == 0) {
+            for (int v = 0; v < nvars; ++v) __atomic_store_n(&sl[1 + v], c[v], __ATOMIC_RELAXED);
+            __atomic_store_n(&sl[0], id + 1, __ATOMIC_RELEASE);
+            return;
+        }
+        k = (k + 1) & T.mask;
+    }
+}
+
+// bulk inserts (k_table_insert): every thread of the launch takes its share
+__device__ __forceinline__ void table_insert_items(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* __restrict__ stab,
+                                                   const int* __restrict__ items, int n, int nvars)
+{
+    const int stride = gridDim.x * blockDim.x;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) table_insert_item(S, stab, items + (size_t)i * (nvars + 2), nvars);
+}
+
+// The inserts that ride with a batch's first kernel take EXTRA blocks behind the `first_block` working ones, so they run
+// beside the batch instead of in front of it (a lookup that misses one of them just reports "unknown").  Returns true
+// for such a block: the caller returns at once.
+__device__ __forceinline__ bool table_insert_block(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* __restrict__ stab,
+                                                   const int* __restrict__ items, int n, int first_block)
+{
+    if ((int)blockIdx.x < first_block) return false;
+    const int i = ((int)blockIdx.x - first_block) * (int)blockDim.x + (int)threadIdx.x;
+    const int nvars = S->model.nvars;
+    if (i < n) table_insert_item(S, stab, items + (size_t)i * (nvars + 2), nvars);
+    return true;
+}
+
+extern "C" __global__ void __launch_bounds__(BLOCK)
+k_table_insert(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* __restrict__ stab, const int* __restrict__ items,
+               int n, int nvars)
+{
+    table_insert_items(S, stab, items, n, nvars);
+}
+
+// manip_lattice_action_space.cpp:662-691
+__device__ __forceinline__ bool mprim_active(const SmplxActionsDev& A, double goal_dist, int type)
+{
+    if (type == SMPLX_MP_LONG) {
+        if (A.use_long_and_short) return true;
+        const bool near_goal = goal_dist <= A.thresh[SMPLX_MP_SHORT];
+        return !(A.enabled[SMPLX_MP_SHORT] && near_goal);
+    } else if (type == SMPLX_MP_SHORT) {
+        if (A.use_long_and_short) return A.enabled[type] != 0;
+        const bool near_goal = goal_dist <= A.thresh[type];
+        return A.enabled[type] && near_goal;
+    }
+    return A.enabled[type] && goal_dist <= A.thresh[type];
+}
+
+// can the primitive produce an action at all (a snap needs a joint-space goal: manip_lattice_action_space.cpp:551-559)
+__device__ __forceinline__ bool prim_has_action(const SmplxActionsDev& A, const SmplxGoalDev& G, int p)
+{
+    const int ty = A.type[p];
+    return ty == SMPLX_MP_LONG || ty == SMPLX_MP_SHORT || (ty == SMPLX_MP_SNAP_XYZ_RPY && G.type == SMPLX_GOAL_JOINT);
+}
+
+// Joint values of the successor of `parent` under primitive pi -> sq (global memory, registers or LDS).  Returns
+// prim_has_action: false, with sq untouched, where the primitive has no action for this goal type.  The one definition
+// for every path; host_apply_prim (engine.hip) mirrors its first branch.
+__device__ __forceinline__ bool successor_values(const ModelLds* __restrict__ M, const SmplxActionsDev& A, const SmplxGoalDev& G,
+                                                 int pi, const double* __restrict__ parent, double* __restrict__ sq)
+{
+    const int nv = MV_NVARS(M);
+    const int type = A.type[pi];
+    if (type == SMPLX_MP_LONG || type == SMPLX_MP_SHORT) {
+        // applyMotionPrimitive (manip_lattice_action_space.cpp:575-621)
+        double d0 = A.delta[pi][0], d1 = nv > 1 ? A.delta[pi][1] : 0.0;
+        if (A.xy_rotate_by_var3 && nv > 3) {
+            double s, c;
+            smplx_sincos(parent[3], &s, &c);
+            const double a0 = d0, a1 = d1;
+            d0 = c * a0 + (-s) * a1;
+            d1 = s * a0 + c * a1;
+        }
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) {
+            const double d = v == 0 ? d0 : (v == 1 ? d1 : A.delta[pi][v]);
+            sq[v] = d + parent[v];
+        }
+        return true;
+    }
+    if (type == SMPLX_MP_SNAP_XYZ_RPY && G.type == SMPLX_GOAL_JOINT) {
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v) sq[v] = G.angles[v];   // :551-559
+        return true;
+    }
+    return false;
+}
+
+// Goal test and heuristic of the successor with joint values sq and coordinates sc: planning-link FK, isGoal, BFS cost of
+// its cell.  Returns h.  The one definition for every path; discretisation and the table probe stay with the callers.
+__device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, const SmplxGoalDev& G, const SmplxBfsDev& bfs,
+                                                const SmplxGridDev& grid, const double* __restrict__ sq, const int* sc,
+                                                bool& is_goal)
+{
+    const int nv = MV_NVARS(M);
+    double p[3], R[9];
+    planning_fk(M, sq, p, R);
+    if (G.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
+        is_goal = true;
+        MV_UNROLL
+        for (int v = 0; v < nv; ++v)
+            if (fabs((double)(sc[v] - G.coord[v])) > G.angle_tol[v]) is_goal = false;
+    } else {                               // the position box of both pose goals :1632-1637, :1682-1684
+        is_goal = fabs(p[0] - G.xyz[0]) <= G.xyz_tol[0] && fabs(p[1] - G.xyz[1]) <= G.xyz_tol[1] &&
+                  fabs(p[2] - G.xyz[2]) <= G.xyz_tol[2];
+        // XYZ_RPY :1652-1667: the angle theta between the link's rotation and the goal's is below the tolerance iff
+        // 4 cos^2(theta / 2) = 1 + trace(Rg^T R) is above the goal's rpy_c4 (device_types.h SmplxGoalDev)
+        if (G.type == SMPLX_GOAL_XYZ_RPY && is_goal) {
+            double t = 1.0;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) t += G.rot[i] * R[i];
+            is_goal = t > G.rpy_c4;
+        }
+    }
+    int c[3];
+    world_to_cell(grid, p, c);
+    return bfs_cost_to_goal(bfs, c);
+}

@@ -500,7 +500,7 @@ bool compile_robot_text(const char* text, HostModel& m)
         D.pair_first[D.ntrees] = n;
     }
 
-    // The traversal stacks of the kernels (kernels.hip check_tree / resolve_root: one byte per level below the root;
+    // The traversal stacks of the kernels (sphere_checks.h check_tree / resolve_root: one byte per level below the root;
     // check_pair_full: two bytes per split of either tree) live in LDS, stack_bytes per thread: what this model's trees need
     {
         std::function<int(int)> depth = [&](int n) { return D.nodes[n].left < 0 ? 0 : 1 + std::max(depth(D.nodes[n].left), depth(D.nodes[n].right)); };

@@ -29,6 +29,9 @@
 // A wall-clock budget (smplx_time_params, SMPLX_TIME_WALL) is checked by the search wave itself, once per step where the
 // expansion bound is (ARAStar::timedOut, arastar.cpp:454-484): the first launch of a call records the call's start in the
 // header, moved back by the host time the call spent before that launch (`pre_ticks`); later launches of the call keep it.
+#pragma once
+
+#include "small_batch.h"   // ExpandLds, expand_state_block's lane functions, SMPLX_WAVE_SYNC
 
 #define SMPLX_AC_LEVELS 16
 #define SMPLX_AC_SLOTS 128
@@ -400,7 +403,7 @@ struct SearchRegs {
 
 // getMetricGoalDistance recovered from a state's heuristic h = cost_per_cell * BFS distance (bfs_heuristic.cpp:129-138 /
 // 355-366: both read the BFS cell of the same planning-link position); the caller knows that the product is invertible.
-// The distance of an unreachable cell must stay the one metric_goal_distance (kernels.hip) gives.
+// The distance of an unreachable cell must stay the one metric_goal_distance (lattice_steps.h) gives.
 __device__ __forceinline__ double goal_distance_of_h(int h, int cpc, const SmplxGridDev& grid)
 {
     return h == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(h / cpc) * grid.res;
@@ -488,7 +491,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
     const int book0 = (ncfg + 63) / 64 * 64;                  // first thread of the search wave
     ModelLds Mv;
 #ifdef SMPLX_CONST_MODEL
-    constexpr bool RS = true;        // the waypoint lanes keep the saved link transforms in registers (kernels.hip const_chain<.., true>)
+    constexpr bool RS = true;        // the waypoint lanes keep the saved link transforms in registers (sphere_checks.h const_chain<.., true>)
 #else
     constexpr bool RS = false;
 #endif

@@ -27,9 +27,9 @@ namespace smplx {
 
 namespace {
 
-const char* const kNames[K_COUNT] = {"k_state_prep", "k_expand", "k_pipe_prep", "k_pipe_setup", "k_pipe_configs",
-                                     "k_pipe_finish", "k_small_batch", "k_edge_valid", "k_state_valid", "k_heuristic",
-                                     "k_sphere_positions", "k_search", "k_attached_positions", "k_planning_pose"};
+#define X(id, kernel) #kernel,
+const char* const kNames[K_COUNT] = {SMPLX_PER_ROBOT_KERNELS(X)};
+#undef X
 
 uint64_t fnv1a(uint64_t h, const std::string& s)
 {
@@ -138,12 +138,9 @@ std::map<std::pair<uint64_t, int>, Loaded> g_loaded;   // (model hash, device) -
 
 void generic_kernels(KernelSet& ks)
 {
-    const void* g[K_COUNT] = {(const void*)k_state_prep, (const void*)k_expand, (const void*)k_pipe_prep,
-                              (const void*)k_pipe_setup, (const void*)k_pipe_configs, (const void*)k_pipe_finish,
-                              (const void*)k_small_batch, (const void*)k_edge_valid, (const void*)k_state_valid,
-                              (const void*)k_heuristic, (const void*)k_sphere_positions, (const void*)k_search,
-                              (const void*)k_attached_positions, (const void*)k_planning_pose};
-    for (int i = 0; i < K_COUNT; ++i) { ks.k[i].fn = nullptr; ks.k[i].generic = g[i]; }
+#define X(id, kernel) ks.k[K_##id] = KernelRef{nullptr, (const void*)kernel};
+    SMPLX_PER_ROBOT_KERNELS(X)
+#undef X
     ks.specialized = false;
 }
 
@@ -153,11 +150,8 @@ bool specialized_kernels(const SmplxModelDev& model, KernelSet& ks, std::string&
     const std::string header = model_const_header(model);
     uint64_t h = 0xCBF29CE484222325ull;
     h = fnv1a(h, header);
-    h = fnv1a(h, SRC_KERNELS_HIP);
-    h = fnv1a(h, SRC_DET_MATH_H);
-    h = fnv1a(h, SRC_DEVICE_TYPES_H);
-    h = fnv1a(h, SRC_KERNELS_H);
-    h = fnv1a(h, SRC_SEARCH_KERNEL_H);
+    h = fnv1a(h, kRootSource);
+    for (const EmbeddedSource& s : kEmbeddedHeaders) h = fnv1a(fnv1a(h, s.name), s.text);   // every file the build reads
     for (const char* o : kRtcOptions) h = fnv1a(h, o);
     for (const std::string& x : rtc_extra_defines()) h = fnv1a(h, x);
     int major = 0, minor = 0;

@@ -1,9 +1,9 @@
 // smpl_amd/csrc/specialize.h -- per-robot kernel specialisation.  The kinematic structure of a compiled model
 // (joint kinds and origins, which link carries which sphere tree, the checked pairs) is turned into compile-time
-// constants (model_compile.cpp model_const_header) and kernels.hip is compiled against them with hiprtc when a
-// planning space is created: the joint loop of the collision kernels becomes straight-line code.  Results are
-// bit-identical to the generic kernels (same operations, same order).  Code objects are cached in the process and
-// on disk ($SMPLX_CACHE_DIR, else $XDG_CACHE_HOME/smpl_amd, else $HOME/.cache/smpl_amd, else /tmp).
+// constants (model_compile.cpp model_const_header) and kernels.hip, with the headers it includes, is compiled against
+// them with hiprtc when a planning space is created: the joint loop of the collision kernels becomes straight-line
+// code.  Results are bit-identical to the generic kernels (same operations, same order).  Code objects are cached in the
+// process and on disk ($SMPLX_CACHE_DIR, else $XDG_CACHE_HOME/smpl_amd, else $HOME/.cache/smpl_amd, else /tmp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,15 +12,13 @@
 #include <tuple>
 #include <utility>
 
-#include "device_types.h"
+#include "kernels.h"
 
 namespace smplx {
 
-enum KernelId {
-    K_STATE_PREP = 0, K_EXPAND, K_PIPE_PREP, K_PIPE_SETUP, K_PIPE_CONFIGS, K_PIPE_FINISH, K_SMALL_BATCH, K_EDGE_VALID,
-    K_STATE_VALID, K_HEURISTIC, K_SPHERE_POSITIONS, K_SEARCH, K_ATTACHED_POSITIONS, K_PLANNING_POSE,
-    K_COUNT
-};
+#define X(id, kernel) K_##id,
+enum KernelId { SMPLX_PER_ROBOT_KERNELS(X) K_COUNT };
+#undef X
 
 // a kernel to launch: the per-robot build (hipFunction_t from the hiprtc module) when present, else the generic
 // kernel linked into the library

@@ -21,7 +21,7 @@
 
 namespace {
 
-// per-block tallies: 4 uint64 per block of the (state x primitive) grid (kernels.hip tally_block)
+// per-block tallies: 4 uint64 per block of the (state x primitive) grid (step_kernels.h tally_block)
 inline size_t counter_words(int B, int M) { return (size_t)blocks_for((long long)B * M, SMPLX_BLOCK) * SMPLX_TALLIES; }
 
 // carve of the per-batch device scratch: the one statement of its layout (from a null base it only measures: .bytes)
@@ -169,7 +169,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     const int be = blocks_for((long long)B * s->M, SMPLX_BLOCK);
     if (path == ExpandPath::SmallZeroCopy || path == ExpandPath::Small) {
         ++s->small.small_launches;
-        // a handful of states: ONE launch, all FK chains side by side (kernels.hip k_small_batch)
+        // a handful of states: ONE launch, all FK chains side by side (small_batch.h k_small_batch)
         // zero_copy: parents are read from, and results also written to, that space's pinned host buffers
         const ZeroCopy* zc = path == ExpandPath::SmallZeroCopy ? a.zero_copy : nullptr;
         const int small_block = smplx_small_block(s->M);

@@ -168,6 +168,32 @@ def test_per_robot_source_compiles_for_gfx950_with_the_helper(robot, tmp_path):
         assert k.encode() in code
 
 
+def test_every_source_the_kernels_include_is_embedded_and_nothing_else():
+    """The per-robot build compiles kernels.hip against the sources embedded in the library (build.py writes them into
+    csrc/_embedded_sources.h; rtc_compile.h hands the table to hiprtc, specialize.cpp hashes it into the cache key).  A header
+    that kernels.hip reaches and the table lacks would make every per-robot build fail and fall back to the generic
+    kernels: the table is the #include "..." closure of kernels.hip, found here on the test's own, and nothing else."""
+    from smpl_amd import build
+    capi.lib()   # builds, and with that writes the table, where there is no library yet
+    found, todo = set(), ["kernels.hip"]
+    while todo:
+        f = todo.pop()
+        if f in found:
+            continue
+        found.add(f)
+        if f != "model_const.h":   # written for the robot at run time (model_compile.cpp model_const_header)
+            text = open(os.path.join(build.CSRC, f)).read()
+            todo += re.findall(r'^\s*#\s*include\s+"([^"]+)"', text, re.M)   # <...> includes are the toolchain's
+            todo += ["model_const.h"] * len(re.findall(r'^\s*#\s*include\s+SMPLX_CONST_MODEL\b', text, re.M))
+    gen = open(os.path.join(build.CSRC, build.GENERATED)).read()
+    table = re.findall(r'^    \{"([^"]+)",$', gen, re.M)
+    assert 'kRootSource[] =\nR"SMPLXSRC(' + open(os.path.join(build.CSRC, "kernels.hip")).read() + ')SMPLXSRC";' in gen
+    assert found - {"kernels.hip"} == set(table) | {"model_const.h"}
+    assert table == sorted(set(table)) and "search_kernel.h" in table    # each once, in a fixed order
+    unreachable = set(os.listdir(build.CSRC)) - found
+    assert {"engine.hip", "step.h", "specialize.cpp", "rtc_compile.h"} <= unreachable and not unreachable & set(table)
+
+
 def test_default_is_the_forks_xy_rotation(small_cfg):
     """[FORK] manip_lattice_action_space.cpp:590-599: delta[0], delta[1] rotated by state[3] -- the reference's
     behaviour is what every config runs unless told otherwise (xy_rotate_by_var3 = 0 selects upstream smpl)."""

@@ -1,5 +1,5 @@
-"""One GetSuccs loop body for every expansion kernel: the four shared steps of kernels.hip (successor joint values,
-waypoint count, metric goal distance, goal test plus heuristic) are reached through six launch paths, and every path
+"""One GetSuccs loop body for every expansion kernel: the four shared steps (successor joint values, metric goal distance,
+goal test plus heuristic in csrc/lattice_steps.h; waypoint count in csrc/config_checks.h) are reached through six launch paths, and every path
 must leave the oracle's bits for the same rows.
 
 Inputs: 37 states of the 7-DOF arm on the small scene -- the start, the goal, the goal with each joint moved by 4 degrees

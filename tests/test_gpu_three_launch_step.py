@@ -201,7 +201,7 @@ def _host_ids(s):
 
 def _assert_oracle(got, exp, host, N):
     """One step against the oracle rows of its states; ids against the host's table; the stream against both.
-    The lookup tally of a colliding edge has no early exit on the waypoint-parallel path (kernels.hip, the comment above
+    The lookup tally of a colliding edge has no early exit on the waypoint-parallel path (csrc/step_kernels.h, the comment above
     the pipeline): it is compared where the edge does not collide."""
     B = got["flags"].shape[0]
     e = {k: v[:B] for k, v in exp.items()}
