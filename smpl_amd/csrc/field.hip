@@ -375,7 +375,7 @@ int smplx_grid_update_points(smplx_grid* g, const double* old_xyz, int n_old, co
 {
     // DistanceMap::updatePointsInMap (distance_map.hpp:367-435): as SETS of cells, remove old \ new, then add new \ old.
     // OccupancyGrid::updatePointsInField passes the points through without touching its reference counts ("TODO: ref
-    // counting", occupancy_grid.cpp:408-415): neither does this.
+    // counting", occupancy_grid.cpp:416-422): neither does this.
     std::vector<int> co, cn;
     if (int e = points_to_cells(g, old_xyz, n_old, co)) return e;
     if (int e = points_to_cells(g, new_xyz, n_new, cn)) return e;

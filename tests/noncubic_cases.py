@@ -46,12 +46,17 @@ def brute_force(occ, dmax):
     nx, ny, nz = occ.shape
     pad = np.ones((nx + 2, ny + 2, nz + 2), bool)
     pad[1:-1, 1:-1, 1:-1] = occ
-    obs = np.argwhere(pad).astype(np.int64) - 1          # interior coordinates; the border layer sits at -1 and n
+    # the narrowest integers that hold 3 n^2, the largest squared distance there is (n: the longest extent): the work
+    # is cells x obstacles element operations, and numpy does them four times as fast on 2 bytes as on 8
+    bound = 3 * max(occ.shape) ** 2
+    dt = np.int16 if bound < 2 ** 15 else np.int32 if bound < 2 ** 31 else np.int64
+    obs = (np.argwhere(pad) - 1).astype(dt)              # interior coordinates; the border layer sits at -1 and n
     out = np.zeros(occ.shape, np.int64)
-    cells = np.argwhere(np.ones(occ.shape, bool)).astype(np.int64)
-    for k in range(0, cells.shape[0], 2048):
-        c = cells[k:k + 2048]
-        d = ((c[:, None, :] - obs[None, :, :]) ** 2).sum(axis=2).min(axis=1)
+    cells = np.argwhere(np.ones(occ.shape, bool)).astype(dt)
+    for k in range(0, cells.shape[0], 256):              # (256 cells x obstacles at a time stays in cache)
+        c = cells[k:k + 256]
+        d = sum((c[:, None, a] - obs[None, :, a]) ** 2 for a in range(3)).min(axis=1)
+        assert d.dtype == dt
         out[c[:, 0], c[:, 1], c[:, 2]] = d
     return np.minimum(out, dmax * dmax).astype(np.int32)
 
