@@ -279,7 +279,7 @@ int smplx_bfs_levels(const smplx_space* s);
 int smplx_expand_batch(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* coord, double* succ_q,
                        int32_t* h, int32_t* cost, int32_t* lookups);
 /* same, everything resident in HBM; launches on `stream` and returns without synchronising.
- * work: device scratch of smplx_expand_work_bytes(s, B) bytes.  d_counters: see smplx_counters_bytes (may be NULL). */
+ * work: device scratch of smplx_expand_work_bytes(s, B) bytes, 16-byte aligned.  d_counters: see smplx_counters_bytes (may be NULL). */
 size_t smplx_expand_work_bytes(const smplx_space* s, int B);
 /* d_counters: device scratch of smplx_counters_bytes(s, B) bytes, zeroed by the caller; tallies accumulate per
  * thread block without atomics.  smplx_counters_read sums them (synchronous copy): out[0] successor evaluations,

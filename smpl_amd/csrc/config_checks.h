@@ -12,9 +12,12 @@
 // self_collision_model.cpp:407-428): group trees vs grid in chain order, then the checked
 // link pairs sphere-vs-sphere.
 // the configuration's joint values are already staged in the thread's LDS slots (stage_config or the caller itself)
-template <bool RS = false>
+// SC (per-robot build): sn[v], cs[v] = smplx_sincos of the staged value of every variable of CM_TRIG_COLLISION, which the
+// caller has from the parent's row (sphere_checks.h parent_trig); every other caller leaves the chain to evaluate them
+template <bool RS = false, bool SC = false>
 __device__ __forceinline__ bool config_valid_staged(const ModelLds* __restrict__ M, const ThreadLds& L, const SmplxGridDev& g,
-                                                    const EdgeRef& e, int& lookups)
+                                                    const EdgeRef& e, int& lookups, const double* sn = nullptr,
+                                                    const double* cs = nullptr)
 {
     double T[12];
 #pragma unroll
@@ -32,9 +35,13 @@ __device__ __forceinline__ bool config_valid_staged(const ModelLds* __restrict__
         for (int i = 0; i < 12; ++i) C.T[i] = 0.0;
 #pragma unroll
         for (int v = 0; v < CM_NV; ++v) C.q[v] = lds_d(L, L.q_base + v);
+        if constexpr (SC) {
+#pragma unroll
+            for (int v = 0; v < CM_NV; ++v) { C.sn[v] = sn[v]; C.cs[v] = cs[v]; }
+        }
         C.pair_hit = false; C.recheck_all = false; C.P = P;
         C.pd2 = 0;
-        if (!const_chain<0, -1, RS>(M, L, g, C, lookups)) return false;
+        if (!const_chain<0, -1, RS, SC>(M, L, g, C, lookups)) return false;
         pair_hit = C.pair_hit; recheck_all = C.recheck_all;
         const PendingPairs filled = C.P;
         P = filled;

@@ -49,20 +49,20 @@ __global__ void k_expand(const SmplxSpaceDev* S, const double* Q, int B, const d
 __global__ void k_pipe_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
                             int* work_count,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* cmp_totals,
-                            const int* ins_items, int n_ins);
+                            const int* ins_items, int n_ins, double* trig);
 __global__ void k_pipe_setup(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
                              unsigned char* out_flags, double* out_q, int* edge_w, int* edge_lookups,
                              unsigned char* edge_bad, int* state_lookups, unsigned char* state_bad, unsigned long long* work,
                              int* work_count, int capacity,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int have_goal_dist,
-                             int* cmp_totals, const int* ins_items, int n_ins, int nprims, int nvars);
+                             int* cmp_totals, const int* ins_items, int n_ins, int nprims, int nvars, double* trig);
 __global__ void k_pipe_configs(const SmplxSpaceDev* S, const double* Q, int B, const double* out_q,
                                const int* edge_w, int* edge_lookups, unsigned char* edge_bad, int* state_lookups,
                                unsigned char* state_bad, const unsigned long long* work, const int* work_count, int capacity,
                                int cfg_blocks, const unsigned char* out_flags, int* succ_coord,
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int want_id,
                                unsigned long long* succ_eval, unsigned char* succ_goal, int nprims, int nvars,
-                               const unsigned char* blob, int blob_bytes);
+                               const unsigned char* blob, int blob_bytes, const double* trig);
 __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, int B, const int* edge_w,
                               const int* edge_lookups, const unsigned char* edge_bad, const int* state_lookups,
                               const unsigned char* state_bad, unsigned char* out_flags, int* out_coord, double* out_q,

@@ -50,6 +50,23 @@ __device__ __forceinline__ void planning_fk(const ModelLds* __restrict__ M, cons
     planning_fk(M, q, p, nullptr);
 }
 
+#ifdef SMPLX_CONST_MODEL
+// ... with the sines and cosines of the (normalised) joint values handed in (sphere_checks.h const_planning_chain_sc)
+__device__ __forceinline__ void planning_fk_sc(const ModelLds* __restrict__ M, const double* __restrict__ q, const double* __restrict__ sn,
+                                               const double* __restrict__ cs, double p[3], double* R)
+{
+    double T[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = 0.0;
+    const_planning_chain_sc<0, true>(M, q, sn, cs, T);
+    p[0] = T[3]; p[1] = T[7]; p[2] = T[11];
+    if (R) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { R[3 * i] = T[4 * i]; R[3 * i + 1] = T[4 * i + 1]; R[3 * i + 2] = T[4 * i + 2]; }
+    }
+}
+#endif
+
 __device__ __forceinline__ void world_to_cell(const SmplxGridDev& g, const double p[3], int c[3])
 {
     c[0] = (int)(g.inv_res * (p[0] - g.origin_minus_res[0]) + 0.5) - 1;
@@ -69,6 +86,49 @@ __device__ __forceinline__ double metric_goal_distance(const ModelLds* __restric
     world_to_cell(grid, p, c);
     return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
 }
+
+#ifdef SMPLX_CONST_MODEL
+// ... from the state's sines and cosines (planning_fk_sc)
+__device__ __forceinline__ double metric_goal_distance_sc(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
+                                                          const double* __restrict__ q, const double* __restrict__ sn,
+                                                          const double* __restrict__ cs)
+{
+    double p[3];
+    planning_fk_sc(M, q, sn, cs, p, nullptr);
+    int c[3];
+    world_to_cell(grid, p, c);
+    return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
+}
+#endif
+
+#ifdef SMPLX_CONST_MODEL
+// metric_goal_distance of the state with joint values q, and -- store -- the state's row of sines and cosines
+// (sphere_checks.h parent_trig): the normalised ones are what the distance's chain evaluates anyway, the raw ones are
+// evaluated where they can differ (a continuous variable outside [-pi, pi])
+__device__ __forceinline__ double trig_row_and_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
+                                                             const double* __restrict__ q, double* __restrict__ trig_row, bool store)
+{
+    double sn[CM_NV], cs[CM_NV];
+    trig_pair_t* row = reinterpret_cast<trig_pair_t*>(trig_row);
+#pragma unroll
+    for (int v = 0; v < CM_NV; ++v) {
+        const double x = q[v];
+        double xn = x;
+        if (CM_VAR_TYPE[v] == SMPLX_JT_CONTINUOUS) xn = smplx_normalize_angle(x);
+        sn[v] = 0.0; cs[v] = 0.0;   // a variable no SMPLX_TK_REV_*_T joint turns on: nobody reads its pairs, zeros are stored
+        if ((CM_TRIG_ANY >> v) & 1u) smplx_sincos(xn, &sn[v], &cs[v]);
+        double rs = sn[v], rc = cs[v];
+        if (((CM_TRIG_ANY >> v) & 1u) && CM_VAR_TYPE[v] == SMPLX_JT_CONTINUOUS)
+            if (__double_as_longlong(xn) != __double_as_longlong(x)) smplx_sincos(x, &rs, &rc);
+        if (store) {
+            trig_pair_t raw, nrm;
+            raw.x = rs; raw.y = rc; nrm.x = sn[v]; nrm.y = cs[v];
+            row[v] = raw; row[CM_NV + v] = nrm;
+        }
+    }
+    return metric_goal_distance_sc(M, grid, bfs, q, sn, cs);
+}
+#endif
 
 // BfsHeuristic::getBfsCostToGoal (bfs_heuristic.cpp:355-366)
 __device__ __forceinline__ int bfs_cost_to_goal(const SmplxBfsDev& b, const int c[3])
@@ -247,12 +307,18 @@ __device__ __forceinline__ bool successor_values(const ModelLds* __restrict__ M,
 
 // Goal test and heuristic of the successor with joint values sq and coordinates sc: planning-link FK, isGoal, BFS cost of
 // its cell.  Returns h.  The one definition for every path; discretisation and the table probe stay with the callers.
+// SC (per-robot build): sn, cs = the sines and cosines the planning-link chain would evaluate (planning_fk_sc).
+template <bool SC = false>
 __device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, const SmplxGoalDev& G, const SmplxBfsDev& bfs,
                                                 const SmplxGridDev& grid, const double* __restrict__ sq, const int* sc,
-                                                bool& is_goal)
+                                                bool& is_goal, const double* sn = nullptr, const double* cs = nullptr)
 {
     const int nv = MV_NVARS(M);
     double p[3], R[9];
+#ifdef SMPLX_CONST_MODEL
+    if constexpr (SC) planning_fk_sc(M, sq, sn, cs, p, R);
+    else
+#endif
     planning_fk(M, sq, p, R);
     if (G.type == SMPLX_GOAL_JOINT) {      // manip_lattice.cpp:1596-1606
         is_goal = true;

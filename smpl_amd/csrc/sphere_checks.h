@@ -183,6 +183,7 @@ __device__ __forceinline__ JointHead load_joint_head(const ModelLds* __restrict_
 struct ChainState {
     double T[12];
     double q[CM_NV];
+    double sn[CM_NV], cs[CM_NV];   // const_chain<.., SC = true>: sine and cosine of q[v], handed in by the caller (parent_trig below)
     double roots[3 * (CM_NT > 0 ? CM_NT : 1)];   // only the slots that lead a pair are ever touched
     bool pair_hit, recheck_all;
     PendingPairs P;
@@ -221,12 +222,24 @@ __device__ __forceinline__ void const_pairs(const ThreadLds& L, ChainState& C, c
 
 // apply_joint_t with the origin's translation as literals: terms with an exactly-zero coefficient are dropped
 // (x*0 is +-0 and adding it changes no non-zero value)
-template <int J, bool OnRoot>
-__device__ __forceinline__ void apply_joint_const(double q, double T[12])
+// SC: the sine and cosine of q come in as sv and cv (smplx_sincos(q) evaluated elsewhere: the same bits) -- the
+// SMPLX_TK_REV_*_T kinds only; what follows the sincos is the same sequence of operations
+template <int J, bool OnRoot, bool SC = false>
+__device__ __forceinline__ void apply_joint_const(double q, double T[12], double sv = 0.0, double cv = 0.0)
 {
     constexpr int kind = CM_KIND[J];
     constexpr double tx = CM_TX[J], ty = CM_TY[J], tz = CM_TZ[J];
-    if constexpr (OnRoot) {
+    if constexpr (OnRoot && SC && kind != SMPLX_TK_FIXED_T) {
+        // apply_joint_t on the root link, the sincos taken out
+#pragma unroll
+        for (int i = 0; i < 12; ++i) T[i] = 0.0;
+        T[0] = 1.0; T[5] = 1.0; T[10] = 1.0;
+        T[3] = tx; T[7] = ty; T[11] = tz;
+        const double s = sv, c = cv;
+        if constexpr (kind == SMPLX_TK_REV_X_T) { T[5] = c; T[6] = 0.0 - s; T[9] = s; T[10] = c; }
+        else if constexpr (kind == SMPLX_TK_REV_Y_T) { T[0] = c; T[2] = s; T[8] = 0.0 - s; T[10] = c; }
+        else { T[0] = c; T[1] = 0.0 - s; T[4] = s; T[5] = c; }
+    } else if constexpr (OnRoot) {
         apply_joint_t(kind, tx, ty, tz, q, T, true);
     } else {
         if constexpr (tx != 0.0 || ty != 0.0 || tz != 0.0) {
@@ -242,7 +255,8 @@ __device__ __forceinline__ void apply_joint_const(double q, double T[12])
         }
         if constexpr (kind != SMPLX_TK_FIXED_T) {
             double s, c;
-            smplx_sincos(q, &s, &c);
+            if constexpr (SC) { s = sv; c = cv; }
+            else smplx_sincos(q, &s, &c);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const double a = T[4 * i + 0], b = T[4 * i + 1], d = T[4 * i + 2];
@@ -330,7 +344,8 @@ __device__ __forceinline__ bool resolve_root(const ModelLds* __restrict__ M, con
 }
 
 // PT = the tree whose root lookup was issued at an earlier joint and has not been looked at yet (-1: none)
-template <int J, int PT, bool RS = false>
+// SC: the SMPLX_TK_REV_*_T joints take C.sn / C.cs instead of evaluating smplx_sincos(C.q[var])
+template <int J, int PT, bool RS = false, bool SC = false>
 __device__ __forceinline__ bool const_chain(const ModelLds* __restrict__ M, const ThreadLds& L, const SmplxGridDev& g,
                                             ChainState& C, int& lookups)
 {
@@ -342,7 +357,8 @@ __device__ __forceinline__ bool const_chain(const ModelLds* __restrict__ M, cons
         }
         double q = 0.0;
         if constexpr (var >= 0) q = C.q[var];
-        if constexpr (kind >= SMPLX_TK_FIXED_T) apply_joint_const<J, src == SMPLX_SRC_ROOT>(q, C.T);
+        if constexpr (SC && kind > SMPLX_TK_FIXED_T && var >= 0) apply_joint_const<J, src == SMPLX_SRC_ROOT, true>(q, C.T, C.sn[var], C.cs[var]);
+        else if constexpr (kind >= SMPLX_TK_FIXED_T) apply_joint_const<J, src == SMPLX_SRC_ROOT>(q, C.T);
         else apply_joint(&M->joints[J], q, C.T, src == SMPLX_SRC_ROOT);
         if constexpr (save >= 0) {
 #pragma unroll
@@ -366,9 +382,9 @@ __device__ __forceinline__ bool const_chain(const ModelLds* __restrict__ M, cons
 #ifndef ABL_NO_PAIRS
             const_pairs<tree, CM_PAIR_FIRST[tree], CM_PAIR_FIRST[tree + 1]>(L, C, rp);
 #endif
-            return const_chain<J + 1, tree, RS>(M, L, g, C, lookups);
+            return const_chain<J + 1, tree, RS, SC>(M, L, g, C, lookups);
         } else {
-            return const_chain<J + 1, -1, RS>(M, L, g, C, lookups);
+            return const_chain<J + 1, -1, RS, SC>(M, L, g, C, lookups);
         }
     } else {
         if constexpr (PT >= 0) {
@@ -401,6 +417,102 @@ __device__ __forceinline__ void const_planning_chain(const ModelLds* __restrict_
         } else {
             const_planning_chain<J + 1, First>(M, q, T);
         }
+    }
+}
+
+// ... with the sines and cosines handed in: sn[v], cs[v] = smplx_sincos of q[v], normalised first where v is continuous
+// (what the chain above evaluates itself), for every variable of CM_TRIG_PLANNING.  q is still what the other kinds take.
+template <int J, bool First>
+__device__ __forceinline__ void const_planning_chain_sc(const ModelLds* __restrict__ M, const double* __restrict__ q,
+                                                        const double* __restrict__ sn, const double* __restrict__ cs, double T[12])
+{
+    if constexpr (J < CM_NJ) {
+        if constexpr (CM_ON_CHAIN[J] != 0) {
+            constexpr int kind = CM_KIND[J], var = CM_VAR[J];
+            if constexpr (kind > SMPLX_TK_FIXED_T && var >= 0) {
+                apply_joint_const<J, First, true>(0.0, T, sn[var], cs[var]);
+            } else {
+                double qv = 0.0;
+                if constexpr (var >= 0) {
+                    qv = q[var];
+                    if constexpr (CM_VAR_TYPE[var] == SMPLX_JT_CONTINUOUS) qv = smplx_normalize_angle(qv);
+                }
+                if constexpr (kind >= SMPLX_TK_FIXED_T) apply_joint_const<J, First>(qv, T);
+                else apply_joint(&M->joints[J], qv, T, First);
+            }
+            const_planning_chain_sc<J + 1, false>(M, q, sn, cs, T);
+        } else {
+            const_planning_chain_sc<J + 1, First>(M, q, sn, cs, T);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The parent's sines and cosines ("a parent's sines and cosines").  A frontier step keeps, per
+// state, smplx_sincos of every joint value in its scratch (ExpandWork::trig, step.h): row[si] is 4 * CM_NV doubles,
+//   [0, 2 NV)     (sin, cos) of q[v]                          -- what the collision chain evaluates
+//   [2 NV, 4 NV)  (sin, cos) of smplx_normalize_angle(q[v]) where v is continuous, of q[v] otherwise -- the planning-link chain
+// each pair 16 bytes, each half a run of 16-byte pieces.  On an edge almost every variable keeps the parent's bits
+// (start + alpha * 0 == start), and smplx_sincos is a function of its argument's bits: such a variable takes the row's pair,
+// the others are evaluated, one per lane and round (a wave runs as many rounds as its worst lane has changed variables).
+// ---------------------------------------------------------------------------------------------
+typedef double __attribute__((ext_vector_type(2))) trig_pair_t;
+
+constexpr unsigned cm_trig_vars(bool planning)
+{
+    unsigned m = 0;
+    for (int j = 0; j < CM_NJ; ++j)
+        if (CM_KIND[j] > SMPLX_TK_FIXED_T && CM_VAR[j] >= 0 && (!planning || CM_ON_CHAIN[j] != 0)) m |= 1u << CM_VAR[j];
+    return m;
+}
+constexpr unsigned CM_TRIG_COLLISION = cm_trig_vars(false);   // variables a SMPLX_TK_REV_*_T joint of the whole chain turns on
+constexpr unsigned CM_TRIG_PLANNING = cm_trig_vars(true);     // ... of the planning-link chain
+constexpr int cm_popcount(unsigned m) { int n = 0; for (; m != 0; m &= m - 1) ++n; return n; }
+// Whether the step keeps the table for this robot.  An edge evaluates the one or two variables it moves whatever else
+// happens, so the table saves at most (variables of CM_TRIG_COLLISION) - 2 sincos a configuration and costs a row of loads and
+// registers: a robot with fewer than four such variables (the mixed-kinds test robot has one) computes as it always did.
+constexpr bool CM_PARENT_TRIG = cm_popcount(CM_TRIG_COLLISION) >= 4;
+constexpr unsigned CM_TRIG_ANY = CM_TRIG_COLLISION | CM_TRIG_PLANNING;   // variables whose pairs some consumer reads
+#define SMPLX_TRIG_ROW (4 * CM_NV)
+
+// one half of a state's row (raw: Norm = false) into registers
+template <bool Norm>
+__device__ __forceinline__ void trig_row_load(const double* __restrict__ trig, long long si, double (&row)[2 * CM_NV])
+{
+    const trig_pair_t* p = reinterpret_cast<const trig_pair_t*>(trig + si * SMPLX_TRIG_ROW + (Norm ? 2 * CM_NV : 0));
+#pragma unroll
+    for (int v = 0; v < CM_NV; ++v) { const trig_pair_t t = p[v]; row[2 * v] = t.x; row[2 * v + 1] = t.y; }
+}
+
+// sn[v], cs[v] for the variables of Mask: the row's pair where x[v] has the bits of the parent's value ref[v] (compared as
+// integers: -0.0 is not +0.0), smplx_sincos(x[v]) -- Norm: of the normalised angle of a continuous variable -- otherwise
+template <unsigned Mask, bool Norm>
+__device__ __forceinline__ void parent_trig(const double (&x)[CM_NV], const double (&ref)[CM_NV], const double (&row)[2 * CM_NV],
+                                            double (&sn)[CM_NV], double (&cs)[CM_NV])
+{
+    unsigned todo = 0;
+#pragma unroll
+    for (int v = 0; v < CM_NV; ++v) {
+        sn[v] = row[2 * v]; cs[v] = row[2 * v + 1];
+        if ((Mask >> v) & 1u)
+            if (__double_as_longlong(x[v]) != __double_as_longlong(ref[v])) todo |= 1u << v;
+    }
+    while (todo != 0) {
+        const int v = __ffs((int)todo) - 1;
+        todo &= todo - 1;
+        double a = x[0];
+#pragma unroll
+        for (int u = 1; u < CM_NV; ++u) a = v == u ? x[u] : a;
+        if (Norm) {
+            bool cont = false;
+#pragma unroll
+            for (int u = 0; u < CM_NV; ++u) if (CM_VAR_TYPE[u] == SMPLX_JT_CONTINUOUS) cont = cont || v == u;
+            if (cont) a = smplx_normalize_angle(a);
+        }
+        double s, c;
+        smplx_sincos(a, &s, &c);
+#pragma unroll
+        for (int u = 0; u < CM_NV; ++u) { sn[u] = v == u ? s : sn[u]; cs[u] = v == u ? c : cs[u]; }
     }
 }
 #endif   // SMPLX_CONST_MODEL

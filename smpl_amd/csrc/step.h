@@ -38,6 +38,7 @@ struct ExpandWork {
     int32_t* work_count;        // NOT in the caller's scratch: the stream's counter set (StepLaunch::work_counters)
     unsigned long long* work;   // 64-bit items: edge | waypoint << 32 | waypoint count << 48
     int capacity;
+    double* trig;               // per state: sines and cosines of its joint values, 4 N doubles (sphere_checks.h parent_trig)
     size_t bytes;               // of the whole scratch (smplx_expand_work_bytes)
 };
 
@@ -59,6 +60,7 @@ ExpandWork carve_work(void* base, int B, int M, int N)
     k.work_count = nullptr; o += 2048;       // (where the counters used to live: the size callers allocate stays what it was)
     k.work = (unsigned long long*)(w + o); o += align256(bm * 16 * 8);
     k.capacity = (int)std::min<size_t>(bm * 16, (size_t)1 << 30) / 8 * 8;
+    k.trig = (double*)(w + o); o += align256(b * 4 * N * 8);
     k.bytes = o;
     return k;
 }
@@ -218,12 +220,12 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         const bool pipe_prep = s->step.pipe_prep || be > s->step.three_launch_blocks;
         if (pipe_prep)
             KLAUNCH(s, K_PIPE_PREP, k_pipe_prep, dim3(bs + blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), lm, a.stream, s->d_space, a.q, B,
-                               k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins);
+                               k.goal_dist, k.work_count, a.stab, a.state_q, cmp.totals, ins_items, n_ins, k.trig);
         const int n_ins_setup = pipe_prep ? 0 : n_ins;
         KLAUNCH(s, K_PIPE_SETUP, k_pipe_setup, dim3(be + blocks_for(n_ins_setup, SMPLX_BLOCK)), dim3(pipe_prep ? SMPLX_BLOCK : SMPLX_SETUP_BLOCK), lm, a.stream, s->d_space, a.q, B,
                            k.goal_dist, a.flags, a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad,
                            k.work, k.work_count, k.capacity, a.stab, a.state_q, pipe_prep ? 1 : 0, cmp.totals, ins_items, n_ins_setup,
-                           s->M, s->N);
+                           s->M, s->N, k.trig);
         if (ev) (void)hipEventRecord(ev[0], a.stream);
         // (a smaller grid was tried -- idle blocks cost next to nothing: 22.0 us at 3 configurations per edge, 21.7 at 1.35)
         // behind the bc collision blocks: one successor thread per edge (dense: it leaves at once where setup's flag is not 0)
@@ -234,7 +236,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, B,
                            a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
                            k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal,
-                           s->M, s->N, blob, (int)s->blob_bytes);
+                           s->M, s->N, blob, (int)s->blob_bytes, k.trig);
         if (ev) (void)hipEventRecord(ev[1], a.stream);
         // edges whose waypoints did not fit the work list (normally none) are walked whole by their finish thread
         KLAUNCH(s, K_PIPE_FINISH, k_pipe_finish, dim3(be), dim3(SMPLX_BLOCK), s->lds_bytes, a.stream, s->d_space, a.q, B,

@@ -202,6 +202,13 @@ k_expand(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int 
 // reference the three-launch step is compared against.
 // The work-list counters belong to the engine, one set per stream, and are all-zero between steps: block 0 of
 // k_pipe_finish clears them behind their last reader.
+// Per-robot build: the step keeps each state's sines and cosines (sphere_checks.h parent_trig; ExpandWork::trig, 4 N doubles a
+// state: raw, and of the normalised angles).  Written by whoever computes the state's goal distance, whose chain takes the
+// normalised ones: the goal-distance wave of k_pipe_setup -- one (state, variable) pair a lane, handed by shuffles to the
+// lanes that run the chain -- or, in the four-launch mode, the state threads of k_pipe_prep (lattice_steps.h
+// trig_row_and_goal_distance); read a launch later by both roles of k_pipe_configs, in the same round of loads as the
+// joint values: a collision thread evaluates smplx_sincos only for the variables its waypoint moves, a successor thread
+// for those its primitive moves, in rounds of one variable per lane.  The generic build keeps computing from the values.
 // What the host knows comes in as kernel arguments, so that no thread's first indexed load waits for a load from the
 // space record: nprims (every thread's state index is tid / nprims; a cross-query batch uses the lead space's actions for
 // every row, so one value per launch is right), nvars (generic build: row strides in front of the staged model) and, for
@@ -220,7 +227,7 @@ extern "C" __global__ void __launch_bounds__(BLOCK)
 k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
             double* __restrict__ goal_dist, int* __restrict__ work_count,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q, int* __restrict__ cmp_totals,
-            const int* __restrict__ ins_items, int n_ins)
+            const int* __restrict__ ins_items, int n_ins, double* __restrict__ trig)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     // K5: the states the host committed since the last batch join the device table (createHashEntry) in extra blocks
@@ -234,6 +241,12 @@ k_pipe_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, i
         for (int k = threadIdx.x; k < SMPLX_CMP_TOTALS; k += BLOCK) cmp_totals[k] = 0;
     if (i >= B) return;
     const SmplxBfsDev bfs = (stab ? stab[state_q[i]] : S)->bfs;   // per-query data in a cross-query batch
+#ifdef SMPLX_CONST_MODEL
+    if constexpr (CM_PARENT_TRIG) {
+        goal_dist[i] = trig_row_and_goal_distance(M, grid, bfs, Q + (int64_t)i * CM_NV, trig + (int64_t)i * SMPLX_TRIG_ROW, true);
+        return;
+    }
+#endif
     goal_dist[i] = metric_goal_distance(M, grid, bfs, Q + (int64_t)i * MV_NVARS(M));
 }
 
@@ -252,6 +265,11 @@ __device__ __forceinline__ int pipe_edge_values(const ModelLds* __restrict__ M, 
 }
 
 // A block of k_pipe_setup is BLOCK edge threads plus one more wave, which computes the goal distances beside them.
+#ifdef SMPLX_CONST_MODEL
+#define SMPLX_SETUP_SERIAL_DIST (!CM_PARENT_TRIG)   // one lane per state, the whole chain with its sincos
+#else
+#define SMPLX_SETUP_SERIAL_DIST true
+#endif
 extern "C" __global__ void __launch_bounds__(SMPLX_SETUP_BLOCK)
 k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int B,
              double* __restrict__ goal_dist, unsigned char* __restrict__ out_flags, double* __restrict__ out_q,
@@ -260,7 +278,7 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
              unsigned long long* __restrict__ work, int* __restrict__ work_count, int capacity,
         const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q,
              int have_goal_dist, int* __restrict__ cmp_totals, const int* __restrict__ ins_items, int n_ins,
-             int nprims, int nvars)
+             int nprims, int nvars, double* __restrict__ trig)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     const SmplxActionsDev& A = S->actions;
@@ -302,7 +320,52 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
                 for (int k = threadIdx.x - BLOCK; k < SMPLX_CMP_TOTALS; k += 64) cmp_totals[k] = 0;
             const long long e1 = e0 + BLOCK - 1 < n_edges ? e0 + BLOCK - 1 : n_edges - 1;   // (e0 < n_edges: this is an edge block)
             const int s1 = (int)(e1 / nprims);                                               // < B
-            for (int sj = s0 + (int)threadIdx.x - BLOCK; sj <= s1; sj += 64) {
+#ifdef SMPLX_CONST_MODEL
+            // Per-robot build: the chain's sincos are evaluated lane-parallel, one (state, variable) pair per lane, 64 / NV
+            // states a round (one round at 7 states a block), and kept as the state's row of the table (sphere_checks.h
+            // parent_trig); the normalised ones travel by shuffles to the lanes that then run the chain without a sincos in
+            // it.  One writer per row: the block that holds the state's first edge, as for goal_dist.  (One lane per state
+            // that evaluates and stores its whole row ahead of its chain, as k_pipe_prep does, made the step slower than
+            // before the table: profiles/parent_trig_ab.txt section 5.)
+            constexpr int PER = CM_PARENT_TRIG ? 64 / CM_NV : 0;
+            const int l = (int)threadIdx.x - BLOCK;
+            const int ls = l / CM_NV, lv = l - ls * CM_NV;
+            for (int r0 = s0; PER > 0 && r0 <= s1; r0 += PER) {   // (uniform over the wave)
+                const int sj = r0 + ls;
+                double ns = 0.0, nc = 0.0;
+                if (ls < PER && sj <= s1) {
+                    const double x = Q[(int64_t)sj * CM_NV + lv];
+                    double rs = 0.0, rc = 0.0;   // a variable no SMPLX_TK_REV_*_T joint turns on: nobody reads its pairs, zeros are stored
+                    if ((CM_TRIG_ANY >> lv) & 1u) smplx_sincos(x, &rs, &rc);
+                    ns = rs; nc = rc;
+                    bool cont = false;
+#pragma unroll
+                    for (int u = 0; u < CM_NV; ++u) if (CM_VAR_TYPE[u] == SMPLX_JT_CONTINUOUS) cont = cont || lv == u;
+                    if (cont && ((CM_TRIG_ANY >> lv) & 1u)) {
+                        const double xn = smplx_normalize_angle(x);
+                        if (__double_as_longlong(xn) != __double_as_longlong(x)) smplx_sincos(xn, &ns, &nc);
+                    }
+                    if ((long long)sj * nprims >= e0) {
+                        trig_pair_t* row = reinterpret_cast<trig_pair_t*>(trig + (int64_t)sj * SMPLX_TRIG_ROW);
+                        trig_pair_t raw, nrm;
+                        raw.x = rs; raw.y = rc; nrm.x = ns; nrm.y = nc;
+                        row[lv] = raw; row[CM_NV + lv] = nrm;
+                    }
+                }
+                double sn[CM_NV], cs[CM_NV];
+#pragma unroll
+                for (int v = 0; v < CM_NV; ++v) {   // lane k < PER gathers the pairs of state r0 + k (every lane takes part)
+                    const int from = (l * CM_NV + v) & 63;
+                    sn[v] = __shfl(ns, from); cs[v] = __shfl(nc, from);
+                }
+                if (l < PER && r0 + l <= s1) {
+                    const int sk = r0 + l;
+                    const SmplxBfsDev bfs = (stab ? stab[state_q[sk]] : S)->bfs;
+                    block_goal_dist[sk - s0] = metric_goal_distance_sc(M, S->grid, bfs, Q + (int64_t)sk * CM_NV, sn, cs);
+                }
+            }
+#endif
+            for (int sj = s0 + (int)threadIdx.x - BLOCK; SMPLX_SETUP_SERIAL_DIST && sj <= s1; sj += 64) {
                 const SmplxBfsDev bfs = (stab ? stab[state_q[sj]] : S)->bfs;   // a copy: its loads travel in front of the FK chain
                 block_goal_dist[sj - s0] = metric_goal_distance(M, S->grid, bfs, Q + (int64_t)sj * nv);
             }
@@ -380,9 +443,11 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
 // What the verdict of an edge does not decide: discretisation, state-table id, planning-link FK, goal test, heuristic
 // (manip_lattice.cpp:1496-1535 for a successor that passed the limits test).  Needs the successor's joint values and
 // the query's goal, BFS grid and table only, all final when k_pipe_setup ends.  sc: where the coordinates go.
+template <bool SC = false>
 __device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, const SmplxSpaceDev* __restrict__ Sq,
                                                const SmplxGridDev& grid, const double* __restrict__ sq, int* __restrict__ sc,
-                                               bool want_id, int& h, int& id, bool& is_goal)
+                                               bool want_id, int& h, int& id, bool& is_goal, const double* sn = nullptr,
+                                               const double* cs = nullptr)
 {
     const int nv = MV_NVARS(M);
     const SmplxBfsDev bfs = Sq->bfs;
@@ -390,7 +455,7 @@ __device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, c
     for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
     // K5: the table lookup only needs the coordinates; issued here, its probe lands behind the planning-link FK
     id = want_id ? table_lookup<false>(Sq->table, sc, nv) : -1;
-    h = successor_goal_h(M, Sq->goal, bfs, grid, sq, sc, is_goal);
+    h = successor_goal_h<SC>(M, Sq->goal, bfs, grid, sq, sc, is_goal, sn, cs);
 }
 
 // Successor role of k_pipe_configs: the blocks behind the cfg_blocks collision blocks, one thread per edge.  An edge whose
@@ -402,7 +467,8 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
                                                     int* __restrict__ succ_coord, const SmplxSpaceDev* const* __restrict__ stab,
                                                     const unsigned short* __restrict__ state_q, bool want_id,
                                                     unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal,
-                                                    unsigned char* smem, int nprims, int nvars)
+                                                    unsigned char* smem, int nprims, int nvars,
+                                                    const double* __restrict__ Q, const double* __restrict__ trig)
 {
     const long long tid = (long long)((int)blockIdx.x - cfg_blocks) * BLOCK + threadIdx.x;
     // as in the collision blocks: the flag (and, per-robot build, the joint values) are fetched BEFORE the model is staged
@@ -412,6 +478,16 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
     if (live) {
 #pragma unroll
         for (int v = 0; v < CM_NV; ++v) qv[v] = out_q[tid * CM_NV + v];
+    }
+    // ... and with them the parent's joint values and its row of normalised sines and cosines: a variable the primitive
+    // leaves alone (d == 0: sq[v] has the parent's bits) takes the row's pair
+    constexpr bool SC = CM_PARENT_TRIG && CM_TRIG_PLANNING != 0;
+    double pq[CM_NV], prow[2 * CM_NV];
+    if (SC && live) {
+        const long long sp = tid / nprims;
+#pragma unroll
+        for (int v = 0; v < CM_NV; ++v) pq[v] = Q[sp * CM_NV + v];
+        trig_row_load<true>(trig, sp, prow);
     }
 #endif
     const ModelLds Mv = setup_model_only(S, smem);
@@ -429,6 +505,13 @@ __device__ __forceinline__ void pipe_successor_role(const SmplxSpaceDev* __restr
 #endif
     int h, id;
     bool is_goal;
+#ifdef SMPLX_CONST_MODEL
+    if constexpr (SC) {
+        double sn[CM_NV], cs[CM_NV];
+        parent_trig<CM_TRIG_PLANNING, true>(qv, pq, prow, sn, cs);
+        pipe_successor<true>(M, Sq, grid, sq, succ_coord + tid * nv, want_id, h, id, is_goal, sn, cs);
+    } else
+#endif
     pipe_successor(M, Sq, grid, sq, succ_coord + tid * nv, want_id, h, id, is_goal);
     succ_eval[tid] = (unsigned long long)(unsigned int)h | ((unsigned long long)(unsigned int)id << 32);   // one 8-byte store
     succ_goal[tid] = is_goal ? 1 : 0;
@@ -443,14 +526,14 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
                const unsigned char* __restrict__ out_flags, int* __restrict__ succ_coord,
                const SmplxSpaceDev* const* __restrict__ stab, const unsigned short* __restrict__ state_q, int want_id,
                unsigned long long* __restrict__ succ_eval, unsigned char* __restrict__ succ_goal, int nprims, int nvars,
-               const unsigned char* __restrict__ blob, int blob_bytes)
+               const unsigned char* __restrict__ blob, int blob_bytes, const double* __restrict__ trig)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     // the grid is cfg_blocks collision blocks, dispatched first (they hold the long waves), then one successor thread
     // per edge in blocks of their own
     if ((int)blockIdx.x >= cfg_blocks) {
         pipe_successor_role(S, B, cfg_blocks, out_flags, out_q, succ_coord, stab, state_q, want_id != 0, succ_eval, succ_goal, smem,
-                            nprims, nvars);
+                            nprims, nvars, Q, trig);
         return;
     }
     // the model image is known from the arguments: its first pieces travel beside the shard counters
@@ -493,13 +576,16 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
         const long long edge = (long long)(it & 0xFFFFFFFFull);
         const int wp = (int)((it >> 32) & 0xFFFF);
         const int W = (int)(it >> 48);
-        double qs[CM_NV], qf[CM_NV];
+        // ... and so is the parent's row of sines and cosines (sphere_checks.h parent_trig)
+        constexpr bool SC = CM_PARENT_TRIG;
+        double qs[CM_NV], qf[CM_NV], prow[2 * CM_NV];
         if (is_state || is_item) {
             const long long si = is_state ? i : edge / nprims;
             const double* ps = Q + si * nv;
             const double* pf = is_state ? ps : out_q + edge * nv;
 #pragma unroll
             for (int v = 0; v < nv; ++v) { qs[v] = ps[v]; qf[v] = pf[v]; }
+            if constexpr (SC) trig_row_load<false>(trig, si, prow);
         }
         ModelLds Mv;
         ThreadLds L = setup_lds(S, smem, &Mv, BLOCK, !RS, blob, blob_bytes, fetched);
@@ -510,6 +596,7 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
         e.start = nullptr; e.finish = nullptr;   // config_valid_staged never dereferences them
         e.alpha = is_state ? 0.0 : (double)wp * (1.0 / (double)(W - 1));
         int lk = 0;
+        double qc[CM_NV];
 #ifndef ABL_NO_FK
 #pragma unroll
         for (int v = 0; v < nv; ++v) {   // stage_config
@@ -517,9 +604,19 @@ k_pipe_configs(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q
             double q = sv;
             if (e.alpha != 0.0) q = sv + e.alpha * edge_diff(M, v, sv, qf[v]);
             lds_d(L, L.q_base + v) = q;
+            qc[v] = q;
         }
 #endif
-        const bool ok = config_valid_staged<RS>(M, L, grid, e, lk);
+        bool ok;
+        if constexpr (SC) {
+            // a state item changes nothing and evaluates nothing; a waypoint evaluates the one or two variables its
+            // primitive moves (a snap: as many as it moves)
+            double sn[CM_NV], cs[CM_NV];
+            parent_trig<CM_TRIG_COLLISION, false>(qc, qs, prow, sn, cs);
+            ok = config_valid_staged<RS, true>(M, L, grid, e, lk, sn, cs);
+        } else {
+            ok = config_valid_staged<RS>(M, L, grid, e, lk);
+        }
         if (is_state) {
             state_lookups[i] = lk;
             if (!ok) state_bad[i] = 1;
