@@ -617,6 +617,26 @@ class Space:
         lib().smplx_test_set_pipe_prep.argtypes = [C.c_void_p, C.c_int]
         _chk(lib().smplx_test_set_pipe_prep(self.h, 1 if on else 0))
 
+    def set_one_launch(self, mode):
+        """Test hook (csrc/test_hooks.h): which pipeline steps run as the one launch k_step_block: -1 the rule, 0 never,
+        1 whenever the kernel can run at all (a step that then cannot take it raises)."""
+        lib().smplx_test_set_one_launch.argtypes = [C.c_void_p, C.c_int]
+        _chk(lib().smplx_test_set_one_launch(self.h, int(mode)))
+
+    def one_launch_steps(self):
+        """Test hook: steps of this space that took k_step_block so far."""
+        lib().smplx_test_one_launch_steps.argtypes = [C.c_void_p]
+        lib().smplx_test_one_launch_steps.restype = C.c_longlong
+        return int(lib().smplx_test_one_launch_steps(self.h))
+
+    def step_counters_zero(self, stream=None):
+        """Test hook: waits for `stream` and tells whether the space's step counters of that stream are all-zero."""
+        lib().smplx_test_step_counters_zero.argtypes = [C.c_void_p, C.c_void_p]
+        r = lib().smplx_test_step_counters_zero(self.h, C.c_void_p(stream))
+        if r < 0:
+            _chk(r)
+        return r == 1
+
     def set_search_capacity(self, states):
         """Test hook (csrc/test_hooks.h): first capacity of the device search's buffers."""
         lib().smplx_test_set_search_capacity.argtypes = [C.c_void_p, C.c_int]

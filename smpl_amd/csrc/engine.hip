@@ -306,6 +306,9 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
     s->lds_nroot = s->ks.specialized ? 0 : s->model.dev.nroot;
     s->lds_bytes = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
     s->lds_bytes_valid = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->ks.specialized ? 0 : s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
+    s->step.one_launch_lds = smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->ks.specialized ? 0 : s->model.dev.nslots, s->model.dev.nvars,
+                                               s->model.dev.stack_bytes, SMPLX_STEP_BLOCK);
+    s->step.one_launch_blocks = step_block_resident(s, s->step.one_launch_lds, &s->step.one_launch_per_cu);
     if (s->lds_bytes > 160 * 1024) { smplx_space_destroy(s); return set_error(SMPLX_E_LIMIT, "model needs more LDS per block than a CU has (160 KB)"); }
     if ((e = hipEventCreateWithFlags(&s->batch.done, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipMalloc((void**)&s->d_space, sizeof(SmplxSpaceDev))) != hipSuccess) return bail(e, "hipMalloc space");
@@ -382,6 +385,29 @@ int smplx_test_set_pipe_prep(smplx_space* s, int on)
     if (!s) return set_error(SMPLX_E_ARG, "null space");
     s->step.pipe_prep = on != 0;
     return SMPLX_OK;
+}
+
+int smplx_test_set_one_launch(smplx_space* s, int mode)
+{
+    if (!s || mode < -1 || mode > 1) return set_error(SMPLX_E_ARG, "bad argument");
+    s->step.one_launch = mode;
+    return SMPLX_OK;
+}
+
+long long smplx_test_one_launch_steps(const smplx_space* s) { return s ? (long long)s->step.one_launch_steps : -1; }
+
+int smplx_test_step_counters_zero(smplx_space* s, void* stream)
+{
+    if (!s) return set_error(SMPLX_E_ARG, "null space");
+    for (StepLaunch::WorkCounters& w : s->step.work_counters) {
+        if (w.stream != (hipStream_t)stream) continue;
+        std::vector<int32_t> h(SMPLX_WORK_COUNTER_BYTES / sizeof(int32_t));
+        HIP_TRY(hipStreamSynchronize(w.stream));
+        HIP_TRY(hipMemcpy(h.data(), w.p, SMPLX_WORK_COUNTER_BYTES, hipMemcpyDeviceToHost));
+        for (int32_t v : h) if (v != 0) return 0;
+        return 1;
+    }
+    return set_error(SMPLX_E_ARG, "no step has run on this stream");
 }
 
 int smplx_test_set_search_helper(smplx_space* s, int on)

@@ -10,6 +10,15 @@
 
 #define SMPLX_BLOCK 128          // 2 waves; per-thread LDS scratch keeps ~4 blocks per CU resident
 #define SMPLX_SETUP_BLOCK (SMPLX_BLOCK + 64)   // threads of a k_pipe_setup block: the edge threads and the goal-distance wave
+#define SMPLX_STEP_BLOCK SMPLX_SETUP_BLOCK      // threads of a k_step_block block: 128 edge lanes and the goal-distance wave
+#define SMPLX_STEP_STATES 16                    // most states whose edges one k_step_block block may hold (smplx_step_states)
+// k_step_block's part of a stream's counter set (ints; StepLaunch::WorkCounters): behind the pipeline's 2 KB, the claim
+// counters of the compact stream -- region A and region B of each shard on a 128-byte line of its own -- then the overflow
+// flag, the count of finished shards and, per shard, of finished blocks (a line each)
+#define SMPLX_STEP_CTR_BASE 512
+#define SMPLX_STEP_CTR_OVERFLOW (SMPLX_STEP_CTR_BASE + 64 * SMPLX_CMP_SHARDS)
+#define SMPLX_STEP_CTR_DONE (SMPLX_STEP_CTR_OVERFLOW + 32)
+#define SMPLX_WORK_COUNTER_BYTES 16384
 #define SMPLX_SEARCH_STATIC_LDS (44 * 1024)   // static LDS of k_search (2 x ExpandLds + SearchLds + header and primitives copies), an upper bound
 #define SMPLX_GLOBAL_AS __attribute__((address_space(1)))   // device code: a pointer known to be device memory (model_lds.h as_global)
 #define SMPLX_TALLIES 6           // per-block tallies (tally_block)     // per-thread DFS stack (node indices, one byte each)
@@ -29,13 +38,16 @@ static inline size_t smplx_lds_bytes(size_t blob_bytes, int nroot, int nslots, i
     return smplx_lds_bytes_n(blob_bytes, nroot, nslots, nvars, stack_bytes, SMPLX_BLOCK);
 }
 
+// most states that 128 consecutive edges of the (state, primitive) grid belong to
+static inline int smplx_step_states(int nprims) { return (SMPLX_BLOCK - 2 + nprims) / nprims + 1; }
+
 // The kernels that have a per-robot build, stated once as X(id, kernel): enum KernelId (K_<id>, specialize.h), the names
 // asked of the per-robot code object and the generic kernels beside them (specialize.cpp) all come from this list.
 #define SMPLX_PER_ROBOT_KERNELS(X) \
     X(STATE_PREP, k_state_prep) X(EXPAND, k_expand) X(PIPE_PREP, k_pipe_prep) X(PIPE_SETUP, k_pipe_setup) \
     X(PIPE_CONFIGS, k_pipe_configs) X(PIPE_FINISH, k_pipe_finish) X(SMALL_BATCH, k_small_batch) X(EDGE_VALID, k_edge_valid) \
     X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
-    X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose)
+    X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
@@ -71,6 +83,10 @@ __global__ void k_pipe_finish(const SmplxSpaceDev* S, const double* Q, int B, co
                          const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* out_id, SmplxCompactDev cmp,
                               const unsigned long long* succ_eval, const unsigned char* succ_goal, const int* succ_coord,
                               int* work_count, int nprims, int nvars);
+__global__ void k_step_block(const SmplxSpaceDev* S, const double* Q, int B, unsigned char* out_flags, int* out_coord,
+                             double* out_q, int* out_h, int* out_cost, int* out_lookups, unsigned long long* counters,
+                             const SmplxSpaceDev* const* stab, const unsigned short* state_q, int* out_id, SmplxCompactDev cmp,
+                             int* step_ctr, int nprims, int nvars, const unsigned char* blob, int blob_bytes);
 __global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist_out,
                               unsigned char* state_bad_out, int* state_lookups_out, unsigned char* out_flags, int* out_coord,
                               double* out_q, int* out_h, int* out_cost, int* out_lookups,

@@ -13,6 +13,8 @@
 //                       k_pipe_finish (three launches; k_pipe_prep in front of them in the four-launch mode of large
 //                       batches).  Also the fused pair k_state_prep + k_expand, one thread per (state, primitive)
 //                       (manip_lattice.cpp:254-305 loop body), which the pipeline is checked against
+//   step_block.h        k_step_block: the same step in ONE launch for a batch whose blocks are resident in one round;
+//                       each block owns 128 edges and keeps everything between its phases in LDS
 //   small_batch.h       k_small_batch: one block per state, and the lane functions k_search is built from
 //   query_kernels.h     k_edge_valid, k_state_valid, k_heuristic, k_planning_pose, k_sphere_positions,
 //                       k_attached_positions, k_bfs_metric: batch queries of the C-ABI
@@ -38,6 +40,7 @@
 #include "config_checks.h"
 #include "lattice_steps.h"
 #include "step_kernels.h"
+#include "step_block.h"
 #include "small_batch.h"
 #include "query_kernels.h"
 #include "bfs_kernels.h"

@@ -126,9 +126,17 @@ struct StepLaunch {
     int work_list_items = 0;   // > 0: test hook -- a work list this small, so that the deferred pass is exercised
     bool pipe_prep = false;    // test hook: k_pipe_prep in a launch of its own in front of k_pipe_setup
     int three_launch_blocks = 0;   // largest k_pipe_setup grid (edge blocks) that runs the three-launch step; 0: not asked yet
-    // Work-list counters of the pipeline (8 shard counters + deferred count, one 128-byte line each): one set per stream
-    // the space has launched a step on.  A set is all-zero whenever no step is in flight on its stream: k_pipe_finish
-    // clears it behind its last reader.  dirty: a launch sequence on it failed part-way, it is cleared before its next use.
+    int one_launch = -1;       // test hook: -1 the rule (expand_path), 0 never k_step_block, 1 whenever it can run at all
+    size_t one_launch_lds = 0; // dynamic LDS of a k_step_block block
+    int one_launch_per_cu = 0; // blocks of k_step_block that share a CU (occupancy query)
+    int one_launch_blocks = 0; // blocks of k_step_block resident in one round (occupancy query x CUs); 0: it cannot run
+    int64_t one_launch_steps = 0;   // steps that took k_step_block
+    // Counters of a step, SMPLX_WORK_COUNTER_BYTES: the pipeline's work-list counters (8 shard counters + deferred count, one
+    // 128-byte line each) and, behind them, what k_step_block keeps (kernels.h SMPLX_STEP_CTR_*: the claim counters of the
+    // compact stream, the overflow flag, the count of finished blocks).  One set per stream the space has launched a step
+    // on.  A set is all-zero whenever no step is in flight on its stream: k_pipe_finish clears its part behind its last
+    // reader, the last block of k_step_block its own.  dirty: a launch sequence on it failed part-way, it is cleared before
+    // its next use.
     struct WorkCounters { hipStream_t stream; int32_t* p; bool dirty; };
     std::vector<WorkCounters> work_counters;
     // optional per-kernel timing of expand launches (bench.py roofline): 3 events per launch

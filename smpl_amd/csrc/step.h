@@ -115,7 +115,7 @@ struct ExpandArgs {
     bool force_pipeline = false;                // no single launch with copies
 };
 
-enum class ExpandPath { SmallZeroCopy, Small, Fused, Pipeline };
+enum class ExpandPath { SmallZeroCopy, Small, Fused, Pipeline, OneLaunch };
 
 inline size_t small_lds_bytes(const smplx_space* s)
 {
@@ -127,6 +127,14 @@ inline size_t small_lds_bytes(const smplx_space* s)
 // largest batch whose parents and results may stay in pinned host memory (0: never), and force_pipeline, which rules out
 // the single launch with copies.  Armed profile events rule out the zero-copy launch, an event triple left for this
 // launch the single launch altogether; the fused mode takes precedence over the pipeline.
+// A pipeline step runs as the one launch k_step_block (step_block.h) when the space runs per-robot kernels, neither
+// pipeline test hook is set, no event triple is armed for this launch (the triple brackets k_pipe_configs) and its blocks
+// are resident in one round (step_block_resident) with four blocks sharing a CU (three waves per SIMD: the geometry it was
+// measured at -- arm7; dual14 keeps two blocks a CU, the mixed-kinds robot one, neither was timed and both stay on the
+// pipeline); beyond one round the step is bound by throughput and the pipeline stays, as three_launch_blocks decides for
+// its goal-distance wave.  The generic k_step_block has not been measured against the
+// generic pipeline (its k_pipe_configs allows two waves per SIMD, so a batch of the benchmark's size is not resident).
+// StepLaunch::one_launch (test hook): 0 never, 1 whenever the kernel can run at all, resident and per-robot or not.
 ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool force_pipeline)
 {
     const bool small = !s->step.fused_mode && B <= s->small.batch_max && smplx_small_block(s->M) <= 512 &&
@@ -134,17 +142,40 @@ ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool forc
                        s->step.prof_used + 3 > s->step.prof_events.size();
     if (small && B <= zero_copy_max && s->step.prof_events.empty()) return ExpandPath::SmallZeroCopy;
     if (small && !force_pipeline) return ExpandPath::Small;
-    return s->step.fused_mode ? ExpandPath::Fused : ExpandPath::Pipeline;
+    if (s->step.fused_mode) return ExpandPath::Fused;
+    const bool can_run = s->step.one_launch_blocks > 0 && !s->step.pipe_prep && s->step.work_list_items == 0 &&
+                         s->step.prof_used + 3 > s->step.prof_events.size();
+    const bool by_rule = s->ks.specialized && s->step.one_launch_per_cu >= 4 &&
+                         blocks_for((long long)B * s->M, SMPLX_BLOCK) <= s->step.one_launch_blocks;
+    if (can_run && s->step.one_launch != 0 && (s->step.one_launch == 1 || by_rule)) return ExpandPath::OneLaunch;
+    return ExpandPath::Pipeline;
 }
 
-// the work-list counters of `stream`: allocated and zeroed, once and synchronously, the first time the stream is seen
+// Blocks of k_step_block that are resident at once: the occupancy of the kernel this space would launch, at its block
+// size and dynamic LDS, times the CU count.  0: the kernel cannot run for this space (a block would hold the edges of more
+// than SMPLX_STEP_STATES states, or does not fit a CU).  Asked once, when the space is created.
+int step_block_resident(const smplx_space* s, size_t lds, int* blocks_per_cu)
+{
+    *blocks_per_cu = 0;
+    if (smplx_step_states(s->M) > SMPLX_STEP_STATES) return 0;
+    int per_cu = 0, cus = 0;
+    const smplx::KernelRef& k = s->ks.k[smplx::K_STEP_BLOCK];
+    const hipError_t e = k.fn ? hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, SMPLX_STEP_BLOCK, lds)
+                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.generic, SMPLX_STEP_BLOCK, lds);
+    if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device) != hipSuccess || cus <= 0) cus = 256;
+    *blocks_per_cu = per_cu > 0 ? per_cu : 0;
+    return per_cu > 0 ? per_cu * cus : 0;
+}
+
+// the step counters of `stream` (StepLaunch::WorkCounters): allocated and zeroed, once and synchronously, the first time the stream is seen
 int work_counters_for(smplx_space* s, hipStream_t stream, StepLaunch::WorkCounters** out)
 {
     for (StepLaunch::WorkCounters& w : s->step.work_counters)
         if (w.stream == stream) { *out = &w; return SMPLX_OK; }
     int32_t* p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, 2048));
-    hipError_t e = hipMemsetAsync(p, 0, 2048, stream);
+    HIP_TRY(hipMalloc((void**)&p, SMPLX_WORK_COUNTER_BYTES));
+    hipError_t e = hipMemsetAsync(p, 0, SMPLX_WORK_COUNTER_BYTES, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) { (void)hipFree(p); return set_error(SMPLX_E_HIP, std::string("work-list counters: ") + hipGetErrorString(e)); }
     s->step.work_counters.push_back({stream, p, false});
@@ -160,8 +191,11 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     SmplxCompactDev cmp;
     std::memset(&cmp, 0, sizeof(cmp));
     if (a.k5 && a.k5->cmp) cmp = *a.k5->cmp;
-    // (the compact stream is produced by k_pipe_finish)
+    // (the compact stream is produced by k_pipe_finish or k_step_block: no single small launch when it is asked for)
     const ExpandPath path = expand_path(s, B, a.zero_copy ? B : 0, a.force_pipeline || cmp.rec_a);
+    if (s->step.one_launch == 1 && path == ExpandPath::Pipeline)
+        return set_error(SMPLX_E_ARG, "the one-launch step was asked for (smplx_test_set_one_launch) but cannot run: a pipeline test hook or a "
+                                      "profile-event triple is set, or a block of k_step_block does not fit this model");
     const int32_t* ins_items = a.k5 && s->dt.d_table ? a.k5->items : nullptr;
     const int n_ins = ins_items ? a.k5->n_items : 0;
     if (s->step.work_list_items > 0) k.capacity = s->step.work_list_items;   // test hook: almost every edge overflows into the deferred pass
@@ -195,12 +229,29 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
                            k.goal_dist, k.state_bad, k.state_lookups, a.flags, a.coord, a.sq, a.h, a.cost, a.lookups,
                            a.counters, (const int*)nullptr, a.stab, a.state_q);
         if (ev) (void)hipEventRecord(ev[2], a.stream);
+    } else if (path == ExpandPath::OneLaunch) {
+        // the whole step in one launch (step_block.h): block b owns the edges block b of k_pipe_finish owns
+        ++s->small.pipe_launches;
+        StepLaunch::WorkCounters* wc = nullptr;
+        if (int e = work_counters_for(s, a.stream, &wc)) return e;
+        if (wc->dirty) HIP_TRY(hipMemsetAsync(wc->p, 0, SMPLX_WORK_COUNTER_BYTES, a.stream));
+        wc->dirty = true;   // until the launch is in the stream: its last block leaves the set zeroed
+        // K5 inserts: the table must be complete before the same launch probes it
+        if (n_ins > 0) {
+            hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, a.stream, s->d_space, a.stab, ins_items, n_ins, s->N);
+        }
+        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space) + offsetof(SmplxSpaceDev, model_blob);
+        KLAUNCH(s, K_STEP_BLOCK, k_step_block, dim3(be), dim3(SMPLX_STEP_BLOCK), s->step.one_launch_lds, a.stream, s->d_space, a.q, B,
+                           a.flags, a.coord, a.sq, a.h, a.cost, a.lookups, a.counters, a.stab, a.state_q, d_id, cmp, wc->p,
+                           s->M, s->N, blob, (int)s->blob_bytes);
+        wc->dirty = false;
+        ++s->step.one_launch_steps;
     } else {
         const size_t lm = s->blob_bytes;
         ++s->small.pipe_launches;
         StepLaunch::WorkCounters* wc = nullptr;
         if (int e = work_counters_for(s, a.stream, &wc)) return e;
-        if (wc->dirty) HIP_TRY(hipMemsetAsync(wc->p, 0, 2048, a.stream));
+        if (wc->dirty) HIP_TRY(hipMemsetAsync(wc->p, 0, SMPLX_WORK_COUNTER_BYTES, a.stream));
         wc->dirty = true;   // until the whole sequence is in the stream: k_pipe_finish leaves the set zeroed
         k.work_count = wc->p;
         // Every kernel of the step takes nprims (s->M) and nvars (s->N) as arguments: a thread's state index is tid / nprims,

@@ -1,7 +1,9 @@
 // smpl_amd/csrc/step_kernels.h -- the kernels of a frontier step.
 // Owns: the fused pair k_state_prep + k_expand (one thread walks a whole edge: expand_edge) with tally_block, and the
 // waypoint-parallel pipeline, which is the default: k_pipe_setup, k_pipe_configs, k_pipe_finish, with k_pipe_prep in
-// front for the four-launch mode, and their helpers (pipe_edge_values, pipe_successor, pipe_successor_role).
+// front for the four-launch mode, and their helpers (pipe_edge_values, pipe_successor, pipe_successor_role).  The one-launch
+// form of the pipeline for a batch that is resident in one round, k_step_block, is in step_block.h and built from the same
+// helpers.
 // Restates: manip_lattice.cpp:254-305, 1471-1535 (the GetSuccs loop body); manip_lattice_action_space.cpp:385-397;
 // collision_space.cpp:561-577.
 #pragma once
@@ -37,11 +39,12 @@ k_state_prep(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
 }
 
 // per-block tallies without atomics: block b owns counters[4*b .. 4*b+3] (launches on one stream serialise,
-// so a plain read-modify-write is safe); the host sums the blocks (smplx_counters_read)
+// so a plain read-modify-write is safe); the host sums the blocks (smplx_counters_read).  WAVES: waves of the block.
+template <int WAVES = BLOCK / 64>
 __device__ __forceinline__ void tally_block(unsigned long long* __restrict__ counters, int ev, int va, int lk, int pf,
                                             int cfgs, int slk)
 {
-    __shared__ int t_acc[BLOCK / 64][SMPLX_TALLIES];
+    __shared__ int t_acc[WAVES][SMPLX_TALLIES];
     const int wv = threadIdx.x >> 6;
     for (int off = 32; off > 0; off >>= 1) {
         lk += __shfl_down(lk, off); pf += __shfl_down(pf, off); cfgs += __shfl_down(cfgs, off); slk += __shfl_down(slk, off);
@@ -53,7 +56,7 @@ __device__ __forceinline__ void tally_block(unsigned long long* __restrict__ cou
     if (threadIdx.x < SMPLX_TALLIES) {
         int v = 0;
 #pragma unroll
-        for (int k = 0; k < BLOCK / 64; ++k) v += t_acc[k][threadIdx.x];
+        for (int k = 0; k < WAVES; ++k) v += t_acc[k][threadIdx.x];
         counters[(size_t)blockIdx.x * SMPLX_TALLIES + threadIdx.x] += (unsigned long long)v;
     }
 }

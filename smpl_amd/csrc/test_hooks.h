@@ -19,6 +19,18 @@ int smplx_test_set_work_list_items(smplx_space* s, int items);
  * the chip in one round (four beyond that).  Same results, bit for bit. */
 int smplx_test_set_pipe_prep(smplx_space* s, int on);
 
+/* Which pipeline steps run as the one launch k_step_block (step_block.h): -1 the rule (per-robot kernels, no pipeline test
+ * hook, no profile-event triple armed, every block resident in one round), 0 never, 1 whenever the kernel can run at all --
+ * a step that then cannot take it fails with an error instead of running the pipeline.  Same results, bit for bit. */
+int smplx_test_set_one_launch(smplx_space* s, int mode);
+
+/* Steps of this space that took k_step_block so far. */
+long long smplx_test_one_launch_steps(const smplx_space* s);
+
+/* Waits for `stream` and returns 1 if the space's step counters of that stream are all-zero, as they must be whenever no step
+ * is in flight on it, 0 if not; an error (negative) if no step has run on the stream. */
+int smplx_test_step_counters_zero(smplx_space* s, void* stream);
+
 /* The heap primitives of the device-resident search (search_kernel.h) driven by an op sequence in the language of
  * oracle/heap_ref_driver.cpp (pairs code, key; see k_heap_ops): top_after[i] = element at the top after op i, -1 when empty.
  * lds_entries = how many leading heap entries live in LDS (the rest in HBM), 1 .. 4096. */
