@@ -400,7 +400,9 @@ int smplx_plan(smplx_space* s, const smplx_search_params* p, int32_t* path_ids, 
  * [3..9] 10-ns ticks the search wave of the workgroup spent, last search: (idle), select + pop, until the waypoint lanes'
  * round has closed (ancestor prefetch, preparing the next round, waiting), getOrCreateState, relaxation + pushes, epsilon
  * steps (reorder), load / store of the launch state; [10] states on the device, [11] heap entries cached in LDS;
- * [12] evaluation rounds opened on a guess of the next pop, [13] guesses the pop confirmed; [14..15] 0 */
+ * [12] evaluation rounds opened on a guess of the next pop, [13] guesses the pop confirmed; [14] empty state
+ * tables the search allocated and filled from its states' coordinates (the first one, and one each time the states outgrew
+ * it), [15] times the host loop's device table was outgrown and built again */
 int smplx_search_counters(const smplx_space* s, int64_t out[16]);
 /* nq independent queries (each its own smplx_space: goal, BFS grid, state table) on one GPU.  Device-resident search
  * (default): one workgroup per query, all in ONE launch when the queries share grid, robot and primitives.  Host-driven

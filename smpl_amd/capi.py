@@ -152,6 +152,18 @@ def rpy_angle(a, b):
     return t.value
 
 
+def table_probe(nvars, slots, one_home, inserted, queries):
+    """Test hook (csrc/test_hooks.h smplx_test_table_probe): the device search's state-table probe on an empty table of
+    `slots` slots.  Returns (what the probe found for each inserted coordinate before it was stored, id of each query)."""
+    a = np.ascontiguousarray(inserted, dtype=np.int32).reshape(-1, nvars)
+    q = np.ascontiguousarray(queries, dtype=np.int32).reshape(-1, nvars)
+    found = np.zeros(a.shape[0], np.int32); ids = np.zeros(q.shape[0], np.int32)
+    lib().smplx_test_table_probe.argtypes = [C.c_int, C.c_int, C.c_int, _ip, C.c_int, _ip, C.c_int, _ip, _ip]
+    _chk(lib().smplx_test_table_probe(nvars, slots, int(bool(one_home)), _p(a, _ip), a.shape[0], _p(q, _ip), q.shape[0],
+                                      _p(found, _ip), _p(ids, _ip)))
+    return found, ids
+
+
 class Grid:
     """OccupancyGrid, lookup side, resident in HBM (16-bit squared distances in 4x4x4 bricks)."""
 
@@ -603,7 +615,7 @@ class Space:
         lib().smplx_search_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         _chk(lib().smplx_search_counters(self.h, out))
         names = ["searches", "grows", "dup_pushes", "t_idle", "t_select_pop", "t_evaluate", "t_commit", "t_relax", "t_reorder", "t_launch_io",
-                 "device_states", "heap_cache_entries", "spec_rounds", "spec_hits"]
+                 "device_states", "heap_cache_entries", "spec_rounds", "spec_hits", "table_allocs", "table_regrows"]
         return {n: int(out[i]) for i, n in enumerate(names)}
 
     def set_search_helper(self, on):

@@ -49,6 +49,7 @@ int table_grow_if_needed(smplx_space* s)
     if (!s->dt.d_table || s->dt.count * 2 <= s->dt.cap) return SMPLX_OK;
     size_t cap = s->dt.cap;
     while (s->dt.count * 2 > cap) cap *= 4;
+    ++s->dt.regrows;
     return table_realloc(s, cap);
 }
 

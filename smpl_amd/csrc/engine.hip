@@ -435,6 +435,8 @@ int smplx_search_counters(const smplx_space* s, int64_t out[16])
     out[11] = search_heap_cache_entries(s, nullptr);
     out[12] = D.ticks[7] >> 32;            // evaluation rounds opened on a guess of the next pop
     out[13] = D.ticks[7] & 0xFFFFFFFFll;   // ... that the pop confirmed
+    out[14] = D.table_allocs;              // empty state tables the search allocated and filled from the states' coordinates
+    out[15] = s->dt.regrows;               // times the host loop's device table was outgrown and built again
     return SMPLX_OK;
 }
 
@@ -457,6 +459,36 @@ int smplx_test_heap_ops(const int32_t* ops, int nops, int lds_entries, int32_t* 
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(top_after, d_top.p, sizeof(int32_t) * (size_t)nops, hipMemcpyDeviceToHost));
+    return SMPLX_OK;
+}
+
+int smplx_test_table_probe(int nvars, int slots, int one_home, const int32_t* inserted, int n_inserted, const int32_t* queries, int n_queries,
+                           int32_t* found_at_insert, int32_t* ids)
+{
+    if (!inserted || !queries || !found_at_insert || !ids || nvars < 1 || nvars > SMPLX_MAX_VARS || slots < 2 || slots > 4096 ||
+        (slots & (slots - 1)) != 0 || n_inserted < 1 || n_inserted >= slots || n_queries < 1 || n_queries > 65536)
+        return set_error(SMPLX_E_ARG, "bad argument (slots: a power of two up to 4096 with room for an empty slot)");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_error(SMPLX_E_HIP, "no HIP device");
+    const int stride = smplx_table_stride(nvars);
+    DevBuf<int32_t> d_table, d_in, d_out;
+    int e;
+    const size_t n_max = (size_t)std::max(n_inserted, n_queries);
+    if ((e = d_table.reserve((size_t)slots * stride))) return e;
+    if ((e = d_in.reserve(n_max * nvars))) return e;
+    if ((e = d_out.reserve(n_max))) return e;
+    HIP_TRY(hipMemset(d_table.p, 0, sizeof(int32_t) * (size_t)slots * stride));
+    SmplxTableDev T;
+    T.slots = d_table.p; T.mask = (uint32_t)(slots - 1); T.stride = stride; T.pad = 0;
+    for (int pass = 0; pass < 2; ++pass) {     // the inserts, then the lookups in a launch of their own
+        const int32_t* src = pass == 0 ? inserted : queries;
+        const int n = pass == 0 ? n_inserted : n_queries;
+        HIP_TRY(hipMemcpy(d_in.p, src, sizeof(int32_t) * (size_t)n * nvars, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_table_probe_ops, dim3(1), dim3(64), 0, 0, T, (const int*)d_in.p, n, nvars, one_home ? 1 : 0, pass == 0 ? 1 : 0, d_out.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(pass == 0 ? found_at_insert : ids, d_out.p, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    }
     return SMPLX_OK;
 }
 

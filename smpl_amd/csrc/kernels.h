@@ -95,6 +95,7 @@ __global__ void k_small_batch(const SmplxSpaceDev* S, const double* Q, int B, do
                               int n_ins);
 __global__ void k_search(const SmplxSpaceDev* const* stab, int max_steps, int lh, int* status_out, long long pre_ticks);
 __global__ void k_search_table_fill(const SmplxSpaceDev* Sq, const int* coord, int first, int n, int nvars);
+__global__ void k_table_probe_ops(SmplxTableDev T, const int* coords, int n, int nv, int one_home, int insert, int* out);
 __global__ void k_heap_ops(const int* ops, int nops, int lh, unsigned long long* heap_hbm, SmplxSState* st, int* top_after);
 __global__ void k_edge_valid(const SmplxSpaceDev* S, const double* Aq, const double* Bq, int n, unsigned char* out,
                              int* out_lookups, int* out_waypoints);

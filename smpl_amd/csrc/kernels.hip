@@ -19,7 +19,7 @@
 //   query_kernels.h     k_edge_valid, k_state_valid, k_heuristic, k_planning_pose, k_sphere_positions,
 //                       k_attached_positions, k_bfs_metric: batch queries of the C-ABI
 //   bfs_kernels.h       k_bfs_*: label-correcting 26-connected BFS over 8x8x8 bricks (bfs3d.cpp:507-547)
-//   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query; k_search_table_fill, k_heap_ops
+//   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query; k_search_table_fill, k_heap_ops, k_table_probe_ops
 //
 // No MFMA: the path is integer/byte gathers from the voxel grid plus a short serial FK chain in fp64.
 // The sphere trees are staged in LDS; per-thread scratch (tree-root positions, saved link transforms,

@@ -129,12 +129,14 @@ int search_reserve(smplx_space* s, const SearchCaps& want)
         ++D.grows;
     }
     // the state table: at most half full with cap_states states
-    size_t tcap = s->dt.cap ? s->dt.cap : ((size_t)1 << 16);
+    // (test hook: with a first capacity set, the table starts small too, so that it is outgrown and filled again as well)
+    size_t tcap = s->dt.cap ? s->dt.cap : (D.test_capacity > 0 ? (size_t)64 : (size_t)1 << 16);
     while (tcap < 2 * (size_t)c.states) tcap *= 2;
     if (!s->dt.d_table || tcap != s->dt.cap) {
         HIP_TRY(hipStreamSynchronize(s->stream));
         if (int e = table_alloc(s, tcap)) return e;
         D.table_fresh = true;   // empty: every state is inserted again (k_search_table_fill)
+        ++D.table_allocs;
         s->dt.pending_ins.clear();
     }
     if (s->hs.search != D.d_hdr || grow || D.table_fresh) {

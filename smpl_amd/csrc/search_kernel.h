@@ -314,20 +314,26 @@ __device__ __forceinline__ SmplxSState sstate_load(const SMPLX_GLOBAL_AS SmplxSS
 // while the kernel runs, so what it reads is current.  table_probe_start issues the loads of the home slot (they land
 // behind the planning-link FK); table_probe_finish looks at them and walks on if it has to.
 struct TableProbe { int id; unsigned int free_slot; };
-struct TableProbeLoads { sk_int4 w[4]; unsigned int slot; };
-__device__ __forceinline__ void table_slot_load(const SmplxTableDev& T, unsigned int slot, int nv, sk_int4 w[4])
+// A slot's tag and coordinate take (nv + 1 + 3) / 4 words of 16 bytes: SMPLX_TABLE_WORDS for the widest robot.  The loops
+// below run to that bound and stop at the robot's own count, which a per-robot build knows when it compiles, so that the
+// words a robot does not have cost it nothing.
+#define SMPLX_TABLE_WORDS ((SMPLX_MAX_VARS + 1 + 3) / 4)
+static_assert(4 * SMPLX_TABLE_WORDS >= SMPLX_MAX_VARS + 1, "the words of a probe hold the tag and every coordinate of the widest robot");
+static_assert(4 * SMPLX_TABLE_WORDS <= (SMPLX_MAX_VARS + 1 + 7) / 8 * 8, "... and lie inside its slot (smplx_table_stride)");
+struct TableProbeLoads { sk_int4 w[SMPLX_TABLE_WORDS]; unsigned int slot; };
+__device__ __forceinline__ void table_slot_load(const SmplxTableDev& T, unsigned int slot, int nv, sk_int4 w[SMPLX_TABLE_WORDS])
 {
     const SMPLX_GLOBAL_AS sk_int4* sl = (const SMPLX_GLOBAL_AS sk_int4*)(as_global(T.slots) + (size_t)slot * T.stride);
     const int nw = (nv + 1 + 3) / 4;       // 16-byte words that hold the tag and the coordinate (stride is a multiple of 8 ints)
 #pragma unroll
-    for (int k = 0; k < 4; ++k) if (k < nw) w[k] = sl[k];
+    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) if (k < nw) w[k] = sl[k];
 }
-__device__ __forceinline__ bool table_slot_match(const sk_int4 w[4], const LDS_AS int* c, int nv)
+__device__ __forceinline__ bool table_slot_match(const sk_int4 w[SMPLX_TABLE_WORDS], const LDS_AS int* c, int nv)
 {
     const int nw = (nv + 1 + 3) / 4;
     bool same = w[0].x > 0;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) {
         if (k >= nw) continue;
         const int base = 4 * k - 1;        // coordinate index of .x
         if (k > 0 && base < nv) same = same && w[k].x == c[base];
@@ -1232,6 +1238,31 @@ k_search_table_fill(const SmplxSpaceDev* __restrict__ Sq, const int* __restrict_
                 break;
             }
             k = (k + 1) & T.mask;
+        }
+    }
+}
+
+// Parity-test kernel (test_hooks.h): the state-table probe of k_search (table_probe_start / table_probe_finish /
+// table_store_own) on a table of the caller's size.  insert = 1: one lane takes the n coordinates in turn, probes, and stores
+// coordinate i under id i where the probe found none (out[i] = what the probe found, -1 for a new coordinate); insert = 0:
+// every lane looks its share of the n coordinates up (out[i] = id or -1).  one_home: every coordinate's probe starts at
+// slot 0 instead of its hash, so that a lookup walks over every state inserted before the one it looks for.
+extern "C" __global__ void __launch_bounds__(64)
+k_table_probe_ops(SmplxTableDev T, const int* __restrict__ coords, int n, int nv, int one_home, int insert, int* __restrict__ out)
+{
+    __shared__ int cbuf[64][SMPLX_MAX_VARS];
+    const int lane = threadIdx.x;
+    if (insert && lane != 0) return;
+    for (int i = lane; i < n; i += insert ? 1 : 64) {
+        for (int v = 0; v < nv; ++v) cbuf[lane][v] = coords[(size_t)i * nv + v];
+        const LDS_AS int* c = (const LDS_AS int*)cbuf[lane];
+        const unsigned int hash = one_home ? 0u : coord_hash_lds(c, nv);
+        TableProbeLoads ld = table_probe_start(T, nv, hash);
+        const TableProbe pr = table_probe_finish(T, ld, c, nv);
+        out[i] = pr.id;
+        if (insert && pr.id < 0) {
+            table_store_own(T, pr.free_slot, c, nv, i);
+            __threadfence();
         }
     }
 }

@@ -70,6 +70,7 @@ struct FrontierBatch {
 struct DeviceTable {
     int32_t* d_table = nullptr;
     size_t cap = 0, count = 0;
+    int64_t regrows = 0;          // times the table was outgrown (load factor above 1/2) and allocated again, every state re-inserted
     std::vector<int32_t> pending_ins;
     DevBuf<int32_t> b_ins;
     PinBuf<int32_t> p_ins;
@@ -176,6 +177,7 @@ struct DevSearch {
     bool log_on_device = false;          // the expansion log of the last search has not been read back
     int call_number = 0, n_succ_kept = 0;
     int64_t grows = 0, searches = 0, ticks[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t table_allocs = 0;            // state tables the search allocated: each starts empty and is filled by k_search_table_fill
     int dup_pushes = 0;
     int64_t evals_base[3] = {0, 0, 0};   // the header's committed / GPU evaluations and grid lookups when the call began
     int test_capacity = 0;               // test hook: first capacity in states

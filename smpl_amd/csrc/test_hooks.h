@@ -36,8 +36,18 @@ int smplx_test_step_counters_zero(smplx_space* s, void* stream);
  * lds_entries = how many leading heap entries live in LDS (the rest in HBM), 1 .. 4096. */
 int smplx_test_heap_ops(const int32_t* ops, int nops, int lds_entries, int32_t* top_after);
 
+/* The state-table probe of the device-resident search (search_kernel.h table_probe_start / table_probe_finish /
+ * table_store_own, see k_table_probe_ops) on an empty table of `slots` slots (a power of two, more than n_inserted) for
+ * coordinates of nvars ints: `inserted` go in one after the other, coordinate i under id i (found_at_insert[i] = what the
+ * probe found before the store: -1 unless the coordinate was there already), then every row of `queries` is looked up
+ * (ids[i] = id or -1).  one_home = 1: every probe starts at slot 0 instead of the coordinate's hash. */
+int smplx_test_table_probe(int nvars, int slots, int one_home, const int32_t* inserted, int n_inserted, const int32_t* queries, int n_queries,
+                           int32_t* found_at_insert, int32_t* ids);
+
 /* First capacity (states) of the device-resident search's buffers, so that a test can make a search outgrow them
- * (SMPLX_SS_GROW: the host enlarges and launches again); 0 restores the default sizing. */
+ * (SMPLX_SS_GROW: the host enlarges and launches again); 0 restores the default sizing.  A state table that the search
+ * allocates while the hook is set starts at the smallest size that holds this capacity half full (instead of 2^16 slots),
+ * so it is outgrown and filled again along with the buffers. */
 int smplx_test_set_search_capacity(smplx_space* s, int states);
 
 /* on = 0: the device-resident search runs WITHOUT its helper wave (the search wave does the successors' bookkeeping inline,
