@@ -649,6 +649,17 @@ class Space:
             _chk(r)
         return r == 1
 
+    def set_table_slots(self, slots):
+        """Test hook (csrc/test_hooks.h): slots of the first device state table this space allocates (0: the default)."""
+        lib().smplx_test_set_table_slots.argtypes = [C.c_void_p, C.c_int]
+        _chk(lib().smplx_test_set_table_slots(self.h, int(slots)))
+
+    def table_slots(self):
+        """Test hook: slots of the space's device state table now (0 while it has none)."""
+        lib().smplx_test_table_slots.argtypes = [C.c_void_p]
+        lib().smplx_test_table_slots.restype = C.c_longlong
+        return int(lib().smplx_test_table_slots(self.h))
+
     def set_search_capacity(self, states):
         """Test hook (csrc/test_hooks.h): first capacity of the device search's buffers."""
         lib().smplx_test_set_search_capacity.argtypes = [C.c_void_p, C.c_int]

@@ -83,7 +83,7 @@ int table_upload(smplx_space* lead, const std::vector<int32_t>& items, DevBuf<in
 int table_ensure(smplx_space* s)
 {
     if (s->dt.d_table) return SMPLX_OK;
-    size_t cap = (size_t)1 << 18;
+    size_t cap = s->dt.test_slots ? s->dt.test_slots : (size_t)1 << 18;   // (test hook: a table small enough to be dense)
     const size_t nstates = s->lat.h_of_id.size();
     while (nstates * 2 > cap) cap *= 4;
     if (int e = table_realloc(s, cap)) return e;

@@ -410,6 +410,16 @@ int smplx_test_step_counters_zero(smplx_space* s, void* stream)
     return set_error(SMPLX_E_ARG, "no step has run on this stream");
 }
 
+int smplx_test_set_table_slots(smplx_space* s, int slots)
+{
+    if (!s || slots < 0 || (slots != 0 && (slots < 64 || (slots & (slots - 1)) != 0)))
+        return set_error(SMPLX_E_ARG, "slots must be 0 or a power of two of at least 64");
+    s->dt.test_slots = (size_t)slots;
+    return SMPLX_OK;
+}
+
+long long smplx_test_table_slots(const smplx_space* s) { return s ? (long long)(s->dt.d_table ? s->dt.cap : 0) : -1; }
+
 int smplx_test_set_search_helper(smplx_space* s, int on)
 {
     if (!s) return set_error(SMPLX_E_ARG, "null space");

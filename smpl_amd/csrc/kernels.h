@@ -12,12 +12,14 @@
 #define SMPLX_SETUP_BLOCK (SMPLX_BLOCK + 64)   // threads of a k_pipe_setup block: the edge threads and the goal-distance wave
 #define SMPLX_STEP_BLOCK SMPLX_SETUP_BLOCK      // threads of a k_step_block block: 128 edge lanes and the goal-distance wave
 #define SMPLX_STEP_STATES 16                    // most states whose edges one k_step_block block may hold (smplx_step_states)
-// k_step_block's part of a stream's counter set (ints; StepLaunch::WorkCounters): behind the pipeline's 2 KB, the claim
-// counters of the compact stream -- region A and region B of each shard on a 128-byte line of its own -- then the overflow
-// flag, the count of finished shards and, per shard, of finished blocks (a line each)
+// k_step_block's part of a stream's counter set (ints; StepLaunch::WorkCounters): behind the pipeline's 2 KB, one 64-bit claim
+// word per shard of the compact stream on a 128-byte line of its own -- records claimed in region A in bits 0-23, in region
+// B in bits 24-47, blocks of the shard that have claimed in bits 48-63 -- then, on a line of its own, the count of shards
+// whose blocks have all claimed
 #define SMPLX_STEP_CTR_BASE 512
-#define SMPLX_STEP_CTR_OVERFLOW (SMPLX_STEP_CTR_BASE + 64 * SMPLX_CMP_SHARDS)
-#define SMPLX_STEP_CTR_DONE (SMPLX_STEP_CTR_OVERFLOW + 32)
+#define SMPLX_STEP_CTR_DONE (SMPLX_STEP_CTR_BASE + 32 * SMPLX_CMP_SHARDS)
+#define SMPLX_STEP_CLAIM_BITS 24    // bits of a claim word's record fields
+#define SMPLX_STEP_COUNT_BITS 16    // ... and of its block count
 #define SMPLX_WORK_COUNTER_BYTES 16384
 #define SMPLX_SEARCH_STATIC_LDS (44 * 1024)   // static LDS of k_search (2 x ExpandLds + SearchLds + header and primitives copies), an upper bound
 #define SMPLX_GLOBAL_AS __attribute__((address_space(1)))   // device code: a pointer known to be device memory (model_lds.h as_global)
@@ -40,6 +42,13 @@ static inline size_t smplx_lds_bytes(size_t blob_bytes, int nroot, int nslots, i
 
 // most states that 128 consecutive edges of the (state, primitive) grid belong to
 static inline int smplx_step_states(int nprims) { return (SMPLX_BLOCK - 2 + nprims) / nprims + 1; }
+// can a k_step_block grid of `blocks` blocks claim in the packed words: a shard's blocks fit the count field and the records
+// they can hold (SMPLX_BLOCK each) a record field
+static inline bool smplx_step_claim_fits(long long blocks)
+{
+    const long long in_shard = (blocks + SMPLX_CMP_SHARDS - 1) / SMPLX_CMP_SHARDS;
+    return in_shard < (1ll << SMPLX_STEP_COUNT_BITS) && in_shard * SMPLX_BLOCK < (1ll << SMPLX_STEP_CLAIM_BITS);
+}
 
 // The kernels that have a per-robot build, stated once as X(id, kernel): enum KernelId (K_<id>, specialize.h), the names
 // asked of the per-robot code object and the generic kernels beside them (specialize.cpp) all come from this list.

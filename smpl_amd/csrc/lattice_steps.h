@@ -1,8 +1,8 @@
 // smpl_amd/csrc/lattice_steps.h -- the steps of ManipLattice::GetSuccs that are not collision checks, one definition
 // each for every expansion kernel.
 // Owns: planning_fk, world_to_cell, metric_goal_distance, bfs_cost_to_goal, check_joint_limits, var_to_coord;
-// the device copy of the state table (table_lookup, the insert functions and k_table_insert); mprim_active,
-// prim_has_action, successor_values, successor_goal_h.
+// the device copy of the state table (table_probe_issue / table_probe_resolve, table_lookup, the insert functions and
+// k_table_insert); mprim_gate / mprim_active, prim_has_action, successor_values, successor_goal_h.
 // Restates: kdl_robot_model.cpp:173-235, 400-423; bfs_heuristic.cpp:129-138, 355-366;
 // manip_lattice.cpp:1263-1354, 1596-1684; manip_lattice_action_space.cpp:551-621, 662-691.
 #pragma once
@@ -176,23 +176,95 @@ __device__ __forceinline__ int var_to_coord(const ModelLds* __restrict__ M, int 
 // is negative is being filled.  No slot between a coordinate's home and its own slot can have been empty since it was
 // inserted, so meeting an empty or a busy slot first means the coordinate was not in the table before this launch.
 // ConcurrentInserts: inserts may run in other workgroups of the SAME launch (k_small_batch: the extra blocks of
-// table_insert_block).  In the pipeline the inserts ride with the first kernel and the lookups run in the last one, a
-// kernel boundary later, where plain loads do (acquires there cost k_pipe_finish 15 -> 33 us, measured).
+// table_insert_block).  In the pipeline the inserts ride with the first kernel and the lookups run in a later one, a
+// kernel boundary behind them, where plain loads do (acquires there cost k_pipe_finish 15 -> 33 us, measured): that form
+// is table_probe_issue + table_probe_resolve below, the whole slot in one round of 16-byte loads.
+// A slot's tag and coordinate take (nv + 1 + 3) / 4 words of 16 bytes: SMPLX_TABLE_WORDS for the widest robot.  Loops over
+// the words run to that bound and stop at the robot's own count, which a per-robot build knows when it compiles, so that
+// the words a robot does not have cost it nothing.  smplx_table_stride pads a slot to a multiple of 32 bytes and the table
+// comes from hipMalloc: every word is 16-byte aligned.
+#define SMPLX_TABLE_WORDS ((SMPLX_MAX_VARS + 1 + 3) / 4)
+static_assert(4 * SMPLX_TABLE_WORDS >= SMPLX_MAX_VARS + 1, "the words of a probe hold the tag and every coordinate of the widest robot");
+static_assert(4 * SMPLX_TABLE_WORDS <= (SMPLX_MAX_VARS + 1 + 7) / 8 * 8, "... and lie inside its slot (smplx_table_stride)");
+typedef int __attribute__((ext_vector_type(4))) table_int4;
+struct TableSlotWords { table_int4 w[SMPLX_TABLE_WORDS]; unsigned int slot; };
+
+// the whole slot in one round of plain 16-byte loads
+__device__ __forceinline__ void table_slot_load(const SmplxTableDev& T, unsigned int slot, int nv, table_int4 w[SMPLX_TABLE_WORDS])
+{
+    const SMPLX_GLOBAL_AS table_int4* sl = (const SMPLX_GLOBAL_AS table_int4*)(as_global(T.slots) + (size_t)slot * T.stride);
+    const int nw = (nv + 1 + 3) / 4;
+#pragma unroll
+    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) if (k < nw) w[k] = sl[k];
+}
+// every coordinate compared, no short circuit: nothing here waits for anything (c: global memory, registers or LDS)
+template <class CoordPtr>
+__device__ __forceinline__ bool table_slot_match(const table_int4 w[SMPLX_TABLE_WORDS], CoordPtr c, int nv)
+{
+    const int nw = (nv + 1 + 3) / 4;
+    int differ = 0;
+#pragma unroll
+    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) {
+        if (k >= nw) continue;
+        const int base = 4 * k - 1;        // coordinate index of .x
+        if (k > 0 && base < nv) differ |= w[k].x ^ c[base];
+        if (base + 1 < nv) differ |= w[k].y ^ c[base + 1];
+        if (base + 2 < nv) differ |= w[k].z ^ c[base + 2];
+        if (base + 3 < nv) differ |= w[k].w ^ c[base + 3];
+    }
+    return differ == 0;
+}
+
+// The probe of a table that no workgroup of this launch writes (the inserts ran in an earlier launch: k_table_insert in
+// front of k_step_block, a kernel boundary in the pipeline), cut in two after the pattern of issue_root / resolve_root
+// (sphere_checks.h).  table_probe_issue hashes the coordinate and issues the loads of its home slot; it waits for
+// nothing, so a caller can put other work behind it.  table_probe_resolve looks at those words and walks on, one slot a
+// round, only where the home slot held another coordinate.  A slot whose tag is not positive is free (or, in a table that
+// IS being written, being filled): a miss.
+// (what resolves to a miss without a load: a free slot)
+__device__ __forceinline__ TableSlotWords table_probe_none()
+{
+    TableSlotWords r;
+#pragma unroll
+    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) r.w[k] = table_int4{0, 0, 0, 0};
+    r.slot = 0;
+    return r;
+}
+__device__ __forceinline__ TableSlotWords table_probe_issue(const SmplxTableDev& T, const int* __restrict__ c, int nv)
+{
+    TableSlotWords r = table_probe_none();
+    if (!T.slots) return r;               // no table: a miss
+    r.slot = smplx_coord_hash(c, nv) & T.mask;
+    table_slot_load(T, r.slot, nv, r.w);
+    return r;
+}
+__device__ __forceinline__ int table_probe_resolve(const SmplxTableDev& T, const int* __restrict__ c, int nv, TableSlotWords ld)
+{
+    while (true) {
+        const int tag = ld.w[0].x;
+        if (tag <= 0) return -1;          // free, or being filled: a miss (the host resolves misses)
+        if (table_slot_match(ld.w, c, nv)) return tag - 1;
+        ld.slot = (ld.slot + 1) & T.mask;
+        table_slot_load(T, ld.slot, nv, ld.w);
+    }
+}
+
 template <bool ConcurrentInserts>
 __device__ __forceinline__ int table_lookup(const SmplxTableDev& T, const int* __restrict__ c, int nv)
 {
+    if constexpr (!ConcurrentInserts) return table_probe_resolve(T, c, nv, table_probe_issue(T, c, nv));
     if (!T.slots) return -1;
     unsigned int i = smplx_coord_hash(c, nv) & T.mask;
     while (true) {
         const SMPLX_GLOBAL_AS int* sl = as_global(T.slots) + (size_t)i * T.stride;
-        // ConcurrentInserts (k_small_batch): table_insert_item publishes the tag with a release after the coordinates, from
-        // another workgroup; the tag is read with an acquire and the coordinates with loads that bypass this CU's L1, which is
-        // never refreshed by another CU's stores -- a plain load could compare against a stale line (zeros, or half a
-        // coordinate) and return another state's id
-        const int tag = ConcurrentInserts ? __atomic_load_n(&sl[0], __ATOMIC_ACQUIRE) : __atomic_load_n(&sl[0], __ATOMIC_RELAXED);
+        // k_small_batch: table_insert_item publishes the tag with a release after the coordinates, from another workgroup;
+        // the tag is read with an acquire and the coordinates with loads that bypass this CU's L1, which is never refreshed
+        // by another CU's stores -- a plain load could compare against a stale line (zeros, or half a coordinate) and
+        // return another state's id
+        const int tag = __atomic_load_n(&sl[0], __ATOMIC_ACQUIRE);
         if (tag <= 0) return -1;          // free, or being filled: a miss (the host resolves misses)
         bool same = true;
-        for (int v = 0; v < nv; ++v) same = same && (ConcurrentInserts ? __atomic_load_n(&sl[1 + v], __ATOMIC_RELAXED) : sl[1 + v]) == c[v];
+        for (int v = 0; v < nv; ++v) same = same && __atomic_load_n(&sl[1 + v], __ATOMIC_RELAXED) == c[v];
         if (same) return tag - 1;
         i = (i + 1) & T.mask;
     }
@@ -250,19 +322,31 @@ k_table_insert(const SmplxSpaceDev* __restrict__ S, const SmplxSpaceDev* const* 
     table_insert_items(S, stab, items, n, nvars);
 }
 
-// manip_lattice_action_space.cpp:662-691
+// manip_lattice_action_space.cpp:662-691 in two steps.  mprim_gate loads what the gate of a primitive of kind `type` needs
+// from the action record -- constants of the launch, so a kernel loads them at its head, beside its other first loads --
+// and mprim_active decides from them and the state's goal distance.  A long primitive is gated by the SHORT kind's
+// switch and threshold, every other kind by its own.
+struct MprimGate { int type, use_long_and_short, enabled; double thresh; };
+__device__ __forceinline__ MprimGate mprim_gate(const SmplxActionsDev& A, int type)
+{
+    const int kind = type == SMPLX_MP_LONG ? SMPLX_MP_SHORT : type;
+    MprimGate g;
+    g.type = type;
+    g.use_long_and_short = A.use_long_and_short;
+    g.enabled = A.enabled[kind];
+    g.thresh = A.thresh[kind];
+    return g;
+}
+__device__ __forceinline__ bool mprim_active(const MprimGate& g, double goal_dist)
+{
+    const bool near_goal = goal_dist <= g.thresh;
+    if (g.type == SMPLX_MP_LONG) return g.use_long_and_short || !(g.enabled && near_goal);
+    if (g.type == SMPLX_MP_SHORT && g.use_long_and_short) return g.enabled != 0;
+    return g.enabled && near_goal;
+}
 __device__ __forceinline__ bool mprim_active(const SmplxActionsDev& A, double goal_dist, int type)
 {
-    if (type == SMPLX_MP_LONG) {
-        if (A.use_long_and_short) return true;
-        const bool near_goal = goal_dist <= A.thresh[SMPLX_MP_SHORT];
-        return !(A.enabled[SMPLX_MP_SHORT] && near_goal);
-    } else if (type == SMPLX_MP_SHORT) {
-        if (A.use_long_and_short) return A.enabled[type] != 0;
-        const bool near_goal = goal_dist <= A.thresh[type];
-        return A.enabled[type] && near_goal;
-    }
-    return A.enabled[type] && goal_dist <= A.thresh[type];
+    return mprim_active(mprim_gate(A, type), goal_dist);
 }
 
 // can the primitive produce an action at all (a snap needs a joint-space goal: manip_lattice_action_space.cpp:551-559)

@@ -286,7 +286,7 @@ __device__ __forceinline__ void sstate_reinit(SmplxSState& s, int call_number)
     s.flags = 0;
 }
 
-typedef int __attribute__((ext_vector_type(4))) sk_int4;
+typedef table_int4 sk_int4;   // (lattice_steps.h)
 
 // write a state's fields back; heap_index only when the caller owns it (it is otherwise kept current by the sifts)
 __device__ __forceinline__ void sstate_store(SMPLX_GLOBAL_AS SmplxSState* dst, const SmplxSState& s, bool with_heap_index)
@@ -311,38 +311,13 @@ __device__ __forceinline__ SmplxSState sstate_load(const SMPLX_GLOBAL_AS SmplxSS
 }
 
 // One probe sequence of the state table with plain 16-byte loads.  Only the workgroup that owns the query writes its table
-// while the kernel runs, so what it reads is current.  table_probe_start issues the loads of the home slot (they land
-// behind the planning-link FK); table_probe_finish looks at them and walks on if it has to.
+// while the kernel runs, so what it reads is current.  table_probe_start issues the loads of the home slot (the caller
+// puts the planning-link FK between the two, for the loads to travel behind); table_probe_finish looks at them and walks on
+// if it has to.
 struct TableProbe { int id; unsigned int free_slot; };
-// A slot's tag and coordinate take (nv + 1 + 3) / 4 words of 16 bytes: SMPLX_TABLE_WORDS for the widest robot.  The loops
-// below run to that bound and stop at the robot's own count, which a per-robot build knows when it compiles, so that the
-// words a robot does not have cost it nothing.
-#define SMPLX_TABLE_WORDS ((SMPLX_MAX_VARS + 1 + 3) / 4)
-static_assert(4 * SMPLX_TABLE_WORDS >= SMPLX_MAX_VARS + 1, "the words of a probe hold the tag and every coordinate of the widest robot");
-static_assert(4 * SMPLX_TABLE_WORDS <= (SMPLX_MAX_VARS + 1 + 7) / 8 * 8, "... and lie inside its slot (smplx_table_stride)");
-struct TableProbeLoads { sk_int4 w[SMPLX_TABLE_WORDS]; unsigned int slot; };
-__device__ __forceinline__ void table_slot_load(const SmplxTableDev& T, unsigned int slot, int nv, sk_int4 w[SMPLX_TABLE_WORDS])
-{
-    const SMPLX_GLOBAL_AS sk_int4* sl = (const SMPLX_GLOBAL_AS sk_int4*)(as_global(T.slots) + (size_t)slot * T.stride);
-    const int nw = (nv + 1 + 3) / 4;       // 16-byte words that hold the tag and the coordinate (stride is a multiple of 8 ints)
-#pragma unroll
-    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) if (k < nw) w[k] = sl[k];
-}
-__device__ __forceinline__ bool table_slot_match(const sk_int4 w[SMPLX_TABLE_WORDS], const LDS_AS int* c, int nv)
-{
-    const int nw = (nv + 1 + 3) / 4;
-    bool same = w[0].x > 0;
-#pragma unroll
-    for (int k = 0; k < SMPLX_TABLE_WORDS; ++k) {
-        if (k >= nw) continue;
-        const int base = 4 * k - 1;        // coordinate index of .x
-        if (k > 0 && base < nv) same = same && w[k].x == c[base];
-        if (base + 1 < nv) same = same && w[k].y == c[base + 1];
-        if (base + 2 < nv) same = same && w[k].z == c[base + 2];
-        if (base + 3 < nv) same = same && w[k].w == c[base + 3];
-    }
-    return same;
-}
+// (SMPLX_TABLE_WORDS, the 16-byte words of a slot: lattice_steps.h)
+// (table_slot_load and table_slot_match, the slot's loader and its compare, are shared with the step kernels: lattice_steps.h)
+typedef TableSlotWords TableProbeLoads;
 __device__ __forceinline__ TableProbeLoads table_probe_start(const SmplxTableDev& T, int nv, unsigned int hash)
 {
     TableProbeLoads r;
@@ -355,7 +330,7 @@ __device__ __forceinline__ TableProbe table_probe_finish(const SmplxTableDev& T,
     TableProbe r;
     while (true) {
         if (ld.w[0].x == 0) { r.id = -1; r.free_slot = ld.slot; return r; }
-        if (table_slot_match(ld.w, c, nv)) { r.id = ld.w[0].x - 1; r.free_slot = 0; return r; }
+        if (ld.w[0].x > 0 && table_slot_match(ld.w, c, nv)) { r.id = ld.w[0].x - 1; r.free_slot = 0; return r; }
         ld.slot = (ld.slot + 1) & T.mask;
         table_slot_load(T, ld.slot, nv, ld.w);
     }

@@ -70,6 +70,7 @@ struct FrontierBatch {
 struct DeviceTable {
     int32_t* d_table = nullptr;
     size_t cap = 0, count = 0;
+    size_t test_slots = 0;        // test hook: slots of the first table table_ensure allocates (0: the default)
     int64_t regrows = 0;          // times the table was outgrown (load factor above 1/2) and allocated again, every state re-inserted
     std::vector<int32_t> pending_ins;
     DevBuf<int32_t> b_ins;
@@ -133,8 +134,9 @@ struct StepLaunch {
     int one_launch_blocks = 0; // blocks of k_step_block resident in one round (occupancy query x CUs); 0: it cannot run
     int64_t one_launch_steps = 0;   // steps that took k_step_block
     // Counters of a step, SMPLX_WORK_COUNTER_BYTES: the pipeline's work-list counters (8 shard counters + deferred count, one
-    // 128-byte line each) and, behind them, what k_step_block keeps (kernels.h SMPLX_STEP_CTR_*: the claim counters of the
-    // compact stream, the overflow flag, the count of finished blocks).  One set per stream the space has launched a step
+    // 128-byte line each) and, behind them, what k_step_block keeps (kernels.h SMPLX_STEP_CTR_*: one packed claim word per
+    // shard of the compact stream -- records of both regions and the blocks that have claimed -- and the count of finished
+    // shards).  One set per stream the space has launched a step
     // on.  A set is all-zero whenever no step is in flight on its stream: k_pipe_finish clears its part behind its last
     // reader, the last block of k_step_block its own.  dirty: a launch sequence on it failed part-way, it is cleared before
     // its next use.

@@ -143,8 +143,11 @@ ExpandPath expand_path(const smplx_space* s, int B, int zero_copy_max, bool forc
     if (small && B <= zero_copy_max && s->step.prof_events.empty()) return ExpandPath::SmallZeroCopy;
     if (small && !force_pipeline) return ExpandPath::Small;
     if (s->step.fused_mode) return ExpandPath::Fused;
+    // (smplx_step_claim_fits: the packed claim words of k_step_block hold a shard's blocks and records; a grid beyond that --
+    // a million blocks, never a resident one -- keeps the pipeline)
     const bool can_run = s->step.one_launch_blocks > 0 && !s->step.pipe_prep && s->step.work_list_items == 0 &&
-                         s->step.prof_used + 3 > s->step.prof_events.size();
+                         s->step.prof_used + 3 > s->step.prof_events.size() &&
+                         smplx_step_claim_fits(blocks_for((long long)B * s->M, SMPLX_BLOCK));
     const bool by_rule = s->ks.specialized && s->step.one_launch_per_cu >= 4 &&
                          blocks_for((long long)B * s->M, SMPLX_BLOCK) <= s->step.one_launch_blocks;
     if (can_run && s->step.one_launch != 0 && (s->step.one_launch == 1 || by_rule)) return ExpandPath::OneLaunch;
@@ -195,7 +198,8 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     const ExpandPath path = expand_path(s, B, a.zero_copy ? B : 0, a.force_pipeline || cmp.rec_a);
     if (s->step.one_launch == 1 && path == ExpandPath::Pipeline)
         return set_error(SMPLX_E_ARG, "the one-launch step was asked for (smplx_test_set_one_launch) but cannot run: a pipeline test hook or a "
-                                      "profile-event triple is set, or a block of k_step_block does not fit this model");
+                                      "profile-event triple is set, a block of k_step_block does not fit this model, or the grid is beyond "
+                                      "what its claim words count");
     const int32_t* ins_items = a.k5 && s->dt.d_table ? a.k5->items : nullptr;
     const int n_ins = ins_items ? a.k5->n_items : 0;
     if (s->step.work_list_items > 0) k.capacity = s->step.work_list_items;   // test hook: almost every edge overflows into the deferred pass

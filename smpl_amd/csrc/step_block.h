@@ -2,12 +2,16 @@
 // Block b owns edges [128 b, 128 b + 128) of the (state, primitive) grid -- the edges block b of k_pipe_finish owns, so
 // block_tab rows, compaction shards and per-block tallies keep their meaning -- and runs the pipeline's stages on them
 // with everything between the stages in LDS instead of in HBM arrays and global atomics:
-//   head       edge lanes load their parent's joint values; the block stages the model image and the joint values of
-//              the (at most SMPLX_STEP_STATES, 7 at M = 25) states its edges belong to
+//   head       edge lanes load their parent's joint values and what their primitive's gate needs of the action record
+//              (mprim_gate); the block stages the model image and the joint values of the (at most SMPLX_STEP_STATES, 7 at
+//              M = 25) states its edges belong to
 //   planning   the third wave is the goal-distance wave of k_pipe_setup (lane-parallel sincos -> the states' rows of sines
-//              and cosines in LDS -> the chain); beside it the edge lanes run pipe_edge_values in registers
-//   gate       mprim_active from LDS; per-robot build: the successor evaluation of k_pipe_configs' successor role for an
-//              edge that is active and within limits; successor joint values, waypoint counts and their prefix to LDS
+//              and cosines in LDS -> the chain); beside it the edge lanes run pipe_edge_values in registers and, per-robot
+//              build, discretise an edge within limits
+//   gate       one compare with the distance in LDS; per-robot build: the rest of k_pipe_configs' successor role for an
+//              edge that is active and within limits -- the loads of its home slot in the state table issued, chain, goal
+//              test, heuristic, then the table id from the slot that has arrived meanwhile; successor joint values,
+//              waypoint counts and their prefix to LDS
 //   collision  every thread takes items t, t + blockDim.x, ... of n_states + sum(W - 1): the block's states at alpha 0,
 //              then (edge, waypoint) found by a search over the prefix; one item is the fast path of k_pipe_configs.  No
 //              list, hence no capacity, no deferred edge and no whole-edge walk.  Every waypoint is examined, as on the
@@ -15,10 +19,12 @@
 //   verdict    edge lanes: k_pipe_finish's verdict, outputs, ballot compaction, tally_block
 // A state whose edges straddle two blocks has its distance and its own check computed by both (same inputs, same
 // instructions, same bits); what is per state in the tallies is counted by the owner of its primitive 0.
-// No block waits for another.  The one cross-block step sits behind every output: the claim counters of the compact stream
-// live in the stream's counter set (all-zero between steps), and the block that finishes last copies them to the caller's
-// totals -- which need not be zero beforehand -- and zeroes the set.  Finished blocks are counted per shard, then the
-// shards, without a device-wide fence: one counter for all 800 blocks behind a fence each made the step 53 us.
+// No block waits for another.  The one cross-block step is the claim of the compact stream: each compaction shard has one
+// 64-bit word in the stream's counter set (all-zero between steps; kernels.h SMPLX_STEP_CTR_*) that holds the records
+// claimed in region A, in region B and the blocks that have claimed, so ONE returning atomic per block claims both ranges
+// and counts the block.  The block that claims last in the step's last shard copies the totals to the caller's -- which
+// need not be zero beforehand -- and zeroes the set.  (One counter for all 800 blocks behind a fence each made the step
+// 53 us; two claim atomics and a count, one after the other, were three round trips at the tail of every block.)
 // The generic build keeps the successor's joint values in out_q (as its pipeline does) and evaluates the successor of a
 // valid edge behind the verdict; the launch rule (step.h) takes this kernel for per-robot builds that keep four blocks a CU.
 #pragma once
@@ -67,7 +73,11 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     const int pi = in_range ? (int)(tid - (long long)si * nprims) : 0;
     const int ks = si - s0;
     const SmplxSpaceDev* Sq = stab ? stab[state_q[si]] : S;
-    const int type = A.type[pi];
+    const MprimGate gate = mprim_gate(A, A.type[pi]);   // constants of the launch: they travel with the model image and the parents
+#if defined(SMPLX_CONST_MODEL) && !defined(ABL_NO_SUCC)
+    SmplxTableDev table = {nullptr, 0u, 0, 0};
+    if (out_id) table = Sq->table;
+#endif
     if (t < BLOCK) { s_elk[t] = 0; s_ebad[t] = 0; }
     if (t < SMPLX_STEP_STATES) { s_slk[t] = 0; s_sbad[t] = 0; }
 #ifdef SMPLX_CONST_MODEL
@@ -95,6 +105,14 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
 #pragma unroll
     for (int v = 0; v < CM_NV; ++v) scv[v] = 0;
     if (in_range) flags = pipe_edge_values(M, A, Sq, pi, pqv, sqv, W);
+#ifndef ABL_NO_SUCC
+    // ... and so are the coordinates of an edge within limits (pipe_successor's first piece): they need nothing of the
+    // parent's sines and cosines.  (The home slot's loads issued here as well, beside the distance chain, measured no better
+    // than behind the gate: 27.1 against 27.5 us a step, below three times the run-to-run spread.)
+    if (in_range && flags == 0) {
+        successor_coords(M, sqv, scv);
+    }
+#endif
     if (dist_wave) {
         if constexpr (CM_PARENT_TRIG) {
             // The goal-distance wave of k_pipe_setup as it stands: one (state, variable) pair a lane, 64 / NV states a round;
@@ -156,7 +174,7 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     // the gate; successor joint values and waypoint counts where the collision phase finds them
     int items = 0;
     if (in_range) {
-        if (!mprim_active(A, s_gd[ks], type)) {
+        if (!mprim_active(gate, s_gd[ks])) {
             flags = SMPLX_F_INACTIVE;
             W = 0;
         } else {
@@ -166,20 +184,26 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
                 for (int v = 0; v < CM_NV; ++v) { s_sq[v * BLOCK + t] = sqv[v]; out_q[tid * CM_NV + v] = sqv[v]; }
             }
 #ifndef ABL_NO_SUCC
-            // the successor role of k_pipe_configs, behind the gate: discretisation, table id, planning-link FK, goal test,
-            // heuristic of an edge that is active and within limits.  (In front of the gate, beside the distance chain, every
-            // wave pays the seven sincos rounds of its snap edges, active or not: 31.3 against 30.0 us a step.)
+            // the rest of the successor role of k_pipe_configs, behind the gate, for an edge that is active and within
+            // limits: the home slot's loads, which travel during the chain, planning-link FK, goal test, heuristic, table id.
+            // (With the chain in front of the gate too, beside the distance chain, every wave pays the seven sincos rounds of
+            // its snap edges, active or not: 31.3 against 30.0 us a step.  Cutting the heuristic into a load here and its cost
+            // in the verdict hid nothing: the compiler waits for the load where the edge lanes' branch rejoins.)
             if (flags == 0) {
                 constexpr bool SC = CM_PARENT_TRIG && CM_TRIG_PLANNING != 0;
+                const SmplxBfsDev sbfs = Sq->bfs;
+                const TableSlotWords home = table_probe_issue(table, scv, CM_NV);
                 if constexpr (SC) {
                     double prow[2 * CM_NV], sn[CM_NV], cs[CM_NV];
 #pragma unroll
                     for (int j = 0; j < 2 * CM_NV; ++j) prow[j] = s_trig[ks * SMPLX_TRIG_ROW + 2 * CM_NV + j];
                     parent_trig<CM_TRIG_PLANNING, true>(sqv, pqv, prow, sn, cs);
-                    pipe_successor<true>(M, Sq, grid, sqv, scv, out_id != nullptr, succ_h, succ_id, succ_goal, sn, cs);
+                    succ_h = successor_goal_h<true>(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal, sn, cs);
                 } else {
-                    pipe_successor(M, Sq, grid, sqv, scv, out_id != nullptr, succ_h, succ_id, succ_goal);
+                    succ_h = successor_goal_h(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal);
                 }
+                // the home slot arrived during the chain: the id costs one wait, and more only where the probe walks on
+                succ_id = table_probe_resolve(table, scv, CM_NV, home);
             }
 #endif
 #else
@@ -307,7 +331,19 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
         succ_h = h;
         if (out_id) out_id[tid] = succ_id;
     }
-    // K5: validity compaction, as k_pipe_finish; the claim counters are the stream's (step_ctr), not the caller's totals
+    // K5: validity compaction, as k_pipe_finish, but the claim is on the stream's counter set (step_ctr), not on the caller's
+    // totals, and it is one atomic: the shard's word holds records of region A in bits 0-23, of region B in bits 24-47 and
+    // the blocks that have claimed in bits 48-63 (the launch rule keeps a shard's fields from running over: kernels.h
+    // smplx_step_claim_fits).  Every block claims, also one without a record: the claim is what counts it.
+    // Order: the last adder of a word sees every earlier add in that word's modification order; it adds to the count of
+    // shards only after its own claim has returned, and the block whose add completes that count reads the words only
+    // after that add has returned.  Device-scope atomics on this memory execute at one point of coherence, and only atomics
+    // touch these words, so it reads every claim of the step; no block touches the set behind its own claim, so the set it
+    // zeroes stays zero.  A sub-region has overflowed exactly when its final total exceeds its capacity (a block's claim
+    // ends at the running total), so the flag is worked out from the totals and needs no word of its own.  If the order
+    // broke, totals would be wrong and the set would stay non-zero: the tests read the set after back-to-back steps
+    // (smplx_test_step_counters_zero).
+    __shared__ int s_last;
     if (cmp.rec_a) {
         __shared__ int c_cnt[BLOCK / 64][2];
         __shared__ int c_base[2];
@@ -321,15 +357,20 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
             int ta = 0, tb = 0;
 #pragma unroll
             for (int k = 0; k < BLOCK / 64; ++k) { ta += c_cnt[k][0]; tb += c_cnt[k][1]; }
-            const int shard = blockIdx.x % SMPLX_CMP_SHARDS;
+            const int nb = (int)gridDim.x, shard = blockIdx.x % SMPLX_CMP_SHARDS;
+            const int in_shard = (nb - shard + SMPLX_CMP_SHARDS - 1) / SMPLX_CMP_SHARDS;
+            const int shards = nb < SMPLX_CMP_SHARDS ? nb : SMPLX_CMP_SHARDS;
             const int sa = cmp.cap_a / SMPLX_CMP_SHARDS, sb = cmp.cap_b / SMPLX_CMP_SHARDS;
-            int ba = ta > 0 ? atomicAdd(&step_ctr[SMPLX_STEP_CTR_BASE + 64 * shard], ta) : 0;
-            int bb = tb > 0 ? atomicAdd(&step_ctr[SMPLX_STEP_CTR_BASE + 64 * shard + 32], tb) : 0;
-            if (ba + ta > sa || bb + tb > sb) {   // overflow: dense outputs stay valid
-                atomicExch(&step_ctr[SMPLX_STEP_CTR_OVERFLOW], 1);
-                __threadfence();   // (rare) the flag is in place before this block counts as finished
-                ba = -1;
-            }
+            unsigned long long* word = reinterpret_cast<unsigned long long*>(step_ctr + SMPLX_STEP_CTR_BASE + 32 * shard);
+            const unsigned long long mine = (unsigned long long)ta | ((unsigned long long)tb << 24) | (1ull << 48);
+            const unsigned long long was = atomicAdd(word, mine);
+            const int ba0 = ta > 0 ? (int)(was & 0xFFFFFFull) : 0, bb0 = tb > 0 ? (int)((was >> 24) & 0xFFFFFFull) : 0;
+            int ba = ba0, bb = bb0;   // (a block without records of a region starts it at the sub-region's base, as ever)
+            int last = 0;
+            if ((int)(was >> 48) == in_shard - 1)
+                last = atomicAdd(&step_ctr[SMPLX_STEP_CTR_DONE], 1) == shards - 1 ? 1 : 0;
+            s_last = last;
+            if (ba + ta > sa || bb + tb > sb) ba = -1;   // overflow: dense outputs stay valid
             else { ba += shard * sa; bb += shard * sb; }
             c_base[0] = ba; c_base[1] = bb;
             int* bt = cmp.block_tab + 4 * (size_t)blockIdx.x;
@@ -360,39 +401,20 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
         const unsigned long long m_valid = __ballot((flags & SMPLX_F_VALID) != 0);
         tally_block<NT / 64>(counters, dist_wave ? 0 : __popcll(m_eval), dist_wave ? 0 : __popcll(m_valid), lookups, performed, ncfg, slk);
     }
-    // The one cross-block step, behind every output of the block: the block that finishes last hands the claim counters to
-    // the caller's totals (existing layout; whatever they held is overwritten) and leaves the stream's set all-zero for the
-    // next step.  Every block of this grid owns a block_tab row and has written it, so there is no unused row to zero.
-    if (cmp.rec_a) {
-        // Finished blocks are counted in two levels, so that no counter takes more than a sixteenth of the grid's atomics
-        // (same-address atomics serialise): per compaction shard, then the shards.
-        // There is no release fence in front of the count and no acquire fence in the last block, and that rests on the
-        // hardware, not on the memory model (relaxed atomics on different addresses are not ordered by HIP): thread 0's claim
-        // atomics are RETURNING atomics whose values ba / bb it consumes (block_tab, c_base) before the __syncthreads calls
-        // that stand between them and its count, so they have completed when the count issues; device-scope atomics on
-        // this memory execute at one point of coherence, so the last block's atomicExch sees every claim.  Only atomics may
-        // touch these words.  The overflow flag, whose value nobody consumes, is followed by a fence of its own.  If the
-        // order broke, totals would be wrong and the set would stay non-zero: the tests read the set after back-to-back
-        // steps (smplx_test_step_counters_zero).
-        __shared__ int s_last;
-        if (t == 0) {
-            const int nb = (int)gridDim.x, shard = blockIdx.x % SMPLX_CMP_SHARDS;
-            const int in_shard = (nb - shard + SMPLX_CMP_SHARDS - 1) / SMPLX_CMP_SHARDS;
-            const int shards = nb < SMPLX_CMP_SHARDS ? nb : SMPLX_CMP_SHARDS;
-            int last = 0;
-            if (atomicAdd(&step_ctr[SMPLX_STEP_CTR_DONE + 32 * (1 + shard)], 1) == in_shard - 1)
-                last = atomicAdd(&step_ctr[SMPLX_STEP_CTR_DONE], 1) == shards - 1 ? 1 : 0;
-            s_last = last;
-        }
-        __syncthreads();
-        if (s_last) {
-            if (t < 2 * SMPLX_CMP_SHARDS) {
-                const int shard = t >> 1, region = t & 1;
-                cmp.totals[32 * shard + region] = atomicExch(&step_ctr[SMPLX_STEP_CTR_BASE + 64 * shard + 32 * region], 0);
-            } else if (t == 2 * SMPLX_CMP_SHARDS) {
-                cmp.totals[32 * SMPLX_CMP_SHARDS] = atomicExch(&step_ctr[SMPLX_STEP_CTR_OVERFLOW], 0);
-            } else if (t <= 2 * SMPLX_CMP_SHARDS + 1 + SMPLX_CMP_SHARDS) {
-                atomicExch(&step_ctr[SMPLX_STEP_CTR_DONE + 32 * (t - 2 * SMPLX_CMP_SHARDS - 1)], 0);
+    // The step's last claimer hands the totals to the caller (existing layout; whatever they held is overwritten) and leaves
+    // the stream's set all-zero for the next step; every other block is done.  Every block of this grid owns a block_tab row
+    // and has written it, so there is no unused row to zero.
+    if (cmp.rec_a && s_last) {
+        if (t < SMPLX_CMP_SHARDS) {
+            unsigned long long* word = reinterpret_cast<unsigned long long*>(step_ctr + SMPLX_STEP_CTR_BASE + 32 * t);
+            const unsigned long long tot = atomicExch(word, 0ull);
+            const int na = (int)(tot & 0xFFFFFFull), nb = (int)((tot >> 24) & 0xFFFFFFull);
+            cmp.totals[32 * t] = na;
+            cmp.totals[32 * t + 1] = nb;
+            const unsigned long long over = __ballot(na > cmp.cap_a / SMPLX_CMP_SHARDS || nb > cmp.cap_b / SMPLX_CMP_SHARDS);
+            if (t == 0) {
+                cmp.totals[32 * SMPLX_CMP_SHARDS] = over != 0ull ? 1 : 0;
+                atomicExch(&step_ctr[SMPLX_STEP_CTR_DONE], 0);
             }
         }
     }

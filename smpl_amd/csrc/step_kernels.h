@@ -1,7 +1,7 @@
 // smpl_amd/csrc/step_kernels.h -- the kernels of a frontier step.
 // Owns: the fused pair k_state_prep + k_expand (one thread walks a whole edge: expand_edge) with tally_block, and the
 // waypoint-parallel pipeline, which is the default: k_pipe_setup, k_pipe_configs, k_pipe_finish, with k_pipe_prep in
-// front for the four-launch mode, and their helpers (pipe_edge_values, pipe_successor, pipe_successor_role).  The one-launch
+// front for the four-launch mode, and their helpers (pipe_edge_values, successor_coords, pipe_successor, pipe_successor_role).  The one-launch
 // form of the pipeline for a batch that is resident in one round, k_step_block, is in step_block.h and built from the same
 // helpers.
 // Restates: manip_lattice.cpp:254-305, 1471-1535 (the GetSuccs loop body); manip_lattice_action_space.cpp:385-397;
@@ -443,9 +443,20 @@ k_pipe_setup(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
     }
 }
 
+// ManipLattice::stateToCoord (manip_lattice.cpp:1263-1289) of the successor's joint values
+__device__ __forceinline__ void successor_coords(const ModelLds* __restrict__ M, const double* __restrict__ sq, int* __restrict__ sc)
+{
+    const int nv = MV_NVARS(M);
+    MV_UNROLL
+    for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
+}
+
 // What the verdict of an edge does not decide: discretisation, state-table id, planning-link FK, goal test, heuristic
 // (manip_lattice.cpp:1496-1535 for a successor that passed the limits test).  Needs the successor's joint values and
 // the query's goal, BFS grid and table only, all final when k_pipe_setup ends.  sc: where the coordinates go.
+// It is the composition of its pieces -- successor_coords, table_probe_issue, successor_goal_h (chain, goal test,
+// heuristic), table_probe_resolve -- in this order, so that the home slot of the table travels during the chain.  The
+// per-robot k_step_block (step_block.h) places the same pieces itself, the first two in front of its gate.
 template <bool SC = false>
 __device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, const SmplxSpaceDev* __restrict__ Sq,
                                                const SmplxGridDev& grid, const double* __restrict__ sq, int* __restrict__ sc,
@@ -454,11 +465,10 @@ __device__ __forceinline__ void pipe_successor(const ModelLds* __restrict__ M, c
 {
     const int nv = MV_NVARS(M);
     const SmplxBfsDev bfs = Sq->bfs;
-    MV_UNROLL
-    for (int v = 0; v < nv; ++v) sc[v] = var_to_coord(M, v, sq[v]);
-    // K5: the table lookup only needs the coordinates; issued here, its probe lands behind the planning-link FK
-    id = want_id ? table_lookup<false>(Sq->table, sc, nv) : -1;
+    successor_coords(M, sq, sc);
+    const TableSlotWords home = want_id ? table_probe_issue(Sq->table, sc, nv) : table_probe_none();   // K5
     h = successor_goal_h<SC>(M, Sq->goal, bfs, grid, sq, sc, is_goal, sn, cs);
+    id = want_id ? table_probe_resolve(Sq->table, sc, nv, home) : -1;
 }
 
 // Successor role of k_pipe_configs: the blocks behind the cfg_blocks collision blocks, one thread per edge.  An edge whose

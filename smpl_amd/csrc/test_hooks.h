@@ -44,6 +44,15 @@ int smplx_test_heap_ops(const int32_t* ops, int nops, int lds_entries, int32_t* 
 int smplx_test_table_probe(int nvars, int slots, int one_home, const int32_t* inserted, int n_inserted, const int32_t* queries, int n_queries,
                            int32_t* found_at_insert, int32_t* ids);
 
+/* While `slots` is set (a power of two, at least 64; 0 restores the default of 2^18), the first device copy of the state table
+ * that a space without one allocates (smplx_table_sync, the K5 entry points) starts at that many slots; it still grows by the
+ * ordinary rule (a table four times the size at load factor 1/2), so a small lattice gets a table that is between one eighth
+ * and one half full instead of nearly empty, with probe chains that go beyond the home slot. */
+int smplx_test_set_table_slots(smplx_space* s, int slots);
+
+/* Slots of the space's device copy of the state table now; 0 while it has none. */
+long long smplx_test_table_slots(const smplx_space* s);
+
 /* First capacity (states) of the device-resident search's buffers, so that a test can make a search outgrow them
  * (SMPLX_SS_GROW: the host enlarges and launches again); 0 restores the default sizing.  A state table that the search
  * allocates while the hook is set starts at the smallest size that holds this capacity half full (instead of 2^16 slots),
