@@ -172,6 +172,52 @@ int smplx_cc_interpolate(smplx_space* s, const double* a, const double* b, doubl
 /* world positions of all sphere-tree nodes for n states: out[n][nnodes][3] (RobotCollisionState::updateSphereState) */
 int smplx_cc_sphere_positions(smplx_space* s, const double* q, int n, double* out);
 
+/* ---- CollisionDistanceExtension (smpl/include/smpl/collision_checker.h:132-144): distance to collision ----
+ * How far a configuration, or an edge, is from collision and what is closest, in metres, fp64, bit-reproducible (the
+ * arithmetic contract of DESIGN.md section 3; DESIGN.md section 16 has the whole specification).  The reference's own
+ * CollisionSpace::collisionDistance is unfinished (self_collision_model.cpp:1386-1511, 1641), so there is no reference
+ * value to equal; the terms are the reference's, the minimum over them is defined here.  For one configuration, with the
+ * grid, the padding, the checked pairs and the attached bodies as smplx_cc_state_valid_batch uses them:
+ *   world term of a LEAF sphere (of a robot tree or of an attached body) at world position p with radius r:
+ *       res * sqrt((double)d2) - (r + padding),   d2 = the squared cell distance of p's cell, 0 outside the grid
+ *     (SphereCollisionDistance, collision_operations.h:81-89, over distance_map.hpp:143-146).  The grid stores d2 only up
+ *     to dmax_sqrd, so the term saturates at res * sqrt(dmax_sqrd) - (r + padding): a result at that cap means "at
+ *     least".  A sphere outside the grid has the term -(r + padding).
+ *   pair term of two leaf spheres at pa, pb with radii ra, rb (d = pb - pa):
+ *       sqrt((dx*dx + dy*dy) + dz*dz) - (ra + rb)      (sphereDistance, self_collision_model.cpp:1644-1649; no padding)
+ *     over exactly the pairs the validity check tests: leaf x leaf of every checked tree pair (smplx_model_pairs), every
+ *     body against every robot tree not in its allowed list, every body against every later body unless either allows
+ *     the other.
+ *   world = min of the world terms, self = min of the pair terms (+infinity where there is none),
+ *   clearance = min(world, self).  Inner nodes of the sphere trees contribute no term: only leaves are looked up.
+ * parts (may be NULL): n x 2 {world, self}.  witness (may be NULL): n x 4 int32 {kind, a, b, waypoint}, a term that attains
+ * the clearance (any of them where several tie):
+ *   kind 0  robot leaf vs world      a = robot node (smplx_model_nodes order), b = -1
+ *   kind 1  robot leaf vs robot leaf a = node of the group-earlier tree, b = node of the later one
+ *   kind 2  body leaf vs world       a = body node (smplx_attached_nodes order), b = -1
+ *   kind 3  body leaf vs robot leaf  a = body node, b = robot node
+ *   kind 4  body leaf vs body leaf   a = node of the earlier body, b = node of the later one
+ *   kind -1 no term at all (a = b = -1)
+ * waypoint is 0 for a state.  For an edge a -> b everything is the minimum over the configurations isStateToStateValid
+ * interpolates -- W waypoints, waypoint j at alpha = j * (1 / (W - 1)), the rows smplx_cc_interpolate returns -- each part
+ * over all of them, and waypoint is the index of the one the witness belongs to.  An edge without motion (W == 0) answers
+ * with its start configuration alone as waypoint 0; note that the edge CHECK visits nothing there and calls such an
+ * edge valid whatever the configuration is.
+ * Relation to validity, in one direction only: clearance > 1e-9 implies smplx_cc_state_valid_batch (for an edge:
+ * smplx_cc_edge_valid_batch) says valid.  The converse does not hold: the reference's traversal looks at a leaf only when
+ * all its ancestors fail, so a leaf may be in collision while an ancestor's lookup clears it.
+ * Conventions of smplx_cc_state_valid_batch*: SMPLX_E_ARG for a null s / q / clearance, n < 0 and non-finite joint
+ * values; n == 0 is SMPLX_OK and touches nothing; the _device form takes device pointers, launches on `stream` and does
+ * not synchronise.  The calls read the field and the bodies as they are, need no goal, are not refused after a grid edit
+ * or an attach, and leave a search that smplx_replan may resume untouched. */
+int smplx_cc_state_clearance_batch(smplx_space* s, const double* q, int n, double* clearance,
+                                   double* parts /* n x 2 {world, self}, may be NULL */,
+                                   int32_t* witness /* n x 4, may be NULL */);
+int smplx_cc_state_clearance_batch_device(smplx_space* s, const double* d_q, int n, double* d_clearance,
+                                          double* d_parts, int32_t* d_witness, void* stream);
+int smplx_cc_edge_clearance_batch(smplx_space* s, const double* a, const double* b, int n, double* clearance,
+                                  double* parts, int32_t* witness);
+
 /* ---- attached collision bodies (CollisionSpace::processAttachedCollisionObject -> attachObject / detachObject,
  * sbpl_collision_checking/src/collision_space.cpp:119-124, 297-345) ----
  * A body is a set of spheres (n x {x, y, z, r}, metres, in the frame of `link`) rigidly attached to a link of the

@@ -39,6 +39,7 @@ SYMBOLS = [
     "smplx_replan", "smplx_replan_multi", "smplx_set_goals_joint_multi", "smplx_set_goals_xyz_multi",
     "smplx_attach_body", "smplx_detach_body", "smplx_attached_bodies", "smplx_attached_nodes", "smplx_cc_attached_positions",
     "smplx_set_goal_pose", "smplx_set_goals_pose_multi", "smplx_goal_orientation", "smplx_planning_pose_batch", "smplx_rpy_angle",
+    "smplx_cc_state_clearance_batch", "smplx_cc_state_clearance_batch_device", "smplx_cc_edge_clearance_batch",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -377,6 +378,30 @@ class Space:
         out = np.zeros((n, self.model.nnodes, 3))
         _chk(lib().smplx_cc_sphere_positions(self.h, _p(q, _dp), n, _p(out, _dp)))
         return out
+
+    # ---- CollisionDistanceExtension: distance to collision (include/smpl_amd.h has the specification) ----
+    def state_clearance_batch(self, q):
+        """(clearance[n], parts[n, 2] = {world, self}, witness[n, 4] = {kind, a, b, waypoint}) of n states, in metres"""
+        q = _f64(q).reshape(-1, self.N); n = q.shape[0]
+        clr = np.zeros(n); parts = np.zeros((n, 2)); wit = np.zeros((n, 4), np.int32)
+        lib().smplx_cc_state_clearance_batch.argtypes = [C.c_void_p, _dp, C.c_int, _dp, _dp, _ip]
+        _chk(lib().smplx_cc_state_clearance_batch(self.h, _p(q, _dp), n, _p(clr, _dp), _p(parts, _dp), _p(wit, _ip)))
+        return clr, parts, wit
+
+    def state_clearance_batch_device(self, d_q, n, d_clearance, d_parts, d_witness, stream):
+        """Raw device pointers (ints; d_parts and d_witness may be None); launches on `stream`, does not synchronise."""
+        lib().smplx_cc_state_clearance_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                                C.c_void_p, C.c_void_p]
+        _chk(lib().smplx_cc_state_clearance_batch_device(self.h, d_q, n, d_clearance, d_parts, d_witness, stream))
+
+    def edge_clearance_batch(self, a, b):
+        """state_clearance_batch's triple for n edges a[i] -> b[i]: the minimum over each edge's waypoints"""
+        a = _f64(a).reshape(-1, self.N); b = _f64(b).reshape(-1, self.N); n = a.shape[0]
+        assert b.shape == a.shape
+        clr = np.zeros(n); parts = np.zeros((n, 2)); wit = np.zeros((n, 4), np.int32)
+        lib().smplx_cc_edge_clearance_batch.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _dp, _dp, _ip]
+        _chk(lib().smplx_cc_edge_clearance_batch(self.h, _p(a, _dp), _p(b, _dp), n, _p(clr, _dp), _p(parts, _dp), _p(wit, _ip)))
+        return clr, parts, wit
 
     # ---- attached collision bodies (CollisionSpace::attachObject / detachObject) ----
     def attach_body(self, body_id, link, spheres, allowed=()):

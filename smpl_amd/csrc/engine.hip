@@ -306,6 +306,7 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
     s->lds_nroot = s->ks.specialized ? 0 : s->model.dev.nroot;
     s->lds_bytes = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
     s->lds_bytes_valid = smplx_lds_bytes(s->blob_bytes, s->lds_nroot, s->ks.specialized ? 0 : s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
+    s->lds_bytes_clearance = smplx_clearance_lds_bytes(s->blob_bytes, s->model.dev.ntrees, s->model.dev.nslots, s->model.dev.nvars, s->model.dev.stack_bytes);
     s->step.one_launch_lds = smplx_lds_bytes_n(s->blob_bytes, s->lds_nroot, s->ks.specialized ? 0 : s->model.dev.nslots, s->model.dev.nvars,
                                                s->model.dev.stack_bytes, SMPLX_STEP_BLOCK);
     s->step.one_launch_blocks = step_block_resident(s, s->step.one_launch_lds, &s->step.one_launch_per_cu);
@@ -620,6 +621,74 @@ int smplx_cc_sphere_positions(smplx_space* s, const double* q, int n, double* ou
     HIP_TRY(hipMemcpyAsync(out, s->b_sq.p, sizeof(double) * cnt, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return SMPLX_OK;
+}
+
+// ---- clearance: distance to collision (include/smpl_amd.h; kernels: clearance_kernels.h) -------------------------------
+
+namespace {
+
+const char* const kClearanceLds = "the clearance kernels need more LDS per block than a CU has (160 KB) for this model";
+
+// n rows of results from the space's clearance scratch to the caller's arrays, on the space's stream
+int clearance_results(smplx_space* s, int n, double* clearance, double* parts, int32_t* witness)
+{
+    HIP_TRY(hipMemcpyAsync(clearance, s->b_clr_out.p, sizeof(double) * n, hipMemcpyDeviceToHost, s->stream));
+    if (parts) HIP_TRY(hipMemcpyAsync(parts, s->b_clr_out.p + n, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, s->stream));
+    if (witness) HIP_TRY(hipMemcpyAsync(witness, s->b_clr_wit.p, sizeof(int32_t) * 4 * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return SMPLX_OK;
+}
+
+}  // namespace
+
+int smplx_cc_state_clearance_batch(smplx_space* s, const double* q, int n, double* clearance, double* parts, int32_t* witness)
+{
+    if (!s || !q || !clearance || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (!sane_values(q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    if (s->lds_bytes_clearance > 160 * 1024) return set_error(SMPLX_E_LIMIT, kClearanceLds);
+    int e;
+    if ((e = s->b_clr_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->b_clr_out.reserve((size_t)n * 3))) return e;
+    if ((e = s->b_clr_wit.reserve((size_t)n * 4))) return e;
+    HIP_TRY(hipMemcpyAsync(s->b_clr_q.p, q, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    KLAUNCH(s, K_STATE_CLEARANCE, k_state_clearance, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes_clearance, s->stream,
+            s->d_space, s->b_clr_q.p, n, s->params.padding, s->b_clr_out.p, s->b_clr_out.p + n, s->b_clr_wit.p);
+    HIP_TRY(hipGetLastError());
+    return clearance_results(s, n, clearance, parts, witness);
+}
+
+int smplx_cc_state_clearance_batch_device(smplx_space* s, const double* d_q, int n, double* d_clearance, double* d_parts,
+                                          int32_t* d_witness, void* stream)
+{
+    if (!s || !d_q || !d_clearance || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (s->lds_bytes_clearance > 160 * 1024) return set_error(SMPLX_E_LIMIT, kClearanceLds);
+    KLAUNCH(s, K_STATE_CLEARANCE, k_state_clearance, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes_clearance,
+            (hipStream_t)stream, s->d_space, d_q, n, s->params.padding, d_clearance, d_parts, d_witness);
+    HIP_TRY(hipGetLastError());
+    return SMPLX_OK;
+}
+
+int smplx_cc_edge_clearance_batch(smplx_space* s, const double* a, const double* b, int n, double* clearance, double* parts,
+                                  int32_t* witness)
+{
+    if (!s || !a || !b || !clearance || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (!sane_values(a, (size_t)n * s->N) || !sane_values(b, (size_t)n * s->N))
+        return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    if (s->lds_bytes_clearance > 160 * 1024) return set_error(SMPLX_E_LIMIT, kClearanceLds);
+    int e;
+    if ((e = s->b_clr_q.reserve((size_t)n * s->N))) return e;
+    if ((e = s->b_clr_q2.reserve((size_t)n * s->N))) return e;
+    if ((e = s->b_clr_out.reserve((size_t)n * 3))) return e;
+    if ((e = s->b_clr_wit.reserve((size_t)n * 4))) return e;
+    HIP_TRY(hipMemcpyAsync(s->b_clr_q.p, a, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->b_clr_q2.p, b, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    KLAUNCH(s, K_EDGE_CLEARANCE, k_edge_clearance, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->lds_bytes_clearance, s->stream,
+            s->d_space, s->b_clr_q.p, s->b_clr_q2.p, n, s->params.padding, s->b_clr_out.p, s->b_clr_out.p + n, s->b_clr_wit.p);
+    HIP_TRY(hipGetLastError());
+    return clearance_results(s, n, clearance, parts, witness);
 }
 
 // ---- attached bodies -------------------------------------------------------------------------------------------------

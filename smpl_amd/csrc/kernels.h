@@ -39,6 +39,11 @@ static inline size_t smplx_lds_bytes(size_t blob_bytes, int nroot, int nslots, i
 {
     return smplx_lds_bytes_n(blob_bytes, nroot, nslots, nvars, stack_bytes, SMPLX_BLOCK);
 }
+// the clearance kernels (clearance.h clearance_lds): a root position for every tree, the saved transforms in LDS in both builds
+static inline size_t smplx_clearance_lds_bytes(size_t blob_bytes, int ntrees, int nslots, int nvars, int stack_bytes)
+{
+    return smplx_lds_bytes_n(blob_bytes, ntrees, nslots, nvars, stack_bytes, SMPLX_BLOCK);
+}
 
 // most states that 128 consecutive edges of the (state, primitive) grid belong to
 static inline int smplx_step_states(int nprims) { return (SMPLX_BLOCK - 2 + nprims) / nprims + 1; }
@@ -56,7 +61,8 @@ static inline bool smplx_step_claim_fits(long long blocks)
     X(STATE_PREP, k_state_prep) X(EXPAND, k_expand) X(PIPE_PREP, k_pipe_prep) X(PIPE_SETUP, k_pipe_setup) \
     X(PIPE_CONFIGS, k_pipe_configs) X(PIPE_FINISH, k_pipe_finish) X(SMALL_BATCH, k_small_batch) X(EDGE_VALID, k_edge_valid) \
     X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
-    X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block)
+    X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block) \
+    X(STATE_CLEARANCE, k_state_clearance) X(EDGE_CLEARANCE, k_edge_clearance)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
@@ -113,6 +119,10 @@ __global__ void k_heuristic(const SmplxSpaceDev* S, const double* Q, int n, int*
 __global__ void k_planning_pose(const SmplxSpaceDev* S, const double* Q, int n, double* out_T);
 __global__ void k_sphere_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
 __global__ void k_attached_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
+__global__ void k_state_clearance(const SmplxSpaceDev* S, const double* Q, int n, double padding, double* out, double* out_parts,
+                                  int* out_witness);
+__global__ void k_edge_clearance(const SmplxSpaceDev* S, const double* Aq, const double* Bq, int n, double padding, double* out,
+                                 double* out_parts, int* out_witness);
 __global__ void k_table_insert(const SmplxSpaceDev* S, const SmplxSpaceDev* const* stab, const int* items, int n, int nvars);
 __global__ void k_bfs_metric(SmplxGridDev grid, SmplxBfsDev bfs, const double* xyz, int n, double* out);
 __global__ void k_bfs_init(SmplxGridDev g, int wall_thr, int nbx, int nby, int nbz, int* dist);

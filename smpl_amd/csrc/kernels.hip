@@ -18,6 +18,9 @@
 //   small_batch.h       k_small_batch: one block per state, and the lane functions k_search is built from
 //   query_kernels.h     k_edge_valid, k_state_valid, k_heuristic, k_planning_pose, k_sphere_positions,
 //                       k_attached_positions, k_bfs_metric: batch queries of the C-ABI
+//   clearance.h         distance to collision of a configuration and of an edge: leaf spheres against the grid, branch
+//                       and bound over the checked pairs and the attached bodies
+//   clearance_kernels.h k_state_clearance, k_edge_clearance: the clearance queries of the C-ABI
 //   bfs_kernels.h       k_bfs_*: label-correcting 26-connected BFS over 8x8x8 bricks (bfs3d.cpp:507-547)
 //   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query; k_search_table_fill, k_heap_ops, k_table_probe_ops
 //
@@ -43,5 +46,7 @@
 #include "step_block.h"
 #include "small_batch.h"
 #include "query_kernels.h"
+#include "clearance.h"
+#include "clearance_kernels.h"
 #include "bfs_kernels.h"
 #include "search_kernel.h"

@@ -204,6 +204,7 @@ struct smplx_space {
     int N = 0, M = 0;
     size_t lds_bytes = 0, blob_bytes = 0;
     size_t lds_bytes_valid = 0;      // k_state_valid, k_edge_valid, k_pipe_configs: in the per-robot build they keep the saved link transforms in registers
+    size_t lds_bytes_clearance = 0;  // k_state_clearance, k_edge_clearance (kernels.h smplx_clearance_lds_bytes)
     int lds_nroot = 0;   // root-position slots per thread in LDS: none in the per-robot build (they live in registers there)
     smplx::KernelSet ks;       // per-robot kernels (specialize.h), generic ones with SMPLX_SPACE_GENERIC_KERNELS or SMPLX_SPECIALIZE=0
     std::string specialize_note;   // why the per-robot build is absent, if it is
@@ -220,6 +221,9 @@ struct smplx_space {
     DevBuf<unsigned char> b_flags;
     DevBuf<int32_t> b_coord, b_h, b_way;
     DevBuf<unsigned long long> b_counters;
+    // the clearance queries' own scratch: they never touch a buffer a search or a frontier batch may hold between calls
+    DevBuf<double> b_clr_q, b_clr_q2, b_clr_out;   // b_clr_out: n clearances, then n x 2 parts
+    DevBuf<int32_t> b_clr_wit;
     DevBuf<const SmplxSpaceDev*> b_stab;   // cross-query batches (smplx_plan_multi): the query table, owned by the leading space
     FrontierBatch batch;           // the space's own frontier batches (issued on `stream`)
     // the states of the frontier batch in flight
