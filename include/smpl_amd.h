@@ -317,7 +317,7 @@ int smplx_bfs_levels(const smplx_space* s);
 /* ---- ManipLattice (smpl/include/smpl/graph/manip_lattice.h:63-307) ---- */
 /* successor evaluation for B arbitrary parent states: the loop body of GetSuccs
  * (manip_lattice.cpp:254-305) for every (state, primitive), dense outputs indexed [state][prim]:
- * flags (SMPLX_F_* of device_types.h: 1 valid, 2 goal, 0x10 inactive, 0x20 limits, 0x40 collision),
+ * flags (SMPLX_F_* of device_types.h: 1 valid, 2 goal, 4 unchecked (smplx_lazy_expand_batch only), 0x10 inactive, 0x20 limits, 0x40 collision),
  * coord[nvars], q[nvars], h, cost, lookups.  Any output may be NULL.
  * Defined entries: flags everywhere; coord, h and cost where flags has the valid bit (h and cost are 0 elsewhere); q on every
  * edge that is not inactive; lookups on every edge not in collision (a colliding edge's tally stops at its first colliding
@@ -386,6 +386,61 @@ int smplx_start_id(const smplx_space* s);
 int smplx_goal_id(const smplx_space* s);   /* always 0 (manip_lattice.cpp:122) */
 /* GetSuccs (manip_lattice.cpp:219-313): valid successors of a state id in primitive order */
 int smplx_get_succs(smplx_space* s, int id, int32_t* succs, int32_t* costs, int cap, int* n);
+/* ---- lazy successors (RobotPlanningSpace::GetLazySuccs / GetTrueCost, smpl/include/smpl/graph/robot_planning_space.h:124-130) ----
+ * What a lazy planner (the reference's larastar, lmhastar) calls instead of GetSuccs: successors first, without the edge
+ * check that dominates an expansion, and the check later, only for the edges the search comes to rely on.
+ *
+ * smplx_get_lazy_succs: ManipLattice::GetLazySuccs (manip_lattice.cpp:1012-1090).  The goal id has no successors.  For any
+ * other state every action of the primitives that are active there (GetSuccs' gating, manip_lattice_action_space.cpp:339-449)
+ * gets its state -- getOrCreateState, with NO joint-limit and NO collision test in front -- in primitive order: the goal id
+ * where isGoal holds for the action, else the state's id.  Every cost is 1000 (the three-argument cost(), :1388-1412) and
+ * every true_cost flag of the reference is false, so there is no array for it.  A lazy caller therefore sees ids an eager
+ * caller never would (states out of limits or in collision are created too); ids follow the caller's own call sequence,
+ * and smplx_get_succs, smplx_get_lazy_succs and smplx_set_start of one space draw from one counter.  The first call on an id
+ * runs one kernel launch (the states of smplx_hint_frontier ride along; env SMPLX_LAZY_RIDERS = most of them, default 64);
+ * later calls return the stored list and create nothing.  n gets the count, succs / costs (may be NULL) the first cap entries.
+ *
+ * smplx_get_true_cost: ManipLattice::GetTrueCost (manip_lattice.cpp:1094-1167).  The parent's actions are applied again;
+ * those whose coordinate equals the child's in every variable -- for child == goal id: those for which isGoal holds -- go
+ * through checkAction (:1511-1580: joint limits, then the edge parent -> successor, attached bodies included) until one
+ * passes.  *cost = 1000 (int(1000 * 1), :1156) if one does, else -1.  Answers are cached per (parent, child); a miss also
+ * evaluates, in the same launch, the other unevaluated edges of the parent's lazy list and of the lists of the states
+ * expanded last (env SMPLX_TRUE_COST_PARENTS = how many, default 8, 0 = the parent alone).
+ * smplx_true_cost_batch: the same for n pairs in one launch.  prims (may be NULL): the lowest-indexed matching primitive
+ * that passed, -1 if none; nmatch (may be NULL): the number of matching actions.  n == 0 is SMPLX_OK.
+ *
+ * Refused like smplx_get_succs (SMPLX_E_STATE): no goal, a grid edited or bodies attached / detached after the goal was
+ * set.  The reference reads a state without a coordinate when the parent is the goal id or an id is unknown: here the
+ * parent being the goal id is SMPLX_E_ARG, an unknown id SMPLX_E_STATE.  On failure the list is empty and *cost is -1; the
+ * first error of smplx_get_lazy_succs / smplx_get_true_cost stays on the space (smplx_space_status).  Setting the goal again
+ * drops the lists and the cache with the rest of the lattice. */
+int smplx_get_lazy_succs(smplx_space* s, int id, int32_t* succs, int32_t* costs, int cap, int* n);
+int smplx_get_true_cost(smplx_space* s, int parent_id, int child_id, int32_t* cost);
+int smplx_true_cost_batch(smplx_space* s, const int32_t* parent_ids, const int32_t* child_ids, int n, int32_t* costs, int32_t* prims,
+                          int32_t* nmatch);
+/* The loop body of GetLazySuccs (manip_lattice.cpp:1040-1087) for B arbitrary parent states, dense outputs indexed
+ * [state][prim]; it creates no state.  flags: 0x10 (inactive) where the primitive has no action at the state, else 4
+ * ("generated, unchecked"), plus 2 where isGoal holds.  coord[nvars], q[nvars], h (BFS cost of the planning link's cell)
+ * and succ_id (the state's id in the device table, -1 if the coordinate has not been committed) are defined where the
+ * primitive is active; elsewhere coord and q are 0 in the host form and untouched in the device form, h is 0, succ_id -1.
+ * Any output may be NULL (the device form needs d_flags).  The device form launches on `stream` and does not synchronise. */
+int smplx_lazy_expand_batch(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* coord, double* succ_q, int32_t* h,
+                            int32_t* succ_id);
+int smplx_lazy_expand_batch_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,
+                                   int32_t* d_h, int32_t* d_succ_id, void* stream);
+/* GetTrueCost (manip_lattice.cpp:1094-1167) without ids: item i is the parent's joint values parent_q[i], and the child's
+ * coordinate child_coord[i] or, where goal_edge[i] != 0, "the child is the goal" (the coordinate is then ignored; goal_edge
+ * NULL = no such item).  costs / prims / nmatch as smplx_true_cost_batch.  The device form also takes
+ * smplx_true_cost_work_doubles(s, n) doubles of scratch (d_work_q), needs every pointer but d_prims and d_nmatch, launches on `stream` and does not synchronise. */
+int smplx_true_cost_q_batch(smplx_space* s, const double* parent_q, const int32_t* child_coord, const uint8_t* goal_edge, int n,
+                            int32_t* costs, int32_t* prims, int32_t* nmatch);
+size_t smplx_true_cost_work_doubles(const smplx_space* s, int n);
+int smplx_true_cost_q_batch_device(smplx_space* s, const double* d_parent_q, const int32_t* d_child_coord, const uint8_t* d_goal_edge,
+                                   int n, double* d_work_q, int32_t* d_costs, int32_t* d_prims, int32_t* d_nmatch, void* stream);
+/* running totals since the goal was last set: out[0] kernel launches of smplx_get_lazy_succs, [1] its calls served without
+ * one, [2] launches of smplx_get_true_cost / smplx_true_cost_batch, [3] edges they evaluated, [4] pairs answered from the
+ * cache, [5] pairs that were not */
+int smplx_lazy_counters(const smplx_space* s, int64_t out[6]);
 /* optional: ids the caller expects to expand soon (top of OPEN); they ride along in the next batch.  A caller that
  * never hints (an unchanged SBPL planner) still gets frontier batches: the space mirrors the g-values the caller's
  * GetSuccs sequence implies (arastar.cpp:546-551) and lets the unevaluated states with the smallest g + w*h ride

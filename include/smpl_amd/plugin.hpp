@@ -180,6 +180,20 @@ public:
     // DiscreteSpaceInformation side
     virtual void GetSuccs(int state_id, std::vector<int>* succs, std::vector<int>* costs) = 0;     // :135-138
     virtual void GetPreds(int state_id, std::vector<int>* preds, std::vector<int>* costs) = 0;     // :172-175
+    // lazy variants (:124-130); the defaults are GetSuccs with every cost true and its cost (robot_planning_space.cpp:182-200)
+    virtual void GetLazySuccs(int state_id, std::vector<int>* succs, std::vector<int>* costs, std::vector<bool>* true_costs)
+    {
+        GetSuccs(state_id, succs, costs);
+        true_costs->assign(succs->size(), true);
+    }
+    virtual int GetTrueCost(int parent_id, int child_id)
+    {
+        std::vector<int> succs, costs;
+        GetSuccs(parent_id, &succs, &costs);
+        for (size_t i = 0; i < succs.size(); ++i)
+            if (succs[i] == child_id) return costs[i];
+        return -1;
+    }
     virtual void PrintState(int state_id, bool verbose, FILE* f = nullptr) = 0;                    // :177-180
     virtual int GetGoalHeuristic(int state_id)                                                    // robot_planning_space.cpp:133-140
     {
@@ -448,6 +462,40 @@ public:
         }
         succs->insert(succs->end(), s.begin(), s.begin() + n);
         costs->insert(costs->end(), c.begin(), c.begin() + n);
+    }
+    // manip_lattice.cpp:1012-1090: every active action's state, created without a limits or collision test; cost 1000,
+    // true_cost false.  On an engine error the list stays empty, as in GetSuccs.
+    void GetLazySuccs(int state_id, std::vector<int>* succs, std::vector<int>* costs, std::vector<bool>* true_costs) override
+    {
+        const int cap = ctx_->nprims();
+        std::vector<int32_t> s(cap), c(cap);
+        int n = 0;
+        if (smplx_get_lazy_succs(ctx_->space(), state_id, s.data(), c.data(), cap, &n) != SMPLX_OK) {
+            if (!logged_) { fprintf(stderr, "smpl_amd: GetLazySuccs(%d) failed: %s\n", state_id, smplx_last_error()); logged_ = true; }
+            return;
+        }
+        succs->insert(succs->end(), s.begin(), s.begin() + n);
+        costs->insert(costs->end(), c.begin(), c.begin() + n);
+        true_costs->insert(true_costs->end(), (size_t)n, false);
+    }
+    // manip_lattice.cpp:1094-1167: 1000 if an action of the parent that lands in the child's cell (child == goal id: that
+    // satisfies the goal) passes limits and the edge check, else -1; -1 on an engine error too (engineStatus())
+    int GetTrueCost(int parent_id, int child_id) override
+    {
+        int32_t cost = -1;
+        if (smplx_get_true_cost(ctx_->space(), parent_id, child_id, &cost) != SMPLX_OK) {
+            if (!logged_) { fprintf(stderr, "smpl_amd: GetTrueCost(%d, %d) failed: %s\n", parent_id, child_id, smplx_last_error()); logged_ = true; }
+            return -1;
+        }
+        return cost;
+    }
+    // not in the reference: many (parent, child) pairs in one launch; false on an engine error
+    bool GetTrueCosts(const std::vector<int>& parent_ids, const std::vector<int>& child_ids, std::vector<int>* costs)
+    {
+        if (parent_ids.size() != child_ids.size()) return false;
+        costs->assign(parent_ids.size(), -1);
+        return smplx_true_cost_batch(ctx_->space(), parent_ids.data(), child_ids.data(), (int)parent_ids.size(), costs->data(), nullptr,
+                                     nullptr) == SMPLX_OK;
     }
     void GetPreds(int, std::vector<int>*, std::vector<int>*) override {}   // "GetPreds unimplemented" (manip_lattice.cpp:1238-1241)
     // manip_lattice.cpp:152-197

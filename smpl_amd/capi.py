@@ -40,6 +40,8 @@ SYMBOLS = [
     "smplx_attach_body", "smplx_detach_body", "smplx_attached_bodies", "smplx_attached_nodes", "smplx_cc_attached_positions",
     "smplx_set_goal_pose", "smplx_set_goals_pose_multi", "smplx_goal_orientation", "smplx_planning_pose_batch", "smplx_rpy_angle",
     "smplx_cc_state_clearance_batch", "smplx_cc_state_clearance_batch_device", "smplx_cc_edge_clearance_batch",
+    "smplx_get_lazy_succs", "smplx_get_true_cost", "smplx_true_cost_batch", "smplx_lazy_expand_batch", "smplx_lazy_expand_batch_device",
+    "smplx_true_cost_q_batch", "smplx_true_cost_work_doubles", "smplx_true_cost_q_batch_device", "smplx_lazy_counters",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -616,6 +618,77 @@ class Space:
         s = np.zeros(self.M, np.int32); k = np.zeros(self.M, np.int32); n = C.c_int()
         _chk(lib().smplx_get_succs(self.h, i, _p(s, _ip), _p(k, _ip), self.M, C.byref(n)))
         return s[:n.value].copy(), k[:n.value].copy()
+
+    # ---- lazy successors: GetLazySuccs / GetTrueCost (include/smpl_amd.h has the specification) ----
+    def get_lazy_succs(self, i):
+        """(ids, costs) of GetLazySuccs(i): every active action's state, unchecked; the goal id for a goal successor"""
+        s = np.zeros(self.M, np.int32); k = np.zeros(self.M, np.int32); n = C.c_int()
+        lib().smplx_get_lazy_succs.argtypes = [C.c_void_p, C.c_int, _ip, _ip, C.c_int, C.POINTER(C.c_int)]
+        _chk(lib().smplx_get_lazy_succs(self.h, i, _p(s, _ip), _p(k, _ip), self.M, C.byref(n)))
+        return s[:n.value].copy(), k[:n.value].copy()
+
+    def get_true_cost(self, parent, child):
+        """GetTrueCost(parent, child): 1000, or -1 when no matching action passes limits and the edge check"""
+        c = C.c_int32()
+        lib().smplx_get_true_cost.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        _chk(lib().smplx_get_true_cost(self.h, parent, child, C.byref(c)))
+        return c.value
+
+    def true_cost_batch(self, parents, children):
+        """(costs, prims, nmatch) of n (parent id, child id) pairs in one launch"""
+        a = np.ascontiguousarray(parents, np.int32).reshape(-1); b = np.ascontiguousarray(children, np.int32).reshape(-1)
+        assert a.shape == b.shape
+        n = a.shape[0]
+        cost = np.zeros(n, np.int32); prim = np.zeros(n, np.int32); nm = np.zeros(n, np.int32)
+        lib().smplx_true_cost_batch.argtypes = [C.c_void_p, _ip, _ip, C.c_int, _ip, _ip, _ip]
+        _chk(lib().smplx_true_cost_batch(self.h, _p(a, _ip), _p(b, _ip), n, _p(cost, _ip), _p(prim, _ip), _p(nm, _ip)))
+        return cost, prim, nm
+
+    def lazy_expand_batch(self, q):
+        """Dense rows of k_lazy_succs for arbitrary parent states: flags (0x10 inactive; else 4, plus 2 for a goal), coord, q,
+        h and succ_id (device-table id, -1 = unknown), indexed [state][prim].  Creates no state."""
+        q = _f64(q).reshape(-1, self.N); B = q.shape[0]; M, N = self.M, self.N
+        flags = np.zeros((B, M), np.uint8); coord = np.zeros((B, M, N), np.int32); sq = np.zeros((B, M, N))
+        h = np.zeros((B, M), np.int32); sid = np.zeros((B, M), np.int32)
+        lib().smplx_lazy_expand_batch.argtypes = [C.c_void_p, _dp, C.c_int, _up, _ip, _dp, _ip, _ip]
+        _chk(lib().smplx_lazy_expand_batch(self.h, _p(q, _dp), B, _p(flags, _up), _p(coord, _ip), _p(sq, _dp), _p(h, _ip), _p(sid, _ip)))
+        return dict(flags=flags, coord=coord, q=sq, h=h, succ_id=sid)
+
+    def lazy_expand_batch_device(self, d_q, B, d_flags, d_coord, d_sq, d_h, d_id, stream):
+        """Raw device pointers (ints; all but d_flags may be None); launches on `stream`, does not synchronise."""
+        lib().smplx_lazy_expand_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        _chk(lib().smplx_lazy_expand_batch_device(self.h, d_q, B, d_flags, d_coord, d_sq, d_h, d_id, stream))
+
+    def true_cost_q_batch(self, parent_q, child_coord, goal_edge=None):
+        """(costs, prims, nmatch) of n items of k_true_cost: a parent's joint values and either the child's coordinate or,
+        where goal_edge is set, "the child is the goal" """
+        q = _f64(parent_q).reshape(-1, self.N); n = q.shape[0]
+        c = np.ascontiguousarray(child_coord, np.int32).reshape(n, self.N)
+        g = np.zeros(n, np.uint8) if goal_edge is None else np.ascontiguousarray(goal_edge, np.uint8).reshape(n)
+        cost = np.zeros(n, np.int32); prim = np.zeros(n, np.int32); nm = np.zeros(n, np.int32)
+        lib().smplx_true_cost_q_batch.argtypes = [C.c_void_p, _dp, _ip, _up, C.c_int, _ip, _ip, _ip]
+        _chk(lib().smplx_true_cost_q_batch(self.h, _p(q, _dp), _p(c, _ip), _p(g, _up), n, _p(cost, _ip), _p(prim, _ip), _p(nm, _ip)))
+        return cost, prim, nm
+
+    def true_cost_work_doubles(self, n):
+        """doubles of scratch true_cost_q_batch_device needs for n items"""
+        lib().smplx_true_cost_work_doubles.restype = C.c_size_t
+        lib().smplx_true_cost_work_doubles.argtypes = [C.c_void_p, C.c_int]
+        return lib().smplx_true_cost_work_doubles(self.h, n)
+
+    def true_cost_q_batch_device(self, d_parent_q, d_child_coord, d_goal_edge, n, d_work_q, d_costs, d_prims, d_nmatch, stream):
+        """Raw device pointers (ints; d_prims and d_nmatch may be None); launches on `stream`, does not synchronise."""
+        lib().smplx_true_cost_q_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        _chk(lib().smplx_true_cost_q_batch_device(self.h, d_parent_q, d_child_coord, d_goal_edge, n, d_work_q, d_costs, d_prims,
+                                                  d_nmatch, stream))
+
+    def lazy_counters(self):
+        """smplx_lazy_counters as a dict"""
+        out = (C.c_int64 * 6)()
+        lib().smplx_lazy_counters.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        _chk(lib().smplx_lazy_counters(self.h, out))
+        names = ("lazy_launches", "lazy_served", "true_cost_launches", "edges_evaluated", "cache_hits", "cache_misses")
+        return dict(zip(names, (int(x) for x in out)))
 
     def hint_frontier(self, ids):
         ids = np.ascontiguousarray(ids, np.int32)

@@ -39,7 +39,8 @@ enum { SMPLX_MP_LONG = -1, SMPLX_MP_SNAP_RPY = 0, SMPLX_MP_SNAP_XYZ = 1, SMPLX_M
 // goal types (smpl/include/smpl/types.h)
 enum { SMPLX_GOAL_XYZ = 0, SMPLX_GOAL_XYZ_RPY = 1, SMPLX_GOAL_JOINT = 2 };
 // per-successor flags
-enum { SMPLX_F_VALID = 1, SMPLX_F_GOAL = 2, SMPLX_F_INACTIVE = 0x10, SMPLX_F_LIMITS = 0x20, SMPLX_F_COLLISION = 0x40,
+enum { SMPLX_F_VALID = 1, SMPLX_F_GOAL = 2, SMPLX_F_UNCHECKED = 4 /* k_lazy_succs: generated, neither limits nor collision tested */,
+       SMPLX_F_INACTIVE = 0x10, SMPLX_F_LIMITS = 0x20, SMPLX_F_COLLISION = 0x40,
        SMPLX_F_DEFERRED = 0x80 /* internal: edge did not fit the work list, resolved by a fused pass */ };
 
 struct SmplxJoint {          // depth-first pre-order; the child link of joint i is "link i"

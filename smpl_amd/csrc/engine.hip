@@ -1,7 +1,7 @@
 // smpl_amd/csrc/engine.hip -- host side of the C-ABI (include/smpl_amd.h): the entry points, which check their
 // arguments and call into the headers below.  The records behind the handles are in space.h, the ManipLattice state
-// table in lattice.h, the kernel launches and frontier batches in step.h, the two ARA* callers in ara_search.h and
-// search_host.h.  There is no CPU fallback: every query below runs the gfx950 kernels and fails with SMPLX_E_HIP when
+// table in lattice.h, the kernel launches and frontier batches in step.h, the lazy successor pair in lazy.h, the two
+// ARA* callers in ara_search.h and search_host.h.  There is no CPU fallback: every query below runs the gfx950 kernels and fails with SMPLX_E_HIP when
 // no GPU is present.
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,7 @@
 #include "device_table.h"
 #include "step.h"
 #include "search_host.h"
+#include "lazy.h"
 #include "ara_search.h"
 #include "multi_query.h"
 #include "path_tools.h"
@@ -255,6 +256,8 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
     s->step.fused_mode = (params->flags & SMPLX_SPACE_FUSED) != 0;
     if (params->flags & SMPLX_SPACE_NO_SMALL_KERNEL) s->small.batch_max = 0;
     if (const char* e = getenv("SMPLX_AUTO_SPECULATE")) s->spec.auto_spec = std::max(0, atoi(e));
+    if (const char* e = getenv("SMPLX_LAZY_RIDERS")) s->lazy.riders = std::max(0, atoi(e));
+    if (const char* e = getenv("SMPLX_TRUE_COST_PARENTS")) s->lazy.ride_parents = std::max(0, atoi(e));
     s->N = s->model.dev.nvars;
     if (!smplx::load_mprim_text(mprim_text, params->resolutions, s->N, s->actions)) {
         const std::string err = s->actions.error;
@@ -1476,6 +1479,92 @@ int smplx_get_succs(smplx_space* s, int id, int32_t* succs, int32_t* costs, int 
         if (succs) succs[i] = ps[i];
         if (costs) costs[i] = pc[i];
     }
+    return SMPLX_OK;
+}
+
+// ---- lazy successors: GetLazySuccs / GetTrueCost (include/smpl_amd.h; kernels: lazy_kernels.h, host: lazy.h) ----------
+
+int smplx_get_lazy_succs(smplx_space* s, int id, int32_t* succs, int32_t* costs, int cap, int* n)
+{
+    if (n) *n = 0;
+    if (!s || !n) return set_error(SMPLX_E_ARG, "null argument");
+    if (int e = lazy_guard(s)) return lazy_keep_status(s, e);
+    const int32_t* ps = nullptr;
+    int cnt = 0;
+    if (int e = get_lazy_succs(s, id, &ps, &cnt)) return lazy_keep_status(s, e);
+    *n = cnt;
+    for (int i = 0; i < cnt && i < cap; ++i) {
+        if (succs) succs[i] = ps[i];
+        if (costs) costs[i] = SMPLX_LAZY_COST;
+    }
+    return SMPLX_OK;
+}
+
+int smplx_true_cost_batch(smplx_space* s, const int32_t* parent_ids, const int32_t* child_ids, int n, int32_t* costs, int32_t* prims,
+                          int32_t* nmatch)
+{
+    if (!s || n < 0 || (n > 0 && (!parent_ids || !child_ids || !costs))) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (int e = lazy_guard(s)) return e;
+    return true_cost_pairs(s, parent_ids, child_ids, n, costs, prims, nmatch, false);
+}
+
+int smplx_get_true_cost(smplx_space* s, int parent_id, int child_id, int32_t* cost)
+{
+    if (cost) *cost = -1;
+    if (!s || !cost) return set_error(SMPLX_E_ARG, "null argument");
+    if (int e = lazy_guard(s)) return lazy_keep_status(s, e);
+    const int32_t p = parent_id, c = child_id;
+    return lazy_keep_status(s, true_cost_pairs(s, &p, &c, 1, cost, nullptr, nullptr, true));
+}
+
+int smplx_lazy_expand_batch(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* coord, double* succ_q, int32_t* h,
+                            int32_t* succ_id)
+{
+    if (!s || !q || B < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (B == 0) return SMPLX_OK;
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "set a goal first (the primitives are gated by goal distance)");
+    if (!sane_values(q, (size_t)B * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    if (int e = pull_lattice(s)) return e;
+    return lazy_rows(s, q, B, flags, coord, succ_q, h, succ_id, true);
+}
+
+int smplx_lazy_expand_batch_device(smplx_space* s, const double* d_q, int B, uint8_t* d_flags, int32_t* d_coord, double* d_succ_q,
+                                   int32_t* d_h, int32_t* d_succ_id, void* stream)
+{
+    if (!s || !d_q || !d_flags || B <= 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "set a goal first");
+    if (int e = pull_lattice(s)) return e;
+    return launch_lazy_succs(s, d_q, B, d_flags, d_coord, d_succ_q, d_h, d_succ_id, (hipStream_t)stream, true);
+}
+
+int smplx_true_cost_q_batch(smplx_space* s, const double* parent_q, const int32_t* child_coord, const uint8_t* goal_edge, int n,
+                            int32_t* costs, int32_t* prims, int32_t* nmatch)
+{
+    if (!s || n < 0 || (n > 0 && (!parent_q || !child_coord || !costs))) return set_error(SMPLX_E_ARG, "bad argument");
+    if (n == 0) return SMPLX_OK;
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "set a goal first (the primitives are gated by goal distance)");
+    if (!sane_values(parent_q, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    return true_cost_items(s, parent_q, child_coord, goal_edge, n, costs, prims, nmatch);
+}
+
+size_t smplx_true_cost_work_doubles(const smplx_space* s, int n)
+{
+    return s && n > 0 ? (size_t)n * s->N * SMPLX_TRUE_COST_LANES : 0;
+}
+
+int smplx_true_cost_q_batch_device(smplx_space* s, const double* d_parent_q, const int32_t* d_child_coord, const uint8_t* d_goal_edge,
+                                   int n, double* d_work_q, int32_t* d_costs, int32_t* d_prims, int32_t* d_nmatch, void* stream)
+{
+    if (!s || !d_parent_q || !d_child_coord || !d_goal_edge || !d_work_q || !d_costs || n <= 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "set a goal first");
+    return launch_true_cost(s, d_parent_q, d_child_coord, d_goal_edge, n, d_work_q, d_costs, d_prims, d_nmatch, (hipStream_t)stream);
+}
+
+int smplx_lazy_counters(const smplx_space* s, int64_t out[6])
+{
+    if (!s || !out) return set_error(SMPLX_E_ARG, "null argument");
+    for (int k = 0; k < 6; ++k) out[k] = s->lazy.counters[k];
     return SMPLX_OK;
 }
 

@@ -23,6 +23,8 @@
 #define SMPLX_WORK_COUNTER_BYTES 16384
 #define SMPLX_SEARCH_STATIC_LDS (44 * 1024)   // static LDS of k_search (2 x ExpandLds + SearchLds + header and primitives copies), an upper bound
 #define SMPLX_GLOBAL_AS __attribute__((address_space(1)))   // device code: a pointer known to be device memory (model_lds.h as_global)
+#define SMPLX_LAZY_COST 1000      // every cost of the lazy pair: the three-argument cost() (manip_lattice.cpp:1388-1412), int(1000 * 1) (:1156)
+#define SMPLX_TRUE_COST_LANES 8    // lanes that share an item of k_true_cost: the waypoints of its edge are dealt out to them
 #define SMPLX_TALLIES 6           // per-block tallies (tally_block)     // per-thread DFS stack (node indices, one byte each)
 
 // dynamic LDS bytes: the packed model, plus (collision kernels) per-thread scratch
@@ -62,7 +64,8 @@ static inline bool smplx_step_claim_fits(long long blocks)
     X(PIPE_CONFIGS, k_pipe_configs) X(PIPE_FINISH, k_pipe_finish) X(SMALL_BATCH, k_small_batch) X(EDGE_VALID, k_edge_valid) \
     X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
     X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block) \
-    X(STATE_CLEARANCE, k_state_clearance) X(EDGE_CLEARANCE, k_edge_clearance)
+    X(STATE_CLEARANCE, k_state_clearance) X(EDGE_CLEARANCE, k_edge_clearance) X(LAZY_SUCCS, k_lazy_succs) \
+    X(TRUE_COST, k_true_cost)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
@@ -123,6 +126,10 @@ __global__ void k_state_clearance(const SmplxSpaceDev* S, const double* Q, int n
                                   int* out_witness);
 __global__ void k_edge_clearance(const SmplxSpaceDev* S, const double* Aq, const double* Bq, int n, double padding, double* out,
                                  double* out_parts, int* out_witness);
+__global__ void k_lazy_succs(const SmplxSpaceDev* S, const double* Q, int B, unsigned char* out_flags, int* out_coord, double* out_q,
+                             int* out_h, int* out_id);
+__global__ void k_true_cost(const SmplxSpaceDev* S, const double* Pq, const int* child_coord, const unsigned char* goal_edge, int n,
+                            double* work_q, int* out_cost, int* out_prim, int* out_nmatch);
 __global__ void k_table_insert(const SmplxSpaceDev* S, const SmplxSpaceDev* const* stab, const int* items, int n, int nvars);
 __global__ void k_bfs_metric(SmplxGridDev grid, SmplxBfsDev bfs, const double* xyz, int n, double* out);
 __global__ void k_bfs_init(SmplxGridDev g, int wall_thr, int nbx, int nby, int nbz, int* dist);

@@ -7,6 +7,7 @@
 
 #include <cstdint>
 #include <cstring>
+#include <unordered_map>
 #include <vector>
 
 namespace {
@@ -92,6 +93,19 @@ struct Lattice {
     std::vector<int32_t> done_succ, done_cost, done_prim;
     std::vector<int32_t> eval_count;    // per id: evaluated (active) primitives, for committed_evals
     std::vector<uint32_t> g_est;        // per id: the g-value a plain GetSuccs caller's expansions imply (PlainSpeculation)
+    // lazy successors (GetLazySuccs, manip_lattice.cpp:1012-1090).  lazy_row: the state's row of k_lazy_succs outputs in
+    // the lz_* arrays (M entries a row), evaluated by its own call or as a rider of another's, -1 = not evaluated.
+    // lazy_off / lazy_cnt: its committed list in lazy_succ (0 for a goal successor) / lazy_goal / lazy_prim.
+    std::vector<int64_t> lazy_row, lazy_off;
+    std::vector<int32_t> lazy_cnt;
+    std::vector<unsigned char> lz_flags;
+    std::vector<int32_t> lz_coord, lz_h, lz_known;
+    std::vector<double> lz_q;
+    std::vector<int32_t> lazy_succ, lazy_prim;
+    std::vector<unsigned char> lazy_goal;
+    // GetTrueCost (manip_lattice.cpp:1094-1167): (parent id << 32 | child id) -> what k_true_cost answered
+    struct TrueCost { int32_t cost, prim, nmatch; };
+    std::unordered_map<uint64_t, TrueCost> true_cost;
 
     int size() const { return (int)h_of_id.size(); }
 
@@ -101,6 +115,9 @@ struct Lattice {
         N = n;
         recs.clear(); rec_coord.clear(); rec_q.clear();
         done_succ.clear(); done_cost.clear(); done_prim.clear();
+        lz_flags.clear(); lz_coord.clear(); lz_h.clear(); lz_known.clear(); lz_q.clear();
+        lazy_succ.clear(); lazy_prim.clear(); lazy_goal.clear();
+        true_cost.clear();
         table.init(N);
         start_id = -1;
         grow(0);
@@ -135,6 +152,9 @@ private:
         done_cnt.resize(total, 0);
         eval_count.resize(total, 0);
         g_est.resize(total, 1000000000u);
+        lazy_row.resize(total, -1);
+        lazy_off.resize(total, -1);
+        lazy_cnt.resize(total, 0);
     }
 };
 

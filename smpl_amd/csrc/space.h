@@ -165,6 +165,26 @@ struct AttachedBodies {
 
 const char* const kBodiesChanged = "bodies were attached or detached after the goal was set: cached successors are stale, set the goal again";
 
+// scratch and tallies of the lazy successor pair (lazy.h): its own buffers, like the clearance queries'
+struct LazyHost {
+    DevBuf<double> b_q, b_sq;
+    DevBuf<int32_t> b_coord, b_h, b_id, b_out;   // b_out: n costs, n primitives, n match counts
+    DevBuf<unsigned char> b_flags, b_goal;
+    int riders = 64;                 // most states that ride along with a GetLazySuccs miss (SMPLX_LAZY_RIDERS, 0 = none)
+    // binary min-heap of (heuristic, id) of the states GetLazySuccs created and has not evaluated: a caller that never hints
+    // (a lazy SBPL planner) gets the ones nearest the goal as riders -- a guess at its OPEN order that costs GPU work when
+    // wrong, never results
+    std::vector<std::pair<int32_t, int32_t>> pool;
+    // GetTrueCost misses: the unevaluated edges of the parent's lazy list ride along, and those of the `ride_parents` states
+    // whose lists were committed last (SMPLX_TRUE_COST_PARENTS, 0 = the parent alone) -- the edges a lazy search is likeliest
+    // to ask about next
+    int ride_parents = 8;
+    std::vector<int32_t> recent;     // ids in the order their lazy lists were committed
+    // [0] k_lazy_succs launches of GetLazySuccs, [1] GetLazySuccs calls served without one, [2] k_true_cost launches of
+    // GetTrueCost / the batch call, [3] edges they evaluated, [4] pairs answered from the cache, [5] pairs that were not
+    int64_t counters[6] = {0, 0, 0, 0, 0, 0};
+};
+
 struct Search;   // the host-driven ARA* (ara_search.h)
 
 // the device-resident ARA* of a query (search_host.h)
@@ -245,6 +265,7 @@ struct smplx_space {
     StepLaunch step;
     AttachedBodies att;
     DevSearch ds;
+    LazyHost lazy;
 };
 
 namespace {
@@ -281,6 +302,9 @@ void reset_lattice(smplx_space* s)
     s->spec.plain_mode = false;
     s->dt.pending_ins.clear();
     s->dt.count = 0;
+    for (int64_t& c : s->lazy.counters) c = 0;
+    s->lazy.pool.clear();
+    s->lazy.recent.clear();
     if (s->dt.d_table) (void)hipMemsetAsync(s->dt.d_table, 0, s->dt.cap * (size_t)s->hs.table.stride * sizeof(int32_t), s->stream);
 }
 
