@@ -91,6 +91,61 @@ long long smplx_grid_last_edit_cells(const smplx_grid* g);
 /* the field as smplx_grid_create takes it: d2[nx*ny*nz], x-major, z fastest */
 int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2);
 
+/* ---- world objects --------------------------------------------------------------------------------------------------
+ * CollisionSpace::insertObject / removeObject / moveShapes / insertShapes / removeShapes
+ * (sbpl_collision_checking/src/collision_space.cpp:228-275) over WorldCollisionModel
+ * (src/world_collision_model.cpp:193-280): named objects made of shapes at poses, voxelised on the GPU and kept in a
+ * registry on the grid.
+ * Every shape becomes a triangle mesh on the host exactly as the reference builds it (smpl/src/geometry/mesh_utils.cpp:
+ * box :39-112, sphere with 7 x 8 lines :116-204, cylinder with 16 rim points :208-264, cone :268-299; a MESH is the
+ * caller's vertices and index triples), its vertices go through the pose (R v + t, voxelize.cpp:608-615), and the
+ * SURFACE of the mesh is voxelised (fill = false, voxel_operations.cpp:319-402) by VoxelizeTriangle
+ * (smpl/include/smpl/geometry/detail/voxelize.hpp:46-180) on the PivotVoxelGrid whose pivot is the grid's origin
+ * (voxelize.cpp:1008-1035): voxel index i along an axis is cell i of the grid.  The arithmetic is the reference's, in
+ * binary64 without fused multiply-add, quirks included (edge p1-p2 of a triangle is never tested on its own).
+ * A shape's cell list holds each filled cell once, in ExtractVoxels order (x-major, z fastest, voxelize.cpp:207-222).
+ * Deliberate difference: only cells inside the grid are kept -- every triangle's candidate range is clipped to the grid
+ * -- where the reference keeps the outside points and addPointsToMap skips them (distance_map.hpp:312-316); the field is
+ * the same and a huge off-grid mesh cannot ask for an unbounded mask.
+ *
+ * pose: 3x4 row major (rotation | translation), world frame, like smplx_planning_pose_batch.  Planes and octomaps are
+ * not supported (SMPLX_E_ARG, like any unknown type).
+ * Refused with SMPLX_E_ARG: a null pointer, an empty id or one with a line break, n < 1, an unknown shape type,
+ * non-finite numbers (|x| >= 1e6), a dimension <= 0, a MESH without vertices or triangles or with an index outside
+ * [0, nvertices), an id already in the world (checkObjectInsert, world_collision_model.cpp:394-407) and, for remove
+ * and move, an id that is not (checkObjectRemove :414-417).  SMPLX_E_STATE: a grid created from a finished field
+ * (smplx_grid_create), which refuses objects as it refuses points.  A refused call changes nothing.
+ *
+ * insert adds each shape's list in order (:227-231): on a reference-counted grid a cell covered by two shapes counts
+ * twice.  remove takes the stored lists out again (:241-262): WITHOUT reference counts this frees cells another object
+ * also covers, exactly like the reference.  move is the reference's moveShapes / insertShapes / removeShapes (:264-280,
+ * all three are remove-then-insert with the new shape list) done as ONE field edit: both occupancy changes are applied,
+ * then the field is updated once over the union of the two windows; field and counts equal remove followed by insert.
+ * Every edit follows EDITS AND SPACES above; an object whose shapes lie wholly outside the grid is a valid edit that
+ * changes no cell.  Cell lists stay on the device; smplx_world_object_cells copies one on request. */
+enum { SMPLX_SHAPE_BOX = 1, SMPLX_SHAPE_SPHERE = 2, SMPLX_SHAPE_CYLINDER = 3, SMPLX_SHAPE_CONE = 4, SMPLX_SHAPE_MESH = 5 };
+typedef struct {
+    int32_t type;            /* SMPLX_SHAPE_BOX / SPHERE / CYLINDER / CONE / MESH */
+    double dims[3];          /* box: x y z;  sphere: r;  cylinder, cone: r, height */
+    double pose[12];         /* 3x4 row major, world frame, like smplx_planning_pose_batch */
+    const double* vertices;  int32_t nvertices;    /* MESH only */
+    const int32_t* triangles; int32_t ntriangles;  /* MESH only: ntriangles x 3 indices */
+} smplx_shape;
+int smplx_world_insert_object(smplx_grid* g, const char* id, const smplx_shape* shapes, int n);
+int smplx_world_remove_object(smplx_grid* g, const char* id);
+int smplx_world_move_object(smplx_grid* g, const char* id, const smplx_shape* shapes, int n);
+int smplx_world_remove_all(smplx_grid* g);
+/* the ids in insertion order, one per line; *n = their number; names (cap bytes, NUL-terminated, truncated when too
+ * small) may be NULL with cap 0 */
+int smplx_world_objects(const smplx_grid* g, char* names, int cap, int* n);  /* '\n'-separated, insertion order */
+/* the cell list of one shape of an object: *n = its length, the first min(cap, *n) cells are copied (cells may be NULL
+ * with cap 0); SMPLX_E_ARG for an unknown id or shape index */
+int smplx_world_object_cells(const smplx_grid* g, const char* id, int shape, int32_t* cells /* n x 3 */, int cap, int* n);
+/* runs the voxeliser and changes nothing (any grid, also one from a finished field): first[s] .. first[s + 1] is the
+ * range of shape s in the lists laid back to back; the first min(cap, first[n]) cells are copied.  Like the edits it
+ * uses the grid's voxeliser work space (kept on the device, grown on demand): one world call at a time per grid */
+int smplx_world_voxelize(const smplx_grid* g, const smplx_shape* shapes, int n, int32_t* cells, int cap, int32_t* first /* n+1 */);
+
 /* ---- robot model --------------------------------------------------------------------------
  * RobotCollisionModel (sbpl_collision_checking/src/robot_collision_model.cpp:117-623),
  * sphere trees (base_collision_models.cpp:337-444), RobotMotionCollisionModel

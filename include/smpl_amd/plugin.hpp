@@ -233,6 +233,29 @@ private:
     std::vector<RobotPlanningSpaceObserver*> m_obs;
 };
 
+// sbpl::collision::Object (sbpl_collision_checking/include/sbpl_collision_checking/shapes.h, world_collision_model.h): an
+// id, shapes and one pose per shape.  A Shape is the flat form of the reference's shapes::Shape hierarchy: box size, sphere
+// radius, cylinder / cone radius and length, or a mesh's vertices and index triples.  Planes and octrees are not supported.
+struct Shape {
+    enum Type { BOX = SMPLX_SHAPE_BOX, SPHERE = SMPLX_SHAPE_SPHERE, CYLINDER = SMPLX_SHAPE_CYLINDER, CONE = SMPLX_SHAPE_CONE, MESH = SMPLX_SHAPE_MESH };
+    Type type = BOX;
+    double dims[3] = {0.0, 0.0, 0.0};      // box: x y z;  sphere: r;  cylinder, cone: r, length
+    std::vector<double> vertices;          // MESH: 3 per vertex
+    std::vector<int32_t> triangles;        // MESH: 3 per triangle
+    static Shape Box(double x, double y, double z) { Shape s; s.type = BOX; s.dims[0] = x; s.dims[1] = y; s.dims[2] = z; return s; }
+    static Shape Sphere(double r) { Shape s; s.type = SPHERE; s.dims[0] = r; return s; }
+    static Shape Cylinder(double r, double length) { Shape s; s.type = CYLINDER; s.dims[0] = r; s.dims[1] = length; return s; }
+    static Shape Cone(double r, double length) { Shape s; s.type = CONE; s.dims[0] = r; s.dims[1] = length; return s; }
+    static Shape Mesh(std::vector<double> v, std::vector<int32_t> t) { Shape s; s.type = MESH; s.vertices = std::move(v); s.triangles = std::move(t); return s; }
+};
+using Pose = std::array<double, 12>;       // 3x4 row major [R | t], world frame (the reference's Eigen::Affine3d)
+inline Pose PoseAt(double x, double y, double z) { return Pose{{1, 0, 0, x, 0, 1, 0, y, 0, 0, 1, z}}; }
+struct CollisionObject {
+    std::string id;
+    std::vector<Shape> shapes;
+    std::vector<Pose> shape_poses;
+};
+
 // One query context on one GPU.  Owns the C-ABI handles; the three plugin facades below share it, the
 // way the reference's lattice, heuristic and checker share one OccupancyGrid and one RobotModel.
 class GpuPlanningContext {
@@ -241,6 +264,18 @@ public:
                        int nz, double res, double max_dist, const int32_t* d2, const smplx_params& params)
     {
         check(smplx_grid_create(origin, nx, ny, nz, res, max_dist, d2, &grid_));
+        check(smplx_model_create(robot_text.c_str(), &model_));
+        check(smplx_space_create(model_, grid_, mprim_text.c_str(), &params, &space_));
+        nvars_ = smplx_space_num_vars(space_);
+        nprims_ = smplx_space_num_prims(space_);
+        res_ = res;
+    }
+    // the same on an EDITABLE grid, built and kept on the GPU (smplx_grid_create_empty): starts empty and takes world objects
+    // through GpuCollisionChecker::insertObject, as CollisionSpace does on its OccupancyGrid
+    GpuPlanningContext(const std::string& robot_text, const std::string& mprim_text, const double origin[3], int nx, int ny,
+                       int nz, double res, double max_dist, const smplx_params& params)
+    {
+        check(smplx_grid_create_empty(origin, nx, ny, nz, res, max_dist, &grid_));
         check(smplx_model_create(robot_text.c_str(), &model_));
         check(smplx_space_create(model_, grid_, mprim_text.c_str(), &params, &space_));
         nvars_ = smplx_space_num_vars(space_);
@@ -256,6 +291,7 @@ public:
     GpuPlanningContext(const GpuPlanningContext&) = delete;
     GpuPlanningContext& operator=(const GpuPlanningContext&) = delete;
     smplx_space* space() const { return space_; }
+    smplx_grid* grid() const { return grid_; }
     int nvars() const { return nvars_; }
     int nprims() const { return nprims_; }
     double resolution() const { return res_; }
@@ -345,6 +381,26 @@ public:
                                  (int)names.size()) == SMPLX_OK;
     }
     bool detachObject(const std::string& id) { return smplx_detach_body(ctx_->space(), id.c_str()) == SMPLX_OK; }
+    // collision_space.cpp:228-275 over world_collision_model.cpp:193-280: world objects, voxelised on the GPU as the
+    // reference voxelises them (smplx_world_* in include/smpl_amd.h).  False with the reason in smplx_last_error() where the
+    // reference returns false (an id already in the world, an unknown id, shapes and poses of different lengths) and for
+    // a context whose grid came from a finished field.  Each is a grid edit: set the lattice's goal again before planning.
+    virtual bool insertObject(const CollisionObject& object)
+    {
+        std::vector<smplx_shape> shapes;
+        return flatten(object, shapes) && smplx_world_insert_object(ctx_->grid(), object.id.c_str(), shapes.data(), (int)shapes.size()) == SMPLX_OK;
+    }
+    virtual bool removeObject(const CollisionObject& object) { return removeObject(object.id); }
+    virtual bool removeObject(const std::string& object_name) { return smplx_world_remove_object(ctx_->grid(), object_name.c_str()) == SMPLX_OK; }
+    // moveShapes, insertShapes and removeShapes are one operation in the reference (remove, then insert the object as
+    // given: world_collision_model.cpp:264-280); here one field edit
+    virtual bool moveShapes(const CollisionObject& object)
+    {
+        std::vector<smplx_shape> shapes;
+        return flatten(object, shapes) && smplx_world_move_object(ctx_->grid(), object.id.c_str(), shapes.data(), (int)shapes.size()) == SMPLX_OK;
+    }
+    virtual bool insertShapes(const CollisionObject& object) { return moveShapes(object); }
+    virtual bool removeShapes(const CollisionObject& object) { return moveShapes(object); }
     // CollisionDistanceExtension: metres to the nearest collision of a state, or of the waypoints of an edge
     // (smplx_cc_state_clearance_batch / smplx_cc_edge_clearance_batch, include/smpl_amd.h: leaf spheres against the
     // distance field and against each other over the checked pairs; saturates at the field's maximum distance).  NaN, with
@@ -386,6 +442,23 @@ public:
     }
 
 private:
+    // checkObjectInsert (world_collision_model.cpp:401-404): one pose per shape
+    static bool flatten(const CollisionObject& object, std::vector<smplx_shape>& out)
+    {
+        if (object.shapes.size() != object.shape_poses.size()) return false;
+        for (size_t i = 0; i < object.shapes.size(); ++i) {
+            const Shape& s = object.shapes[i];
+            smplx_shape c = {};
+            c.type = (int32_t)s.type;
+            for (int k = 0; k < 3; ++k) c.dims[k] = s.dims[k];
+            for (int k = 0; k < 12; ++k) c.pose[k] = object.shape_poses[i][k];
+            c.vertices = s.vertices.data(); c.nvertices = (int32_t)(s.vertices.size() / 3);
+            c.triangles = s.triangles.data(); c.ntriangles = (int32_t)(s.triangles.size() / 3);
+            if (s.type == Shape::MESH && (s.vertices.size() % 3 != 0 || s.triangles.size() % 3 != 0)) return false;   // voxelize.cpp:1016-1019
+            out.push_back(c);
+        }
+        return true;
+    }
     GpuPlanningContext* ctx_;
 };
 

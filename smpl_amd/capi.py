@@ -42,6 +42,8 @@ SYMBOLS = [
     "smplx_cc_state_clearance_batch", "smplx_cc_state_clearance_batch_device", "smplx_cc_edge_clearance_batch",
     "smplx_get_lazy_succs", "smplx_get_true_cost", "smplx_true_cost_batch", "smplx_lazy_expand_batch", "smplx_lazy_expand_batch_device",
     "smplx_true_cost_q_batch", "smplx_true_cost_work_doubles", "smplx_true_cost_q_batch_device", "smplx_lazy_counters",
+    "smplx_world_insert_object", "smplx_world_remove_object", "smplx_world_move_object", "smplx_world_remove_all",
+    "smplx_world_objects", "smplx_world_object_cells", "smplx_world_voxelize",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -167,6 +169,73 @@ def table_probe(nvars, slots, one_home, inserted, queries):
     return found, ids
 
 
+# smplx_shape.type (include/smpl_amd.h)
+SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER, SHAPE_CONE, SHAPE_MESH = 1, 2, 3, 4, 5
+E_ARG = -1
+
+
+class ShapeStruct(C.Structure):
+    _fields_ = [("type", C.c_int32), ("dims", C.c_double * 3), ("pose", C.c_double * 12), ("vertices", _dp),
+                ("nvertices", C.c_int32), ("triangles", _ip), ("ntriangles", C.c_int32)]
+
+
+def pose_at(xyz=(0.0, 0.0, 0.0), R=None):
+    """3x4 [R | t] of a shape, row major; identity rotation unless R (3x3) is given."""
+    P = np.zeros((3, 4))
+    P[:, :3] = np.eye(3) if R is None else np.asarray(R, float).reshape(3, 3)
+    P[:, 3] = xyz
+    return P
+
+
+def _shape(ty, dims, pose, **more):
+    d = list(dims) + [0.0] * (3 - len(dims))
+    return dict(type=ty, dims=tuple(float(x) for x in d), pose=pose_at() if pose is None else _f64(pose).reshape(3, 4), **more)
+
+
+def box(size, pose=None):
+    """shapes::Box: size = (x, y, z) edge lengths, centred on the pose."""
+    return _shape(SHAPE_BOX, size, pose)
+
+
+def sphere(radius, pose=None):
+    return _shape(SHAPE_SPHERE, [radius], pose)
+
+
+def cylinder(radius, height, pose=None):
+    """z-aligned, centred on the pose."""
+    return _shape(SHAPE_CYLINDER, [radius, height], pose)
+
+
+def cone(radius, height, pose=None):
+    """z-aligned, apex up, centred on the pose."""
+    return _shape(SHAPE_CONE, [radius, height], pose)
+
+
+def mesh(vertices, triangles, pose=None):
+    """vertices: n x 3, triangles: index triples.  A triangle list whose length is no multiple of 3 is refused
+    (VoxelizeMesh, smpl/src/geometry/voxelize.cpp:1016-1019)."""
+    t = np.ascontiguousarray(triangles, dtype=np.int32).ravel()
+    v = _f64(vertices).ravel()
+    if t.size % 3 != 0 or v.size % 3 != 0:
+        raise SmplxError(E_ARG, "mesh triangles and vertices come in triples")
+    return _shape(SHAPE_MESH, [], pose, vertices=v.reshape(-1, 3), triangles=t.reshape(-1, 3))
+
+
+def _shape_array(shapes):
+    """-> (smplx_shape array, the numpy arrays it points into: keep them alive over the call)"""
+    shapes = list(shapes)
+    arr, keep = (ShapeStruct * max(1, len(shapes)))(), []
+    for a, s in zip(arr, shapes):
+        a.type = int(s["type"])
+        a.dims[:] = [float(x) for x in s["dims"]]
+        a.pose[:] = [float(x) for x in _f64(s["pose"]).ravel()]
+        if "vertices" in s:
+            v = _f64(s["vertices"]).reshape(-1, 3); t = np.ascontiguousarray(s["triangles"], dtype=np.int32).reshape(-1, 3)
+            keep += [v, t]
+            a.vertices, a.nvertices, a.triangles, a.ntriangles = _p(v, _dp), v.shape[0], _p(t, _ip), t.shape[0]
+    return arr, len(shapes), keep
+
+
 class Grid:
     """OccupancyGrid, lookup side, resident in HBM (16-bit squared distances in 4x4x4 bricks)."""
 
@@ -235,6 +304,65 @@ class Grid:
         lib().smplx_grid_copy_d2.argtypes = [C.c_void_p, _ip]
         _chk(lib().smplx_grid_copy_d2(self.h, _p(out, _ip)))
         return out
+
+    # ---- world objects (include/smpl_amd.h "world objects"): shapes are what box() / sphere() / cylinder() / cone() /
+    # mesh() above return
+    def insert_object(self, object_id, shapes):
+        arr, n, keep = _shape_array(shapes)
+        lib().smplx_world_insert_object.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ShapeStruct), C.c_int]
+        _chk(lib().smplx_world_insert_object(self.h, object_id.encode(), arr, n))
+
+    def move_object(self, object_id, shapes):
+        """moveShapes / insertShapes / removeShapes: the object's shapes become `shapes`, as one field edit."""
+        arr, n, keep = _shape_array(shapes)
+        lib().smplx_world_move_object.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ShapeStruct), C.c_int]
+        _chk(lib().smplx_world_move_object(self.h, object_id.encode(), arr, n))
+
+    def remove_object(self, object_id):
+        lib().smplx_world_remove_object.argtypes = [C.c_void_p, C.c_char_p]
+        _chk(lib().smplx_world_remove_object(self.h, object_id.encode()))
+
+    def remove_all_objects(self):
+        lib().smplx_world_remove_all.argtypes = [C.c_void_p]
+        _chk(lib().smplx_world_remove_all(self.h))
+
+    def objects(self):
+        """ids in insertion order"""
+        L = lib()
+        L.smplx_world_objects.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        cap = 256
+        while True:
+            buf = C.create_string_buffer(cap)
+            _chk(L.smplx_world_objects(self.h, buf, cap, C.byref(n)))
+            names = buf.value.decode().split("\n")[:-1]
+            if len(names) == n.value and (n.value == 0 or buf.value.endswith(b"\n")):
+                return names
+            cap *= 4
+
+    def object_cells(self, object_id, shape=0):
+        """the cells (n x 3) shape `shape` of the object was voxelised into, in ExtractVoxels order"""
+        L = lib()
+        L.smplx_world_object_cells.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _ip, C.c_int, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        _chk(L.smplx_world_object_cells(self.h, object_id.encode(), shape, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), np.int32)
+        _chk(L.smplx_world_object_cells(self.h, object_id.encode(), shape, _p(out, _ip), n.value, C.byref(n)))
+        return out
+
+    def voxelize(self, shapes):
+        """runs the voxeliser and changes nothing: one cell array (n x 3) per shape"""
+        arr, n, keep = _shape_array(shapes)
+        L = lib()
+        L.smplx_world_voxelize.argtypes = [C.c_void_p, C.POINTER(ShapeStruct), C.c_int, _ip, C.c_int, _ip]
+        first = np.zeros(n + 1, np.int32)
+        cap = 4096
+        while True:
+            cells = np.zeros((cap, 3), np.int32)
+            _chk(L.smplx_world_voxelize(self.h, arr, n, _p(cells, _ip), cap, _p(first, _ip)))
+            if first[n] <= cap:
+                return [cells[first[i]:first[i + 1]].copy() for i in range(n)]
+            cap = int(first[n])
 
     def close(self):
         if self.h:

@@ -168,6 +168,9 @@ void smplx_grid_destroy(smplx_grid* g)
     if (g->d_occ) (void)hipFree(g->d_occ);
     if (g->d_tmp) (void)hipFree(g->d_tmp);
     if (g->d_counts) (void)hipFree(g->d_counts);
+    for (WorldObject& o : g->objects)
+        if (o.d_cells) (void)hipFree(o.d_cells);
+    if (g->d_vox) (void)hipFree(g->d_vox);
     delete g;
 }
 

@@ -11,7 +11,8 @@
 //     d2(c) = min( dmax^2 , min over occupied or border cells o of |c - o|^2 )        (cells, integer arithmetic)
 // dmax = ceil(max_dist / res) (distance_map.hpp:126); the cells of the one-cell border layer around the grid count as
 // obstacles (:560-606).  Checked against a brute-force nearest-obstacle search and against the host builder of the
-// test scenes (tests/test_gpu_field.py).  Parity with the reference's own propagation: unpinned.
+// test scenes (tests/test_gpu_field.py).  Parity with the reference's own propagation: unpinned.  What IS pinned to the
+// reference is the step before it, the voxelisation of world objects into cells (voxelize.h, world_objects.h).
 //
 // Method: the squared Euclidean distance separates by axes,
 //     d2(x,y,z) = min_x' (x-x')^2 + [ min_y' (y-y')^2 + [ min_z' over occupied (x',y',z') of (z-z')^2 ] ],
@@ -420,3 +421,6 @@ int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2)
 }
 
 }  // extern "C"
+
+// world objects: shapes voxelised on the GPU, a registry of named objects on the grid
+#include "world_objects.h"

@@ -4,7 +4,26 @@
 
 #include <stdint.h>
 
+#include <string>
+#include <vector>
+
 #include "device_types.h"
+
+// a world object (sbpl::collision::Object: id, shapes, shape poses) with the cells its shapes were voxelised into
+struct WorldShape {
+    int type;
+    double dims[3];
+    double pose[12];
+    std::vector<double> vertices;     // MESH only
+    std::vector<int32_t> triangles;   // MESH only
+};
+struct WorldObject {
+    std::string id;
+    std::vector<WorldShape> shapes;   // as given
+    int32_t* d_cells = nullptr;       // the shapes' cell lists back to back, on the device (n x 3)
+    std::vector<int> first;           // shapes + 1 entries: shape s owns cells [first[s], first[s + 1])
+    std::vector<int> box;             // 6 per shape: the clipped cell range the list lies in (x0 y0 z0 x1 y1 z1)
+};
 
 struct smplx_grid {
     SmplxGridDev dev;
@@ -19,4 +38,9 @@ struct smplx_grid {
     double res, max_dist;
     int n[3];
     int dmax_int, dmax_sqrd;
+    std::vector<WorldObject> objects; // the world's objects in insertion order (world_objects.h)
+    // work space of the voxeliser (triangle constants, prefix, masks, chunk counts): grows, never shrinks, so that a
+    // call does not pay for device allocations; calls on one grid are not reentrant, like its edits
+    mutable void* d_vox = nullptr;
+    mutable size_t vox_bytes = 0;
 };

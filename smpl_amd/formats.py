@@ -32,6 +32,20 @@ def parse_env(text: str):
     return out
 
 
+def env_objects(text: str):
+    """The rows of an `.env` file as world objects: [(name, [box shape])] for `Grid.insert_object`, one box per row with
+    identity rotation, centre and size as `parse_env` gives them -- what the demo builds from a scene file
+    (smpl_test/src/call_planner.cpp:158-207), so that a reference scene goes through the reference's voxeliser.  Rows that
+    share a name are told apart by a `#k` suffix (object ids are unique)."""
+    from . import capi
+    out, seen = [], {}
+    for name, centre, size in parse_env(text):
+        k = seen.get(name, 0)
+        seen[name] = k + 1
+        out.append((name if k == 0 else "%s#%d" % (name, k), [capi.box(size, capi.pose_at(centre))]))
+    return out
+
+
 def sphere_lines_from_collision_yaml(text: str, links=None, rename=None):
     """`sphere <link> <name> x y z radius priority` lines for the links in `links` (default: every link that lists
     spheres).  `rename` maps YAML link names to the names used in the plain-text model."""

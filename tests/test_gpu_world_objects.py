@@ -1,0 +1,259 @@
+"""World objects on the GPU (include/smpl_amd.h "world objects"): the voxeliser against the
+model of the reference (tests/voxelize_ref.py) under the rule of tests/world_cases.py -- cells the model calls undecided
+are left out, everything else is equal as sets and in ExtractVoxels order -- and insert / remove / move against fresh
+grids that got the model's cells through add_points (the field code itself is tested against brute force elsewhere)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import voxelize_ref as V
+import world_cases as W
+from smpl_amd import capi
+
+pytestmark = pytest.mark.gpu
+
+SIX = ["box", "sphere", "cylinder", "soup", "aligned", "cone"]
+
+
+def _grid(counted=False):
+    g = capi.Grid.empty(W.ORIGIN, W.DIMS, W.RES, W.MAX_DIST)
+    if counted:
+        g.set_ref_counted(True)
+    return g
+
+
+def _fresh(adds, removes=(), counted=False):
+    """a new grid that got the model's cells of the shapes in `adds` through add_points, list by list, and then lost
+    those of `removes` through remove_points"""
+    g = _grid(counted)
+    for key in adds:
+        g.add_points(W.world_points(W.judged(key)[1]))
+    for key in removes:
+        g.remove_points(W.world_points(W.judged(key)[1]))
+    return g
+
+
+def _same(g, want, counted=False):
+    assert np.array_equal(g.d2(), want.d2())
+    if counted:
+        assert np.array_equal(g.counts(), want.counts())
+
+
+def _refused(code, call):
+    with pytest.raises(capi.SmplxError) as e:
+        call()
+    assert e.value.code == code
+
+
+@pytest.fixture(scope="module")
+def grid():
+    return _grid()
+
+
+# ---- 4. the voxeliser against the model ------------------------------------------------------------------------------
+@pytest.mark.parametrize("key", SIX)
+def test_voxelize_equals_the_model(grid, key):
+    s, want, und = W.judged(key)
+    (got,) = grid.voxelize([s])
+    n, nu = W.compare(got, key)
+    print(f"{key}: {len(got)} cells, the model {n}, undecided {nu}")
+    if key == "aligned":
+        assert nu <= 0.15 * n
+    else:
+        assert nu == 0 and np.array_equal(got, want)       # no cell is left out of the comparison
+        assert n == W.TRIAL_CELLS.get(key, n)
+
+
+def test_six_shapes_in_one_call_give_the_same_lists(grid):
+    together = grid.voxelize([W.judged(k)[0] for k in SIX])
+    assert len(together) == 6
+    for key, cells in zip(SIX, together):
+        W.compare(cells, key)
+        assert np.array_equal(cells, grid.voxelize([W.judged(key)[0]])[0]), key
+    # voxelize changes nothing, on any grid -- also one made from a finished field
+    assert grid.objects() == [] and np.array_equal(grid.d2(), _grid().d2())
+    fixed = capi.Grid(W.ORIGIN, W.DIMS, W.RES, W.MAX_DIST, np.zeros(W.DIMS, np.int32))
+    assert np.array_equal(fixed.voxelize([W.judged("cone")[0]])[0], together[5])
+
+
+# ---- 5. clipping -----------------------------------------------------------------------------------------------------
+def test_clipping_to_the_grid(grid):
+    s, want, und = W.judged("straddle")
+    (got,) = grid.voxelize([s])
+    assert len(und) == 0 and np.array_equal(got, want) and len(got) > 0
+    assert got.min() >= 0 and np.all(got < np.asarray(W.DIMS)) and got[:, 0].min() == 0 and got[:, 1].min() == 0
+    # the reference's list holds more: the part outside the grid, which addPointsToMap would skip
+    assert len(V.voxelize_shape(s, W.ORIGIN, W.RES)[0]) > len(got)
+    (none,) = grid.voxelize([W.OUTSIDE])
+    assert none.shape == (0, 3)
+    mixed = grid.voxelize([W.OUTSIDE, s, W.OUTSIDE])
+    assert [len(c) for c in mixed] == [0, len(want), 0] and np.array_equal(mixed[1], want)
+    # inserting a shape wholly outside is a valid edit that changes no cell
+    g = _grid(counted=True)
+    g.insert_object("far", [W.OUTSIDE])
+    assert g.objects() == ["far"] and g.object_cells("far", 0).shape == (0, 3)
+    _same(g, _grid(counted=True), counted=True)
+    g.insert_object("edge", [s])
+    _same(g, _fresh(["straddle"], counted=True), counted=True)
+    g.remove_object("far")
+    g.remove_object("edge")
+    _same(g, _grid(counted=True), counted=True)
+
+
+# ---- 6. work distribution --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("key", ["one_triangle", "subdivided", "big_and_small"])
+def test_work_distribution_edges(grid, key):
+    """one triangle; 4097 small ones (more (triangle, voxel) pairs and more triangles than one block covers, so the
+    prefix search crosses blocks); one triangle spanning the whole grid among many of about one voxel"""
+    s, want, und = W.judged(key)
+    ntri = len(np.asarray(s["triangles"]).reshape(-1, 3))
+    assert ntri == {"one_triangle": 1, "subdivided": 4097, "big_and_small": 301}[key]
+    (got,) = grid.voxelize([s])
+    n, nu = W.compare(got, key)
+    print(f"{key}: {ntri} triangles, {len(got)} cells, undecided {nu}")
+    assert n > 0 and nu == 0 and np.array_equal(got, want)       # the model finds no cell of these undecided
+    if key == "big_and_small":
+        assert got.min(0).tolist() == [0, 0, want[:, 2].min()] and got[:, 0].max() == W.DIMS[0] - 1
+
+
+# ---- 7. insert / remove / move ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("counted", [False, True])
+def test_insert_remove_against_fresh_grids(counted):
+    g = _grid(counted)
+    g.insert_object("a", [W.judged("box")[0]])
+    _same(g, _fresh(["box"], counted=counted), counted)
+    assert np.array_equal(g.object_cells("a", 0), W.judged("box")[1])
+    # an object of two shapes: one list per shape, added in order; shared cells count twice
+    g.insert_object("b", [W.judged("sphere")[0], W.judged("cylinder")[0]])
+    _same(g, _fresh(["box", "sphere", "cylinder"], counted=counted), counted)
+    assert g.objects() == ["a", "b"]
+    assert np.array_equal(g.object_cells("b", 0), W.judged("sphere")[1]) and np.array_equal(g.object_cells("b", 1), W.judged("cylinder")[1])
+    shared = set(map(tuple, W.judged("box")[1])) & (set(map(tuple, W.judged("sphere")[1])) | set(map(tuple, W.judged("cylinder")[1])))
+    assert len(shared) > 20          # the objects overlap
+    if counted:
+        assert g.counts().max() >= 2
+    g.remove_object("a")
+    assert g.objects() == ["b"]
+    if counted:      # removing one leaves the other whole
+        _same(g, _fresh(["sphere", "cylinder"], counted=True), True)
+    else:            # the shared cells are cleared with it, as the reference's removePointsFromField does
+        _same(g, _fresh(["box", "sphere", "cylinder"], removes=["box"]))
+        assert not np.array_equal(g.d2(), _fresh(["sphere", "cylinder"]).d2())
+    g.insert_object("c", [W.judged("cone")[0]])
+    assert g.objects() == ["b", "c"]
+    g.remove_all_objects()
+    assert g.objects() == []
+    if counted:
+        _same(g, _grid(True), True)
+    # refusals change nothing
+    g.insert_object("a", [W.judged("box")[0]])
+    before = g.d2()
+    _refused(-1, lambda: g.insert_object("a", [W.judged("cone")[0]]))        # duplicate id
+    _refused(-1, lambda: g.remove_object("nobody"))
+    _refused(-1, lambda: g.move_object("nobody", [W.judged("cone")[0]]))
+    _refused(-1, lambda: g.object_cells("nobody", 0))
+    _refused(-1, lambda: g.object_cells("a", 1))
+    _refused(-1, lambda: g.insert_object("z", []))
+    assert g.objects() == ["a"] and np.array_equal(g.d2(), before)
+
+
+def test_a_grid_from_a_finished_field_refuses_objects():
+    fixed = capi.Grid(W.ORIGIN, W.DIMS, W.RES, W.MAX_DIST, np.zeros(W.DIMS, np.int32))
+    _refused(-5, lambda: fixed.insert_object("a", [W.judged("box")[0]]))
+    _refused(-5, lambda: fixed.move_object("a", [W.judged("box")[0]]))
+    _refused(-5, lambda: fixed.remove_object("a"))
+    _refused(-5, lambda: fixed.remove_all_objects())
+    _refused(-5, lambda: fixed.add_points(np.zeros((1, 3))))
+    assert fixed.objects() == []
+
+
+def _window(cells_lists, dmax):
+    c = np.vstack(cells_lists)
+    lo = np.maximum(c.min(0) - dmax, 0)
+    hi = np.minimum(c.max(0) + dmax, np.asarray(W.DIMS) - 1)
+    n = int(np.prod(hi - lo + 1))
+    whole = int(np.prod(W.DIMS))
+    return whole if 2 * n > whole else n
+
+
+@pytest.mark.parametrize("counted", [False, True])
+def test_move_is_remove_plus_insert_in_one_edit(counted):
+    small = capi.box((0.05, 0.04, 0.03), W.pose((0.2, 0.1, 0.3), W.ROT))
+    moved = capi.box((0.05, 0.04, 0.03), W.pose((0.26, 0.16, 0.34), W.ROT))
+    other = W.judged("cone")[0]
+    a, b = _grid(counted), _grid(counted)
+    for g in (a, b):
+        g.insert_object("other", [other])
+        g.insert_object("crate", [small])
+    old = a.object_cells("crate", 0)
+    a.move_object("crate", [moved])
+    one_edit = a.last_edit_cells()
+    b.remove_object("crate")
+    b.insert_object("crate", [moved])
+    _same(a, b, counted)
+    new = a.object_cells("crate", 0)
+    assert np.array_equal(new, b.object_cells("crate", 0)) and not np.array_equal(new, old)
+    assert a.objects() == b.objects() == ["other", "crate"]      # a moved object keeps its place
+    # against the model, through add_points / remove_points on a fresh grid (without counts the removal also frees the
+    # cells the crate shared with the cone, as in the reference)
+    want, und = V.voxelize_shape(moved, W.ORIGIN, W.RES, clip=W.DIMS)
+    was, und0 = V.voxelize_shape(small, W.ORIGIN, W.RES, clip=W.DIMS)
+    assert len(und) == 0 and len(und0) == 0 and np.array_equal(new, want) and np.array_equal(old, was)
+    f = _grid(counted)
+    f.add_points(W.world_points(W.judged("cone")[1]))
+    f.add_points(W.world_points(was))
+    f.remove_points(W.world_points(was))
+    f.add_points(W.world_points(want))
+    _same(a, f, counted)
+    # one edit over the union of both windows: more than either alone, less than the grid
+    dmax = int(np.ceil(W.MAX_DIST / W.RES))
+    assert one_edit == _window([old, new], dmax) and b.last_edit_cells() == _window([new], dmax)
+    assert _window([new], dmax) < one_edit < int(np.prod(W.DIMS))
+    # insertShapes / removeShapes are the same call with a longer or shorter list
+    a.move_object("crate", [moved, small])
+    assert np.array_equal(a.object_cells("crate", 1), old)
+    a.move_object("crate", [small])
+    b.move_object("crate", [small])
+    _same(a, b, counted)
+    _refused(-1, lambda: a.object_cells("crate", 1))
+
+
+# ---- 8. staleness ----------------------------------------------------------------------------------------------------
+def test_edits_and_spaces(small_cfg):
+    """an inserted object follows EDITS AND SPACES: successors are refused until the goal is set again, while the
+    collision checker reads the new field at once"""
+    cfg, gr = small_cfg, small_cfg.grid
+    model = capi.Model(cfg.robot_text)
+    g = capi.Grid.from_boxes(gr.origin, gr.dims, gr.res, gr.max_dist, cfg.boxes)
+    s = capi.Space(model, g, cfg.mprim, cfg.params, 256)
+    s.set_goal_joint(cfg.goal, cfg.goal_tol)
+    start = s.set_start(cfg.start)
+    succs, _ = s.get_succs(start)
+    assert len(succs) > 0
+    q = np.asarray([cfg.start])
+    assert s.state_valid_batch(q)[0][0] == 1
+    # a box of one cell's size around the centre of the last sphere of the model (on the planning link's end of the arm):
+    # the cell holding the centre is within rc of one of the box's corners, so it fills, and the sphere is in collision
+    centre = s.sphere_positions(q)[0, -1]
+    g.insert_object("crate", [capi.box((gr.res, gr.res, gr.res), capi.pose_at(centre))])
+    cell = np.floor((centre - np.asarray(gr.origin)) / gr.res + 0.5).astype(int)
+    assert any(np.array_equal(c, cell) for c in g.object_cells("crate", 0))
+    assert s.state_valid_batch(q)[0][0] == 0
+    _refused(-5, lambda: s.get_succs(start))
+    _refused(-5, lambda: s.plan(5.0, 1.0, 1.0, True, True, 100, 100))
+    s.set_goal_joint(cfg.goal, cfg.goal_tol)
+    g.remove_object("crate")
+    assert s.state_valid_batch(q)[0][0] == 1
+    _refused(-5, lambda: s.get_succs(start))
+    s.set_goal_joint(cfg.goal, cfg.goal_tol)
+    start = s.set_start(cfg.start)
+    again, _ = s.get_succs(start)
+    assert len(again) == len(succs)
+    # a move is an edit too
+    g.insert_object("crate", [capi.sphere(0.05, capi.pose_at((gr.origin[0] + 0.3, gr.origin[1] + 0.3, gr.origin[2] + 0.3)))])
+    s.set_goal_joint(cfg.goal, cfg.goal_tol)
+    s.set_start(cfg.start)
+    g.move_object("crate", [capi.box((gr.res, gr.res, gr.res), capi.pose_at(centre))])
+    _refused(-5, lambda: s.get_succs(start))
+    assert s.state_valid_batch(q)[0][0] == 0
