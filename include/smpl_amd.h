@@ -146,6 +146,81 @@ int smplx_world_object_cells(const smplx_grid* g, const char* id, int shape, int
  * uses the grid's voxeliser work space (kept on the device, grown on demand): one world call at a time per grid */
 int smplx_world_voxelize(const smplx_grid* g, const smplx_shape* shapes, int n, int32_t* cells, int cap, int32_t* first /* n+1 */);
 
+/* ---- robot body: the links outside the planning group as obstacles ---------------------------------------------------
+ * SelfCollisionModelImpl::updateGroup / updateVoxelsStates (sbpl_collision_checking/src/self_collision_model.cpp:616-760,
+ * 770-837): every link that has a voxel model (CollisionVoxelsModel, robot_collision_model.cpp:566-573) and is not in
+ * the planning group is voxelised into the occupancy grid and kept there as the robot's other joints move.
+ *
+ * The body is a host record beside the model, described by a text in the style of the robot text (DESIGN.md sections 4
+ * and 20): the robot text's `link` and `joint` rows, plus
+ *     geom LINK box SX SY SZ | sphere R | cylinder R LENGTH | mesh NV NT     x y z  r p y
+ *         one <collision> element: the shape, then its origin in the link frame; a mesh is followed by NV rows
+ *         "v x y z" and NT rows "t a b c"
+ *     voxels LINK RES       the link has a voxel model at this resolution
+ *     group NAME LINK ...   the planning group's links: their voxel models are never placed
+ *     value JOINT Q         the joint's position at creation (default 0)
+ * Limits (SMPLX_E_LIMIT beyond them): SMPLX_BODY_MAX_LINKS links, SMPLX_BODY_MAX_MODEL_POINTS voxels in one model (and
+ * vertices or triangles in one mesh), SMPLX_BODY_MAX_POINTS voxels in all models, SMPLX_BODY_MAX_LATTICE lattice cells
+ * in the bounding box of one geom.  There is no limit of 40 joints: the body is not part of the device model.
+ *
+ * Link transforms are computed on the host in binary64 with the arithmetic of the group's links (the root link's frame
+ * is the world's; T_child = T_parent * fn(origin, axis, q), transform_functions.h:95-258; prismatic joints move along
+ * the joint frame's Z).
+ * Voxel models are built once, at smplx_body_create, on the GPU: RobotCollisionModel::voxelizeLink /
+ * voxelizeCollisionElement / voxelizeGeometry (robot_collision_model.cpp:959-1073).  Each geom row of the link, in file
+ * order, becomes the mesh the world objects use (box, sphere 7 x 8, cylinder with 16 rim points), goes through its
+ * origin (R v + t) and its SURFACE is voxelised by the gridless VoxelizeMesh (smpl/src/geometry/voxelize.cpp:962-986):
+ * VoxelizeTriangle on the HalfResVoxelGrid over the mesh's bounding box (discretize.h:94-113, voxel_grid.h:187-193), the
+ * filled voxels as continuous link-frame points in ExtractVoxels order; the elements' points are appended one after
+ * another, duplicates kept.  A link without geom rows has an empty model (the reference warns, :996-998).
+ * Deliberate clip: the grid's high index is discretize(min + (max - min)), which can round below discretize(max); the
+ * reference then indexes its grid past the end, here every triangle's candidates are clipped to the voxel grid's range.
+ *
+ * A voxels state is its model's points under the link's current transform (RobotCollisionState::updateVoxelsState,
+ * robot_collision_state.h:473-497); every point then takes the point rule of smplx_grid_add_points, and one outside the
+ * grid is skipped.  Every state starts dirty; smplx_body_set_joint with a value different from the current one dirties
+ * the states of the joint's child link and all its descendants (robot_collision_state.cpp:62-96); the same value
+ * dirties nothing.  smplx_grid_put_body places every dirty state of a link outside the group, in model order: the
+ * state's stored cell list is taken out, the new one is computed, stored on the grid and added; then the field is
+ * updated ONCE over the union of all windows (as smplx_world_move_object does).  With reference counts every point
+ * counts (several points in one cell count several times); without them a removal frees cells a world object also
+ * covers, like the reference and smplx_world_remove_object.  A put with nothing to place is not an edit; one that
+ * changes cells follows EDITS AND SPACES above.  smplx_grid_take_body removes all stored lists and forgets the body.
+ * Deliberate difference: the reference's updateGroup first inserts the states' initial voxels, still in the LINK frame
+ * (robot_collision_state.cpp:264-266), and the first updateVoxelsStates removes them again, which frees world cells near
+ * the origin on a grid without counts.  Here a state enters the grid transformed, and only so.
+ *
+ * The placement belongs to the grid: a grid holds at most one body (SMPLX_E_STATE for another one), the body handle may
+ * be destroyed while placed, smplx_grid_destroy frees the lists, and a grid from a finished field refuses
+ * (SMPLX_E_STATE).  SMPLX_E_ARG: null pointers, unknown names, non-finite numbers (|x| >= 1e6), res <= 0, dimensions
+ * <= 0, a mesh index outside its vertices, a voxels or geom row on an unknown link, malformed rows -- the text's errors
+ * name their line ("line N: ...") and are found before any GPU is touched.  A refused call changes nothing.
+ * Out of scope: setWorldToModelTransform (it would move the group's spheres too), voxel models of attached bodies,
+ * folding non-zero held joints into the group's model, loading mesh files, planar and floating joints. */
+#define SMPLX_BODY_MAX_LINKS 4096
+#define SMPLX_BODY_MAX_MODEL_POINTS 4000000
+#define SMPLX_BODY_MAX_POINTS 16000000
+#define SMPLX_BODY_MAX_LATTICE 268435456
+typedef struct smplx_body smplx_body;
+int smplx_body_create(const char* body_text, smplx_body** out);
+void smplx_body_destroy(smplx_body* b);
+/* models: links with a voxels row, in the order of those rows; outside: those that are placed; points: in all models */
+int smplx_body_counts(const smplx_body* b, int* links, int* joints, int* models, int* outside_models, int* points);
+int smplx_body_set_joint(smplx_body* b, const char* joint, double q);
+int smplx_body_joint(const smplx_body* b, const char* joint, double* q);
+/* world frames of all links in the order of the text's link rows, 3x4 row major each */
+int smplx_body_link_transforms(const smplx_body* b, double* T /* nlinks x 12 */);
+/* the link of a model: its index among the link rows */
+int smplx_body_model_link(const smplx_body* b, int model, int* link);
+/* the link-frame points of one model, in order: *n = their number, the first min(cap, *n) are copied */
+int smplx_body_model_points(const smplx_body* b, int model, double* xyz /* n x 3 */, int cap, int* n);
+int smplx_body_dirty(const smplx_body* b, uint8_t* per_model);
+int smplx_grid_put_body(smplx_grid* g, smplx_body* b);
+int smplx_grid_take_body(smplx_grid* g);
+/* the stored list of one model: one cell per point in point order, a point outside the grid as (-1, -1, -1); *n = 0 for
+ * a model that has no list (a group link's, or nothing placed yet) */
+int smplx_grid_body_cells(const smplx_grid* g, int model, int32_t* cells /* n x 3 */, int cap, int* n);
+
 /* ---- robot model --------------------------------------------------------------------------
  * RobotCollisionModel (sbpl_collision_checking/src/robot_collision_model.cpp:117-623),
  * sphere trees (base_collision_models.cpp:337-444), RobotMotionCollisionModel

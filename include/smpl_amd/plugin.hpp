@@ -331,6 +331,9 @@ class GpuCollisionChecker : public CollisionChecker, public CollisionDistanceExt
 public:
     using Extension::getExtension;   // keep the typed lookup visible next to the override
     explicit GpuCollisionChecker(GpuPlanningContext* ctx) : ctx_(ctx) {}
+    GpuCollisionChecker(const GpuCollisionChecker&) = delete;
+    GpuCollisionChecker& operator=(const GpuCollisionChecker&) = delete;
+    ~GpuCollisionChecker() { smplx_body_destroy(body_); }   // a placed body stays on the grid, which owns the placement
     bool isStateValid(const RobotState& state, bool = false) override
     {
         uint8_t ok = 0;
@@ -401,6 +404,34 @@ public:
     }
     virtual bool insertShapes(const CollisionObject& object) { return moveShapes(object); }
     virtual bool removeShapes(const CollisionObject& object) { return moveShapes(object); }
+    // The robot's links outside the planning group as obstacles (smplx_body_* in include/smpl_amd.h; the reference keeps
+    // them in the grid through SelfCollisionModelImpl::updateVoxelsStates, self_collision_model.cpp:770-837).
+    // attachRobotBody builds the voxel models of a body text and places them; setJointPosition
+    // (CollisionSpace::setJointPosition, collision_space.cpp) sets the value of a joint of the attached body record and
+    // puts the body again, and returns false for a joint it does not know, as the reference does.  Every call that changes
+    // cells is a grid edit: set the lattice's goal again before planning.  Needs a context on an editable grid.
+    bool attachRobotBody(const std::string& body_text)
+    {
+        if (body_) return false;
+        smplx_body* b = nullptr;
+        if (smplx_body_create(body_text.c_str(), &b) != SMPLX_OK) return false;
+        if (smplx_grid_put_body(ctx_->grid(), b) != SMPLX_OK) { smplx_body_destroy(b); return false; }
+        body_ = b;
+        return true;
+    }
+    bool detachRobotBody()
+    {
+        if (!body_) return false;
+        const bool ok = smplx_grid_take_body(ctx_->grid()) == SMPLX_OK;
+        smplx_body_destroy(body_);
+        body_ = nullptr;
+        return ok;
+    }
+    bool setJointPosition(const std::string& name, double position)
+    {
+        if (!body_ || smplx_body_set_joint(body_, name.c_str(), position) != SMPLX_OK) return false;
+        return smplx_grid_put_body(ctx_->grid(), body_) == SMPLX_OK;
+    }
     // CollisionDistanceExtension: metres to the nearest collision of a state, or of the waypoints of an edge
     // (smplx_cc_state_clearance_batch / smplx_cc_edge_clearance_batch, include/smpl_amd.h: leaf spheres against the
     // distance field and against each other over the checked pairs; saturates at the field's maximum distance).  NaN, with
@@ -460,6 +491,7 @@ private:
         return true;
     }
     GpuPlanningContext* ctx_;
+    smplx_body* body_ = nullptr;
 };
 
 // sbpl::motion::ManipLattice (smpl/include/smpl/graph/manip_lattice.h:63-307)

@@ -44,6 +44,9 @@ SYMBOLS = [
     "smplx_true_cost_q_batch", "smplx_true_cost_work_doubles", "smplx_true_cost_q_batch_device", "smplx_lazy_counters",
     "smplx_world_insert_object", "smplx_world_remove_object", "smplx_world_move_object", "smplx_world_remove_all",
     "smplx_world_objects", "smplx_world_object_cells", "smplx_world_voxelize",
+    "smplx_body_create", "smplx_body_destroy", "smplx_body_counts", "smplx_body_set_joint", "smplx_body_joint",
+    "smplx_body_link_transforms", "smplx_body_model_link", "smplx_body_model_points", "smplx_body_dirty",
+    "smplx_grid_put_body", "smplx_grid_take_body", "smplx_grid_body_cells",
 ]
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
@@ -364,9 +367,98 @@ class Grid:
                 return [cells[first[i]:first[i + 1]].copy() for i in range(n)]
             cap = int(first[n])
 
+    # ---- robot body (include/smpl_amd.h "robot body")
+    def put_body(self, body):
+        """places every dirty voxels state of a link outside the group: one field edit, or none when nothing is dirty"""
+        lib().smplx_grid_put_body.argtypes = [C.c_void_p, C.c_void_p]
+        _chk(lib().smplx_grid_put_body(self.h, body.h))
+
+    def take_body(self):
+        lib().smplx_grid_take_body.argtypes = [C.c_void_p]
+        _chk(lib().smplx_grid_take_body(self.h))
+
+    def body_cells(self, model):
+        """the stored list of one model (n x 3): one cell per point in point order, (-1, -1, -1) outside the grid"""
+        L = lib()
+        L.smplx_grid_body_cells.argtypes = [C.c_void_p, C.c_int, _ip, C.c_int, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        _chk(L.smplx_grid_body_cells(self.h, model, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), np.int32)
+        if n.value:
+            _chk(L.smplx_grid_body_cells(self.h, model, _p(out, _ip), n.value, C.byref(n)))
+        return out
+
     def close(self):
         if self.h:
             lib().smplx_grid_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Body:
+    """The robot body (include/smpl_amd.h "robot body"): links outside the planning group with their voxel models, built
+    on the GPU at creation.  The text's errors are found before any GPU is touched."""
+
+    def __init__(self, body_text: str):
+        self.h = C.c_void_p()
+        L = lib()
+        L.smplx_body_create.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+        L.smplx_body_destroy.argtypes = [C.c_void_p]
+        L.smplx_body_destroy.restype = None
+        _chk(L.smplx_body_create(body_text.encode(), C.byref(self.h)))
+        c = [C.c_int() for _ in range(5)]
+        L.smplx_body_counts.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 5
+        _chk(L.smplx_body_counts(self.h, *[C.byref(x) for x in c]))
+        self.nlinks, self.njoints, self.nmodels, self.noutside, self.npoints = [x.value for x in c]
+
+    def set_joint(self, joint, q):
+        lib().smplx_body_set_joint.argtypes = [C.c_void_p, C.c_char_p, C.c_double]
+        _chk(lib().smplx_body_set_joint(self.h, joint.encode(), float(q)))
+
+    def joint(self, joint):
+        q = C.c_double(0.0)
+        lib().smplx_body_joint.argtypes = [C.c_void_p, C.c_char_p, _dp]
+        _chk(lib().smplx_body_joint(self.h, joint.encode(), C.byref(q)))
+        return q.value
+
+    def link_transforms(self):
+        """[nlinks][3][4] world frames in the order of the text's link rows"""
+        T = np.zeros((self.nlinks, 3, 4))
+        lib().smplx_body_link_transforms.argtypes = [C.c_void_p, _dp]
+        _chk(lib().smplx_body_link_transforms(self.h, _p(T, _dp)))
+        return T
+
+    def model_link(self, model):
+        l = C.c_int(-1)
+        lib().smplx_body_model_link.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        _chk(lib().smplx_body_model_link(self.h, model, C.byref(l)))
+        return l.value
+
+    def model_points(self, model):
+        """the link-frame points of one model (n x 3), in order"""
+        L = lib()
+        L.smplx_body_model_points.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int, C.POINTER(C.c_int)]
+        n = C.c_int(0)
+        _chk(L.smplx_body_model_points(self.h, model, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3))
+        if n.value:
+            _chk(L.smplx_body_model_points(self.h, model, _p(out, _dp), n.value, C.byref(n)))
+        return out
+
+    def dirty(self):
+        out = np.zeros(max(1, self.nmodels), np.uint8)
+        lib().smplx_body_dirty.argtypes = [C.c_void_p, _up]
+        _chk(lib().smplx_body_dirty(self.h, _p(out, _up)))
+        return out[:self.nmodels].astype(bool)
+
+    def close(self):
+        if self.h:
+            lib().smplx_body_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -171,6 +171,12 @@ void smplx_grid_destroy(smplx_grid* g)
     for (WorldObject& o : g->objects)
         if (o.d_cells) (void)hipFree(o.d_cells);
     if (g->d_vox) (void)hipFree(g->d_vox);
+    if (g->body) {
+        if (g->body->d_cells) (void)hipFree(g->body->d_cells);
+        if (g->body->d_points) (void)hipFree(g->body->d_points);
+        if (g->body->d_states) (void)hipFree(g->body->d_states);
+        delete g->body;
+    }
     delete g;
 }
 

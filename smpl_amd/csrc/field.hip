@@ -424,3 +424,6 @@ int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2)
 
 // world objects: shapes voxelised on the GPU, a registry of named objects on the grid
 #include "world_objects.h"
+
+// the robot body: voxel models of the links outside the planning group, placed under the current link transforms
+#include "body_place.h"

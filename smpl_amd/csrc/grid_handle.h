@@ -25,6 +25,20 @@ struct WorldObject {
     std::vector<int> box;             // 6 per shape: the clipped cell range the list lies in (x0 y0 z0 x1 y1 z1)
 };
 
+// the robot body placed on a grid (body_place.h): the cell list of every outside voxels state, one cell per model point
+struct GridBody {
+    uint64_t serial = 0;              // which smplx_body it belongs to (the handle itself may be gone)
+    std::vector<int> first;           // models + 1 entries: model m owns cells [first[m], first[m + 1]) of a half; a
+                                      // model of a group link owns none
+    std::vector<unsigned char> placed, half;   // per model: has a list; which half of d_cells holds it
+    std::vector<int> box;             // 6 per model: the cell range its in-grid cells lie in (x1 < x0: none inside)
+    int32_t* d_cells = nullptr;       // two halves of first.back() cells each (n x 3): a put writes the other half
+    double* d_points = nullptr;       // the body's link-frame points (its own copy: the body may be destroyed)
+    std::vector<int> point_first;     // models + 1: model m's points in d_points
+    void* d_states = nullptr;         // work space of a put: transforms, prefixes and boxes of the states being placed
+    size_t states_bytes = 0;
+};
+
 struct smplx_grid {
     SmplxGridDev dev;
     uint16_t* d_d2 = nullptr;        // brick-tiled squared cell distances (what the kernels read)
@@ -43,4 +57,5 @@ struct smplx_grid {
     // call does not pay for device allocations; calls on one grid are not reentrant, like its edits
     mutable void* d_vox = nullptr;
     mutable size_t vox_bytes = 0;
+    GridBody* body = nullptr;         // at most one placed robot body (body_place.h)
 };

@@ -78,6 +78,18 @@ SMPLX_HD int vox_discretize(double w, double pivot, double res, int n)
 }
 SMPLX_HD double vox_continuize(int i, double pivot, double res) { return pivot + i * res; }
 
+// HalfResDiscretizer (discretize.h:94-113), the lattice of the gridless VoxelizeMesh (voxelize.cpp:962-986) that makes a
+// link's voxel model: discretize(d) = d >= 0 ? (int)(d / res) : (int)(d / res) - 1.  Its continuize(i) = i * res + 0.5 * res
+// is vox_continuize with the pivot 0.5 * res (the sum commutes, so the bits are the same).  The quotient is clamped to
+// +-2^30 in double before the cast: a tiny resolution must not overflow an int (the caller refuses such a model).
+SMPLX_HD int vox_half_discretize(double d, double res)
+{
+    double f = d / res;
+    if (f < -1073741824.0) f = -1073741824.0;
+    if (f > 1073741824.0) f = 1073741824.0;
+    return d >= 0.0 ? (int)f : (int)f - 1;
+}
+
 // the constants of one triangle (voxelize.hpp:52-113); false when the triangle is skipped (:57-60)
 SMPLX_HD bool vox_tri_setup(const double* p1, const double* p2, const double* p3, double res, VoxTri* T)
 {

@@ -257,37 +257,55 @@ struct VoxLists {
     std::vector<int> first, box;      // as in WorldObject
 };
 
-// voxelises the shapes on the grid's lattice.  With occ the cells also become obstacles (an edit; the caller updates the
-// field).  Waits for the device.
-int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, unsigned char* occ, int* counts, VoxLists& out)
+// the lattice a call voxelises on: voxel i along axis a is centred on offset[a] + i * res
+struct VoxLattice {
+    double offset[3];
+    double res;
+    bool half_res;     // indices by the HalfResDiscretizer (gridless voxel models, body_place.h), else by the
+                       // PivotDiscretizer at `offset` (the occupancy grid's own lattice)
+};
+
+// voxelises meshes (vertices already in the lattice's frame) on a lattice.  clip: 6 ints per mesh, the inclusive index
+// range {lo, hi} its candidates are clipped to.  work / work_bytes: the caller's work space, grown on demand.  With occ
+// the cells also become obstacles of a grid whose y and z extents are ny, nz (an edit; the caller updates the field).
+// Waits for the device.
+int voxelize_meshes(void** work, size_t* work_bytes, const VoxLattice& L, const std::vector<Mesh>& meshes, const std::vector<int>& clip,
+                    unsigned char* occ, int* counts, int ny, int nz, VoxLists& out)
 {
-    const int ns = (int)shapes.size();
+    const int ns = (int)meshes.size();
     std::vector<VoxItem> items;
-    std::vector<double> verts;                         // the call's vertices, world frame
+    std::vector<double> verts;                         // the call's vertices
     std::vector<long long> first(1, 0);
     std::vector<VoxShape> vs((size_t)ns + 1);
     out.first.assign((size_t)ns + 1, 0);
     out.box.assign((size_t)ns * 6, 0);
     long long mask_bytes = 0, chunks = 0;
-    Mesh m;
     for (int s = 0; s < ns; ++s) {
-        shape_mesh(shapes[(size_t)s], m);
+        const Mesh& m = meshes[(size_t)s];
+        const int* cl = &clip[6 * (size_t)s];
         const int v0 = (int)(verts.size() / 3);
         verts.insert(verts.end(), m.v.begin(), m.v.end());
-        int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {-1, -1, -1};
+        int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+        bool none = true;
         for (size_t k = 0; k + 2 < m.t.size(); k += 3) {
             const double* p[3] = {&m.v[3 * (size_t)m.t[k]], &m.v[3 * (size_t)m.t[k + 1]], &m.v[3 * (size_t)m.t[k + 2]]};
-            // the candidates: worldToGrid of the vertices' minimum and maximum (voxelize.hpp:115-122), clipped to the grid
+            // the candidates: worldToGrid of the vertices' minimum and maximum (voxelize.hpp:115-122), clipped
             // (a triangle the reference skips is listed too: k_vox_setup finds that out)
             int tl[3], th[3];
             bool any = true;
             for (int a = 0; a < 3; ++a) {
                 const double mn = std::min(p[0][a], std::min(p[1][a], p[2][a])), mx = std::max(p[0][a], std::max(p[1][a], p[2][a]));
-                tl[a] = std::max(0, vox_discretize(mn, g->origin[a], g->res, g->n[a]));
-                th[a] = std::min(g->n[a] - 1, vox_discretize(mx, g->origin[a], g->res, g->n[a]));
+                if (L.half_res) {
+                    tl[a] = std::max(cl[a], vox_half_discretize(mn, L.res));
+                    th[a] = std::min(cl[3 + a], vox_half_discretize(mx, L.res));
+                } else {
+                    tl[a] = std::max(cl[a], vox_discretize(mn, L.offset[a], L.res, cl[3 + a] + 1));
+                    th[a] = std::min(cl[3 + a], vox_discretize(mx, L.offset[a], L.res, cl[3 + a] + 1));
+                }
                 any = any && th[a] >= tl[a];
             }
             if (!any) continue;
+            none = false;
             VoxItem it;
             for (int a = 0; a < 3; ++a) { it.v[a] = v0 + m.t[k + a]; it.lo[a] = tl[a]; lo[a] = std::min(lo[a], tl[a]); hi[a] = std::max(hi[a], th[a]); }
             it.ny = th[1] - tl[1] + 1; it.nz = th[2] - tl[2] + 1;
@@ -297,8 +315,8 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
         }
         VoxShape& S = vs[(size_t)s];
         S.mask_first = mask_bytes; S.list_first = 0; S.first_chunk = (int)chunks; S.pad = 0;
-        for (int a = 0; a < 3; ++a) { S.lo[a] = hi[a] < 0 ? 0 : lo[a]; S.dim[a] = hi[a] < 0 ? 0 : hi[a] - lo[a] + 1; }
-        for (int a = 0; a < 3; ++a) { out.box[6 * (size_t)s + a] = hi[a] < 0 ? 0 : lo[a]; out.box[6 * (size_t)s + 3 + a] = hi[a] < 0 ? -1 : hi[a]; }
+        for (int a = 0; a < 3; ++a) { S.lo[a] = none ? 0 : lo[a]; S.dim[a] = none ? 0 : hi[a] - lo[a] + 1; }
+        for (int a = 0; a < 3; ++a) { out.box[6 * (size_t)s + a] = none ? 0 : lo[a]; out.box[6 * (size_t)s + 3 + a] = none ? -1 : hi[a]; }
         const long long size = (long long)S.dim[0] * S.dim[1] * S.dim[2];
         mask_bytes += size;
         chunks += (size + VOX_CHUNK - 1) / VOX_CHUNK;
@@ -314,13 +332,13 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
                              sizeof(int) * (size_t)nchunks, (size_t)mask_bytes, sizeof(VoxItem) * items.size(), sizeof(double) * verts.size()};
     size_t at[7], need = 0;
     for (int i = 0; i < 7; ++i) { at[i] = need; need += (bytes[i] + 255) & ~(size_t)255; }
-    if (need > g->vox_bytes) {
-        if (g->d_vox) (void)hipFree(g->d_vox);
-        g->d_vox = nullptr; g->vox_bytes = 0;
-        FIELD_TRY(hipMalloc(&g->d_vox, need));
-        g->vox_bytes = need;
+    if (need > *work_bytes) {
+        if (*work) (void)hipFree(*work);
+        *work = nullptr; *work_bytes = 0;
+        FIELD_TRY(hipMalloc(work, need));
+        *work_bytes = need;
     }
-    char* const base = (char*)g->d_vox;
+    char* const base = (char*)*work;
     struct { void* p; } d_tris{base + at[0]}, d_first{base + at[1]}, d_shapes{base + at[2]}, d_chunk{base + at[3]}, d_mask{base + at[4]},
         d_items{base + at[5]}, d_verts{base + at[6]};
     FIELD_TRY(hipMemcpy(d_items.p, items.data(), bytes[5], hipMemcpyHostToDevice));
@@ -333,11 +351,11 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
     struct EvFree { hipEvent_t* e; ~EvFree() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_free{ev};
     g_vox_kernel_ms = 0.0;
     hipLaunchKernelGGL(k_vox_setup, dim3((ntri + FIELD_BLOCK - 1) / FIELD_BLOCK), dim3(FIELD_BLOCK), 0, 0, (const double*)d_verts.p, (const VoxItem*)d_items.p,
-                       ntri, g->res, (VoxTri*)d_tris.p);
+                       ntri, L.res, (VoxTri*)d_tris.p);
     hipLaunchKernelGGL(k_vox_fill, dim3(blocks_of((size_t)first.back())), dim3(FIELD_BLOCK), 0, 0, (const VoxTri*)d_tris.p, (const long long*)d_first.p,
-                       ntri, (const VoxShape*)d_shapes.p, (unsigned char*)d_mask.p, g->origin[0], g->origin[1], g->origin[2], g->res);
+                       ntri, (const VoxShape*)d_shapes.p, (unsigned char*)d_mask.p, L.offset[0], L.offset[1], L.offset[2], L.res);
     hipLaunchKernelGGL(k_vox_compact<false>, dim3(nchunks), dim3(FIELD_BLOCK), 0, 0, (const unsigned char*)d_mask.p, (const VoxShape*)d_shapes.p, ns,
-                       (int*)d_chunk.p, (int*)nullptr, (unsigned char*)nullptr, (int*)nullptr, g->n[1], g->n[2]);
+                       (int*)d_chunk.p, (int*)nullptr, (unsigned char*)nullptr, (int*)nullptr, ny, nz);
     FIELD_TRY(hipGetLastError());
     if (g_vox_timing) FIELD_TRY(hipEventRecord(ev[1], 0));
     std::vector<int> chunk_n((size_t)nchunks);
@@ -359,7 +377,7 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
     FIELD_TRY(d_cells.alloc(sizeof(int32_t) * 3 * (size_t)total));
     if (g_vox_timing) FIELD_TRY(hipEventRecord(ev[2], 0));
     hipLaunchKernelGGL(k_vox_compact<true>, dim3(nchunks), dim3(FIELD_BLOCK), 0, 0, (const unsigned char*)d_mask.p, (const VoxShape*)d_shapes.p, ns,
-                       (int*)d_chunk.p, (int*)d_cells.p, occ, counts, g->n[1], g->n[2]);
+                       (int*)d_chunk.p, (int*)d_cells.p, occ, counts, ny, nz);
     FIELD_TRY(hipGetLastError());
     if (g_vox_timing) FIELD_TRY(hipEventRecord(ev[3], 0));
     FIELD_TRY(hipDeviceSynchronize());
@@ -372,6 +390,20 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
     out.d_cells = (int32_t*)d_cells.p;
     d_cells.p = nullptr;
     return SMPLX_OK;
+}
+
+// voxelises the shapes on the grid's lattice: the pivot is the grid's origin and the candidates are clipped to the grid.
+// With occ the cells also become obstacles (an edit; the caller updates the field).  Waits for the device.
+int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, unsigned char* occ, int* counts, VoxLists& out)
+{
+    std::vector<Mesh> meshes(shapes.size());
+    std::vector<int> clip;
+    for (size_t s = 0; s < shapes.size(); ++s) {
+        shape_mesh(shapes[s], meshes[s]);
+        clip.insert(clip.end(), {0, 0, 0, g->n[0] - 1, g->n[1] - 1, g->n[2] - 1});
+    }
+    const VoxLattice L{{g->origin[0], g->origin[1], g->origin[2]}, g->res, false};
+    return voxelize_meshes(&g->d_vox, &g->vox_bytes, L, meshes, clip, occ, counts, g->n[1], g->n[2], out);
 }
 
 // takes the stored lists of an object out of the occupancy (removePointsFromField per shape, world_collision_model.cpp:

@@ -181,6 +181,78 @@ def urdf_to_robot_text(urdf_xml: str, group_name: str, group_links, planning_joi
     return "\n".join(out) + "\n"
 
 
+def urdf_to_body_text(urdf_xml: str, collision_yaml_text: str, group: str, meshes=None, values=None) -> str:
+    """URDF + collision-model YAML -> the body text of include/smpl_amd.h "robot body" (DESIGN.md section 20): every link
+    and joint of the URDF (fixed / revolute / continuous / prismatic; planar and floating joints are not supported), a
+    `geom` row per `<collision>` element of a link that has a voxel model -- `<box size>`, `<sphere radius>`,
+    `<cylinder radius length>`, and `<mesh filename>` through `meshes[filename] = (vertices, triangles)`, scaled by the
+    element's `scale`; a mesh that is not supplied is a ValueError, as no mesh file is loaded here -- a `voxels` row per
+    entry of the YAML's `voxels_models`, the links of `group` (group_links_from_collision_yaml) and a `value` row per
+    entry of `values` ({joint: position})."""
+    import xml.etree.ElementTree as ET
+    import yaml
+    rob = ET.fromstring(urdf_xml)
+    if rob.tag != "robot":
+        raise ValueError("not a URDF: root element is <%s>" % rob.tag)
+    doc = yaml.safe_load(collision_yaml_text)
+    vox = [(m["link_name"], float(m["res"])) for m in ((doc.get("robot_collision_model") or {}).get("voxels_models") or [])]
+    links = [l.get("name") for l in rob.findall("link")]
+    for name, _ in vox:
+        if name not in links:
+            raise ValueError("voxels model on %s: the URDF has no such link" % name)
+    group_links = group_links_from_collision_yaml(collision_yaml_text, group, urdf_xml)
+
+    def six(o):
+        xyz = [float(x) for x in (o.get("xyz", "0 0 0") if o is not None else "0 0 0").split()]
+        rpy = [float(x) for x in (o.get("rpy", "0 0 0") if o is not None else "0 0 0").split()]
+        return "%r %r %r  %r %r %r" % tuple(xyz + rpy)
+
+    out = ["robot " + rob.get("name", "robot")] + ["link " + l for l in links]
+    for j in rob.findall("joint"):
+        t = j.get("type")
+        if t not in ("fixed", "revolute", "continuous", "prismatic"):
+            raise ValueError("joint %s: type %s is not supported" % (j.get("name"), t))
+        a = j.find("axis")
+        axis = [float(x) for x in (a.get("xyz", "1 0 0") if a is not None else "1 0 0").split()]   # URDF default axis
+        lim = j.find("limit")
+        lo = float(lim.get("lower", "0")) if lim is not None else 0.0
+        hi = float(lim.get("upper", "0")) if lim is not None else 0.0
+        out.append("joint %s %s %s %s  %s  %r %r %r  %r %r" % (j.get("name"), t, j.find("parent").get("link"), j.find("child").get("link"),
+                                                                six(j.find("origin")), axis[0], axis[1], axis[2], lo, hi))
+    with_model = {name for name, _ in vox}
+    for l in rob.findall("link"):
+        if l.get("name") not in with_model:
+            continue
+        for c in l.findall("collision"):
+            g = c.find("geometry")
+            shape = None if g is None else next(iter(g), None)
+            o = six(c.find("origin"))
+            if shape is None:
+                raise ValueError("link %s: a <collision> element without geometry" % l.get("name"))
+            if shape.tag == "box":
+                out.append("geom %s box %s  %s" % (l.get("name"), " ".join(repr(float(x)) for x in shape.get("size").split()), o))
+            elif shape.tag == "sphere":
+                out.append("geom %s sphere %r  %s" % (l.get("name"), float(shape.get("radius")), o))
+            elif shape.tag == "cylinder":
+                out.append("geom %s cylinder %r %r  %s" % (l.get("name"), float(shape.get("radius")), float(shape.get("length")), o))
+            elif shape.tag == "mesh":
+                f = shape.get("filename")
+                if meshes is None or f not in meshes:
+                    raise ValueError("link %s: mesh %s was not supplied (mesh files are not loaded)" % (l.get("name"), f))
+                s = [float(x) for x in shape.get("scale", "1 1 1").split()]
+                v, t = meshes[f]
+                v = [[float(p[k]) * s[k] for k in range(3)] for p in v]
+                t = [[int(x) for x in q] for q in t]
+                out.append("geom %s mesh %d %d  %s" % (l.get("name"), len(v), len(t), o))
+                out += ["v %r %r %r" % tuple(p) for p in v] + ["t %d %d %d" % tuple(q) for q in t]
+            else:
+                raise ValueError("link %s: <%s> geometry is not supported" % (l.get("name"), shape.tag))
+    out += ["voxels %s %r" % (name, res) for name, res in vox]
+    out.append("group %s %s" % (group, " ".join(group_links)))
+    out += ["value %s %r" % (n, float(q)) for n, q in (values or {}).items()]
+    return "\n".join(out) + "\n"
+
+
 def box_spheres(center, size, pitch, radius):
     """Spheres of one radius on a regular grid that spans a box, corners included, at most `pitch` apart (centre and size
     in a link's frame, metres): n x (x, y, z, r) for Space.attach_body.  Not the reference's mesh voxeliser
