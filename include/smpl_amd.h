@@ -253,7 +253,31 @@ typedef struct smplx_params {
     double padding;                   /* SelfCollisionModel m_padding, default 0 */
     int32_t batch_states;             /* frontier batch B (0 = default 4096) */
     int32_t flags;                    /* SMPLX_SPACE_* bits below; 0 = defaults */
+    int32_t heuristic;                /* SMPLX_H_* below: the heuristic the space plans with; 0 (a zero-initialised
+                                         struct) = the BFS.  Any other value: SMPLX_E_ARG */
 } smplx_params;
+
+/* smplx_params.heuristic: PlannerInterface's search.heuristic.space for arastar + manip
+ * (smpl_ros/src/ros/planner_interface.cpp:855-882).
+ *   SMPLX_H_BFS         BfsHeuristic ("bfs").
+ *   SMPLX_H_EUCLID      EuclidDistHeuristic ("euclid", its pose branch, euclid_dist_heuristic.cpp:124-141, 244-272):
+ *                       h = (int)(1000 sqrt(wx dx^2 + wy dy^2 + wz dz^2 + wr theta^2)) between the planning link's pose
+ *                       and the goal's, theta the angle between the two rotations in [0, pi]; weights 1 until
+ *                       smplx_set_euclid_weights.  The goal rotation: a pose goal's rpy; for a joint goal the planning
+ *                       link's rotation at the goal angles; the identity for smplx_set_goal_xyz.  The metric goal
+ *                       distance, which gates the short and snap primitives, is the plain distance to the goal position.
+ *                       theta comes from the rotation matrices (1 + trace = 4 cos^2(theta / 2)), not from the
+ *                       reference's Euler angles and quaternions: parity of its last bits is unpinned, as for pose goals.
+ *   SMPLX_H_JOINT_DIST  JointDistHeuristic ("joint_distance", joint_dist_heuristic.cpp): h = (int)(1000 |q - goal angles|),
+ *                       raw joint values in variable order, no angle wrapping; 0 for every state unless the goal is a
+ *                       joint goal.  Its metric goal distance is 0.0 everywhere, so the gate sees every state "at the
+ *                       goal": short primitives and the snap are active on every expansion, long ones only with
+ *                       use_long_and_short.  That is the reference's behaviour and is kept.
+ * The goal id has h = 0 under every kind.  A space of a closed-form kind (the last two) has no BFS: it allocates no BFS
+ * buffers, setting its goal runs none, smplx_bfs_size and smplx_bfs_levels return 0, and smplx_bfs_copy,
+ * smplx_bfs_metric_goal_distance and smplx_bfs_metric_start_distance fail with SMPLX_E_STATE.  Everything else -- the
+ * goals, smplx_get_succs, the lazy pair, smplx_plan*, smplx_replan*, both searches -- is the same call for every kind. */
+enum { SMPLX_H_BFS = 0, SMPLX_H_EUCLID = 1, SMPLX_H_JOINT_DIST = 2 };
 
 /* smplx_params.flags: which kernels serve the space.  Results are identical whatever the bits (the parity suite runs
  * every combination); they exist for A/B measurements and for callers that want the reference's own lookup tallies. */
@@ -270,6 +294,8 @@ enum {
  * (manip_lattice_action_space.cpp:103-195, upstream or fork rows). */
 int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const char* mprim_text,
                        const smplx_params* params, smplx_space** out);
+/* the SMPLX_H_* kind the space was created with (SMPLX_E_ARG for a null space) */
+int smplx_space_heuristic(const smplx_space* s);
 void smplx_space_destroy(smplx_space* s);
 /* 1 if the space runs kernels compiled for this robot: at creation the model's kinematic structure is turned into
  * compile-time constants and the kernels are built against them with hiprtc (cached per process and on disk under
@@ -428,8 +454,26 @@ int smplx_rpy_angle(const double a[3], const double b[3], double* theta);
 /* computePlanningLinkFK for n states: the planning link's transform, row-major 3x4 each, by the FK the goal test and
  * the heuristic run (column 3 is bit-equal to smplx_heuristic_batch's xyz) */
 int smplx_planning_pose_batch(smplx_space* s, const double* q, int n, double* T /* n x 12 */);
-/* GetGoalHeuristic for arbitrary states (bfs_heuristic.cpp:148-163); xyz (n*3) may be NULL */
+/* GetGoalHeuristic of the space's heuristic kind for arbitrary states (bfs_heuristic.cpp:148-163,
+ * euclid_dist_heuristic.cpp:118-141, joint_dist_heuristic.cpp:70-88); xyz (n*3) may be NULL */
 int smplx_heuristic_batch(smplx_space* s, const double* q, int n, int32_t* h, double* xyz);
+/* setWeightX / Y / Z / Rot of a SMPLX_H_EUCLID space (euclid_dist_heuristic.cpp:78-96), w = {x, y, z, rot}.  The
+ * reference's factory passes its x coefficient to all four setters (planner_interface.cpp:472-475): that is the caller's
+ * to copy.  SMPLX_E_ARG: a negative or non-finite weight; SMPLX_E_STATE: the space's kind is not SMPLX_H_EUCLID.
+ * Afterwards the space has no goal, as after a field edit: every h recorded so far used the old weights, so set the goal
+ * again before any query. */
+int smplx_set_euclid_weights(smplx_space* s, const double w[4]);
+/* getMetricGoalDistance of the space's heuristic kind for n workspace points xyz[n*3]: the value the action space gates the
+ * short and snap primitives on.  SMPLX_H_BFS: smplx_bfs_metric_goal_distance; SMPLX_H_EUCLID: the distance to the goal
+ * position; SMPLX_H_JOINT_DIST: 0.0.  SMPLX_E_STATE without a goal. */
+int smplx_metric_goal_distance(smplx_space* s, const double* xyz, int n, double* out);
+/* The arithmetic of the two closed-form heuristics on the host, the very functions the kernels compile
+ * (smpl_amd/csrc/heuristics.h); they need no space and no GPU.  (int)(1000 * dist) is the h of a state at pose Ta
+ * (row-major 3x4, as smplx_planning_pose_batch gives it) under a goal at pose Tb with weights w = {x, y, z, rot}, and of a
+ * state with joint values a under goal angles b.  SMPLX_E_ARG: a null pointer, a non-finite value, a negative weight,
+ * n < 0 or n > 16. */
+int smplx_pose_distance(const double Ta[12], const double Tb[12], const double w[4], double* dist);
+int smplx_joint_distance(const double* a, const double* b, int n, double* dist);
 /* BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) for n workspace points xyz[n*3]:
  * BFS cell distance * resolution, WALL * resolution outside the grid.  This is the value the action space gates the
  * short / snap primitives on (manip_lattice_action_space.cpp:393-397). */
@@ -437,7 +481,8 @@ int smplx_bfs_metric_goal_distance(smplx_space* s, const double* xyz, int n, dou
 /* BfsHeuristic::getMetricStartDistance (bfs_heuristic.cpp:103-127): Manhattan cell distance to the cell of the start
  * state's planning link, times the resolution (needs smplx_set_start) */
 int smplx_bfs_metric_start_distance(smplx_space* s, const double* xyz, int n, double* out);
-/* the padded (nx+2)(ny+2)(nz+2) BFS_3D distance grid, node order of bfs3d.h:213-220 */
+/* the padded (nx+2)(ny+2)(nz+2) BFS_3D distance grid, node order of bfs3d.h:213-220.  A space of a closed-form heuristic
+ * kind has none: smplx_bfs_size is 0 and smplx_bfs_copy, like the two calls above, fails with SMPLX_E_STATE. */
 int64_t smplx_bfs_size(const smplx_space* s);
 int smplx_bfs_copy(smplx_space* s, int32_t* out);
 /* passes the last BFS took: sweeps over the queued 8x8x8 bricks (the device keeps the grid in brick-major records); after

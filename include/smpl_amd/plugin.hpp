@@ -520,6 +520,9 @@ public:
         case XYZ_GOAL: {
             const std::vector<double>& p = goal.tgt_off_pose.size() >= 3 ? goal.tgt_off_pose : goal.pose;
             if (p.size() < 3) return false;
+            // EuclidDistHeuristic measures against the rotation of the pose's rpy even under an XYZ goal; smplx_set_goal_xyz
+            // has no way to pass one and measures against the identity (rpy 0 0 0): a wrong h is worse than a refusal
+            if (smplx_space_heuristic(ctx_->space()) == SMPLX_H_EUCLID && p.size() >= 6 && (p[3] != 0.0 || p[4] != 0.0 || p[5] != 0.0)) return false;
             const double xyz[3] = {p[0], p[1], p[2]};
             ok = setGoalPosition(xyz, goal.xyz_tolerance);
         } break;
@@ -647,6 +650,11 @@ class GpuBfsHeuristic : public RobotHeuristic {
 public:
     using Extension::getExtension;   // keep the typed lookup visible next to the override
     explicit GpuBfsHeuristic(GpuPlanningContext* ctx) : ctx_(ctx) {}
+    // fails if the context's space was created with another kind (smplx_params.heuristic): its h would not be the BFS's
+    bool init(RobotPlanningSpace* space)
+    {
+        return smplx_space_heuristic(ctx_->space()) == SMPLX_H_BFS && RobotHeuristic::init(space);
+    }
     int GetGoalHeuristic(int state_id) override
     {
         int32_t h = 0;
@@ -676,6 +684,112 @@ public:
     }
 
 private:
+    GpuPlanningContext* ctx_;
+};
+
+// sbpl::motion::EuclidDistHeuristic (smpl/include/smpl/heuristic/euclid_dist_heuristic.h:44-105) over a space created with
+// smplx_params.heuristic = SMPLX_H_EUCLID.  h to the goal is the engine's (every kernel's); between two states it is the
+// same arithmetic on the host (smplx_pose_distance over smplx_planning_pose_batch).  The distance is symmetric bit for bit
+// (squares of the differences, the trace of the same nine products), so "from the goal" is "to the goal".
+// The weight setters mirror setWeightX / Y / Z / Rot; after any of them the goal must be set again (smplx_set_euclid_weights).
+// The reference's factory passes its x coefficient to all four setters (planner_interface.cpp:472-475): a quirk that is the
+// caller's to copy, not this class's.
+class GpuEuclidDistHeuristic : public RobotHeuristic {
+public:
+    using Extension::getExtension;
+    explicit GpuEuclidDistHeuristic(GpuPlanningContext* ctx) : ctx_(ctx) {}
+    bool init(RobotPlanningSpace* space)
+    {
+        return smplx_space_heuristic(ctx_->space()) == SMPLX_H_EUCLID && RobotHeuristic::init(space);
+    }
+    bool setWeightX(double wx) { w_[0] = wx; return push(); }
+    bool setWeightY(double wy) { w_[1] = wy; return push(); }
+    bool setWeightZ(double wz) { w_[2] = wz; return push(); }
+    bool setWeightRot(double wr) { w_[3] = wr; return push(); }
+    int GetGoalHeuristic(int state_id) override                                          // euclid_dist_heuristic.cpp:118-141
+    {
+        int32_t h = 0;
+        return smplx_get_goal_heuristic(ctx_->space(), state_id, &h) == SMPLX_OK ? h : 0;
+    }
+    int GetStartHeuristic(int) override { return 0; }                                    // :161-164
+    int GetFromToHeuristic(int from_id, int to_id) override                              // :166-191
+    {
+        const int goal = smplx_goal_id(ctx_->space());
+        if (from_id == goal) return GetGoalHeuristic(to_id);
+        if (to_id == goal) return GetGoalHeuristic(from_id);
+        double Ta[12], Tb[12], d = 0.0;
+        if (!pose(from_id, Ta) || !pose(to_id, Tb) || smplx_pose_distance(Ta, Tb, w_, &d) != SMPLX_OK) return 0;
+        return (int)(1000.0 * d);
+    }
+    double getMetricGoalDistance(double x, double y, double z) override                  // :98-102
+    {
+        const double p[3] = {x, y, z};
+        double d = 0.0;
+        return smplx_metric_goal_distance(ctx_->space(), p, 1, &d) == SMPLX_OK ? d : 0.0;
+    }
+    double getMetricStartDistance(double, double, double) override { return 0.0; }       // :104-108
+    Extension* getExtension(size_t class_code) override
+    {
+        return class_code == GetClassCode<RobotHeuristic>() ? this : nullptr;            // :110-116
+    }
+
+private:
+    bool push() { return smplx_set_euclid_weights(ctx_->space(), w_) == SMPLX_OK; }
+    bool pose(int id, double T[12])
+    {
+        std::vector<double> q((size_t)ctx_->nvars());
+        return smplx_get_state(ctx_->space(), id, q.data(), nullptr) == SMPLX_OK &&
+               smplx_planning_pose_batch(ctx_->space(), q.data(), 1, T) == SMPLX_OK;
+    }
+    GpuPlanningContext* ctx_;
+    double w_[4] = {1.0, 1.0, 1.0, 1.0};                                                 // euclid_dist_heuristic.h:77-80
+};
+
+// sbpl::motion::JointDistHeuristic (smpl/include/smpl/heuristic/joint_dist_heuristic.h:44-73) over a space created with
+// smplx_params.heuristic = SMPLX_H_JOINT_DIST.  Both metric distances are 0.0, as the reference's are.
+class GpuJointDistHeuristic : public RobotHeuristic {
+public:
+    using Extension::getExtension;
+    explicit GpuJointDistHeuristic(GpuPlanningContext* ctx) : ctx_(ctx) {}
+    bool init(RobotPlanningSpace* space)
+    {
+        return smplx_space_heuristic(ctx_->space()) == SMPLX_H_JOINT_DIST && RobotHeuristic::init(space);
+    }
+    int GetGoalHeuristic(int state_id) override                                          // joint_dist_heuristic.cpp:70-88
+    {
+        int32_t h = 0;
+        return smplx_get_goal_heuristic(ctx_->space(), state_id, &h) == SMPLX_OK ? h : 0;
+    }
+    int GetStartHeuristic(int state_id) override                                         // :90-103
+    {
+        const int start = smplx_start_id(ctx_->space());
+        return state_id == start ? 0 : between(start, state_id);
+    }
+    int GetFromToHeuristic(int from_id, int to_id) override                              // :105-124
+    {
+        const int goal = smplx_goal_id(ctx_->space());
+        if (from_id == goal) return GetGoalHeuristic(to_id);
+        if (to_id == goal) return GetGoalHeuristic(from_id);
+        return between(from_id, to_id);
+    }
+    double getMetricGoalDistance(double, double, double) override { return 0.0; }        // :52-55
+    double getMetricStartDistance(double, double, double) override { return 0.0; }       // :57-60
+    Extension* getExtension(size_t class_code) override
+    {
+        return class_code == GetClassCode<RobotHeuristic>() ? this : nullptr;            // :62-68
+    }
+
+private:
+    int between(int a, int b)
+    {
+        const int n = ctx_->nvars();
+        std::vector<double> qa((size_t)n), qb((size_t)n);
+        double d = 0.0;
+        if (smplx_get_state(ctx_->space(), a, qa.data(), nullptr) != SMPLX_OK || smplx_get_state(ctx_->space(), b, qb.data(), nullptr) != SMPLX_OK ||
+            smplx_joint_distance(qa.data(), qb.data(), n, &d) != SMPLX_OK)
+            return 0;
+        return (int)(1000.0 * d);
+    }
     GpuPlanningContext* ctx_;
 };
 

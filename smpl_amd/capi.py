@@ -47,7 +47,13 @@ SYMBOLS = [
     "smplx_body_create", "smplx_body_destroy", "smplx_body_counts", "smplx_body_set_joint", "smplx_body_joint",
     "smplx_body_link_transforms", "smplx_body_model_link", "smplx_body_model_points", "smplx_body_dirty",
     "smplx_grid_put_body", "smplx_grid_take_body", "smplx_grid_body_cells",
+    "smplx_set_euclid_weights", "smplx_metric_goal_distance", "smplx_pose_distance", "smplx_joint_distance",
+    "smplx_space_heuristic",
 ]
+
+# smplx_params.heuristic (include/smpl_amd.h)
+H_BFS, H_EUCLID, H_JOINT_DIST = 0, 1, 2
+E_STATE = -5
 
 # smplx_time_params.type and smplx_replan_stats.result (include/smpl_amd.h)
 TIME_EXPANSIONS, TIME_WALL = 0, 1
@@ -59,7 +65,7 @@ class Params(C.Structure):
                 ("use_short_dist_mprims", C.c_int32), ("short_dist_mprims_thresh", C.c_double),
                 ("use_xyzrpy_snap_mprim", C.c_int32), ("xyzrpy_snap_dist_thresh", C.c_double),
                 ("xy_rotate_by_var3", C.c_int32), ("use_long_and_short", C.c_int32), ("padding", C.c_double),
-                ("batch_states", C.c_int32), ("flags", C.c_int32)]
+                ("batch_states", C.c_int32), ("flags", C.c_int32), ("heuristic", C.c_int32)]
 
 
 class SearchParams(C.Structure):
@@ -129,6 +135,13 @@ def lib():
         L.smplx_goal_orientation.argtypes = [C.c_void_p, _dp, _dp]
         L.smplx_planning_pose_batch.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
         L.smplx_rpy_angle.argtypes = [_dp, _dp, _dp]
+        L.smplx_set_euclid_weights.argtypes = [C.c_void_p, _dp]
+        L.smplx_metric_goal_distance.argtypes = [C.c_void_p, _dp, C.c_int, _dp]
+        L.smplx_pose_distance.argtypes = [_dp, _dp, _dp, _dp]
+        L.smplx_joint_distance.argtypes = [_dp, _dp, C.c_int, _dp]
+        L.smplx_test_acos.argtypes = [_dp, C.c_int, _dp]
+        L.smplx_test_goal_rotation.argtypes = [C.c_void_p, _dp]
+        L.smplx_space_heuristic.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -158,6 +171,31 @@ def rpy_angle(a, b):
     x = _f64(a); y = _f64(b); t = C.c_double(0.0)
     _chk(lib().smplx_rpy_angle(_p(x, _dp), _p(y, _dp), C.byref(t)))
     return t.value
+
+
+def pose_distance(Ta, Tb, w=(1.0, 1.0, 1.0, 1.0)):
+    """EuclidDistHeuristic's distance between two 3x4 (or 4x4) transforms with weights {x, y, z, rot} (smplx_pose_distance):
+    int(1000 * it) is the h of a SMPLX_H_EUCLID space.  Host arithmetic, needs no GPU."""
+    a = _f64(np.asarray(Ta, float).reshape(-1)[:12]); b = _f64(np.asarray(Tb, float).reshape(-1)[:12]); ww = _f64(w)
+    d = C.c_double(0.0)
+    _chk(lib().smplx_pose_distance(_p(a, _dp), _p(b, _dp), _p(ww, _dp), C.byref(d)))
+    return d.value
+
+
+def joint_distance(a, b):
+    """JointDistHeuristic's distance between two joint vectors (smplx_joint_distance).  Host arithmetic, needs no GPU."""
+    x = _f64(a).reshape(-1); y = _f64(b).reshape(-1)
+    assert x.shape == y.shape
+    d = C.c_double(0.0)
+    _chk(lib().smplx_joint_distance(_p(x, _dp), _p(y, _dp), x.shape[0], C.byref(d)))
+    return d.value
+
+
+def host_acos(x):
+    """Test hook (csrc/test_hooks.h smplx_test_acos): the host build of smplx_acos at every element of x."""
+    a = _f64(x).reshape(-1); out = np.zeros(a.shape[0])
+    _chk(lib().smplx_test_acos(_p(a, _dp), a.shape[0], _p(out, _dp)))
+    return out
 
 
 def table_probe(nvars, slots, one_home, inserted, queries):
@@ -507,7 +545,7 @@ class Space:
 
     def __init__(self, model: Model, grid: Grid, mprim_text: str, params, batch_states: int = 0, fused: bool = False,
                  tiny_work_list: bool = False, no_small_kernel: bool = False, generic_kernels: bool = False,
-                 padding: float = 0.0):
+                 padding: float = 0.0, heuristic: int = H_BFS):
         self.model, self.grid = model, grid
         P = Params()
         for i, r in enumerate(params.resolutions):
@@ -523,6 +561,8 @@ class Space:
         P.padding = padding
         P.batch_states = batch_states
         P.flags = (1 if fused else 0) | (4 if no_small_kernel else 0) | (8 if generic_kernels else 0)
+        P.heuristic = int(heuristic)
+        self.heuristic = int(heuristic)
         self.h = C.c_void_p()
         _chk(lib().smplx_space_create(model.h, grid.h, mprim_text.encode(), C.byref(P), C.byref(self.h)))
         if tiny_work_list:   # test hook (smpl_amd/csrc/test_hooks.h; not part of include/smpl_amd.h)
@@ -533,15 +573,16 @@ class Space:
 
     @classmethod
     def from_config(cls, cfg, batch_states: int = 0, xy_rotate=None, fused: bool = False, tiny_work_list: bool = False,
-                    no_small_kernel: bool = False, generic_kernels: bool = False, padding: float = 0.0):
-        g = Grid(cfg.grid.origin, cfg.grid.dims, cfg.grid.res, cfg.grid.max_dist, cfg.grid.d2)
+                    no_small_kernel: bool = False, generic_kernels: bool = False, padding: float = 0.0, heuristic: int = H_BFS,
+                    grid=None):
+        g = grid if grid is not None else Grid(cfg.grid.origin, cfg.grid.dims, cfg.grid.res, cfg.grid.max_dist, cfg.grid.d2)
         m = Model(cfg.robot_text)
         p = cfg.params
         if xy_rotate is not None:
             import copy
             p = copy.copy(p)
             p.xy_rotate_by_var3 = xy_rotate
-        return cls(m, g, cfg.mprim, p, batch_states, fused, tiny_work_list, no_small_kernel, generic_kernels, padding)
+        return cls(m, g, cfg.mprim, p, batch_states, fused, tiny_work_list, no_small_kernel, generic_kernels, padding, heuristic)
 
     def specialized(self):
         """(True/False, note): whether the space runs the per-robot kernel build (smplx_space_specialized)."""
@@ -743,6 +784,23 @@ class Space:
         _chk(lib().smplx_bfs_metric_goal_distance(self.h, _p(xyz, _dp), xyz.shape[0], _p(out, _dp)))
         return out
 
+    def heuristic_metric_goal_distance(self, xyz):
+        """getMetricGoalDistance of the space's heuristic kind (smplx_metric_goal_distance): the BFS's for H_BFS"""
+        xyz = _f64(xyz).reshape(-1, 3); out = np.zeros(xyz.shape[0])
+        _chk(lib().smplx_metric_goal_distance(self.h, _p(xyz, _dp), xyz.shape[0], _p(out, _dp)))
+        return out
+
+    def goal_rotation(self):
+        """Test hook (csrc/test_hooks.h smplx_test_goal_rotation): the goal rotation an H_EUCLID space measures against"""
+        R = np.zeros((3, 3))
+        _chk(lib().smplx_test_goal_rotation(self.h, _p(R, _dp)))
+        return R
+
+    def set_euclid_weights(self, w):
+        """setWeightX / Y / Z / Rot of an H_EUCLID space; the goal must be set again afterwards"""
+        ww = _f64(w).reshape(4)
+        _chk(lib().smplx_set_euclid_weights(self.h, _p(ww, _dp)))
+
     def metric_start_distance(self, xyz):
         xyz = _f64(xyz).reshape(-1, 3); out = np.zeros(xyz.shape[0])
         _chk(lib().smplx_bfs_metric_start_distance(self.h, _p(xyz, _dp), xyz.shape[0], _p(out, _dp)))
@@ -759,6 +817,10 @@ class Space:
         _chk(lib().smplx_bfs_copy(self.h, _p(out, _ip)))
         g = self.grid.dims
         return out.reshape(g[2] + 2, g[1] + 2, g[0] + 2)
+
+    def bfs_size(self):
+        """cells of the padded BFS grid; 0 for a space of a closed-form heuristic kind, which has none"""
+        return lib().smplx_bfs_size(self.h)
 
     def bfs_levels(self):
         return lib().smplx_bfs_levels(self.h)

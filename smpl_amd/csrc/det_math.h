@@ -64,6 +64,36 @@ SMPLX_HD void smplx_sincos(double x, double* s_out, double* c_out)
     *c_out = (k == 0) ? kc : (k == 1) ? -ks : (k == 2) ? -kc : ks;
 }
 
+// acos(x) for x in [0, 1] (the argument is a clamped |cosine|; anything outside is the caller's to clamp): the
+// rational approximation R(z) of (asin(t) - t) / t^3, z = t^2, on [0, 1/4] that the public fdlibm uses (e_acos.c).
+//   x <  1/2: pi/2 - (x + x R(x^2)), pi/2 in two pieces
+//   x >= 1/2: z = (1 - x) / 2, s = sqrt(z), acos = 2 (s + s R(z)); s is cut into a 26-bit head and its tail with a
+//             Veltkamp split (a multiplication and two subtractions, no bit operations), so that head^2 is exact
+// A fixed sequence of + - * / sqrt, the same bits on host and device.  Accuracy against the true value, measured over
+// [0, 1] with the 192-bit reference of tests/kinematics_ref.py (tests/test_heuristics_host.py holds it to twice this):
+// at most 0.77 ulp; exact at 0 (the double nearest pi/2) and at 1 (0).
+// Stands in for std::acos in the reference's orientation distance (euclid_dist_heuristic.cpp:266).
+SMPLX_HD double smplx_acos(double x)
+{
+    const double PIO2_HI = 1.57079632679489655800e+00, PIO2_LO = 6.12323399573676603587e-17;
+    const double P0 = 1.66666666666666657415e-01, P1 = -3.25565818622400915405e-01, P2 = 2.01212532134862925881e-01,
+                 P3 = -4.00555345006794114027e-02, P4 = 7.91534994289814532176e-04, P5 = 3.47933107596021167570e-05;
+    const double Q1 = -2.40339491173441421878e+00, Q2 = 2.02094576023350569471e+00, Q3 = -6.88283971605453293030e-01,
+                 Q4 = 7.70381505559019352791e-02;
+    const bool low = x < 0.5;
+    const double z = low ? x * x : (1.0 - x) * 0.5;
+    const double p = z * (P0 + z * (P1 + z * (P2 + z * (P3 + z * (P4 + z * P5)))));
+    const double q = 1.0 + z * (Q1 + z * (Q2 + z * (Q3 + z * Q4)));
+    const double r = p / q;
+    if (low) return PIO2_HI - (x - (PIO2_LO - x * r));
+    const double s = sqrt(z);
+    const double t = s * 134217729.0;          // 2^27 + 1
+    const double df = t - (t - s);
+    const double c = s > 0.0 ? (z - df * df) / (s + df) : 0.0;      // x = 1: 0 / 0 otherwise
+    const double w = r * s + c;
+    return 2.0 * (df + w);
+}
+
 // smpl/include/smpl/angles.h:45-62
 SMPLX_HD double smplx_normalize_angle(double angle)
 {

@@ -109,6 +109,23 @@ struct SmplxGridDev {
 // 0xF0000000): a cell whose tag is not the current run's counts as UNDISCOVERED, so a new goal needs no pass over the records
 // to reset them (BFS_3D::run's reset loop, bfs3d.cpp:162-166, was a tenth of a goal at 512^3) except every seventh, when the
 // tags wrap.  -1 reads as tag 15, which no run has.  Grids of 2^28 cells or more run with tag_mask = 0 and a reset per goal.
+// Which heuristic a space plans with (smplx_params.heuristic; the values are the public SMPLX_H_*): the BFS over the grid,
+// or one of the two closed forms of heuristics.h.  A space of a closed-form kind has no BFS grid (SmplxBfsDev::dist is
+// null); what its heuristic needs of the goal is this record, part of the space's device image and rewritten with every
+// goal.  It keeps its own copy of the goal position, rotation and angles, so the kernels' non-BFS arm reads one record
+// through one pointer and the BFS arm passes nothing new around.
+//   rot: pose goal -- the rotation of its rpy (SmplxGoalDev::rot); joint goal -- the planning link's rotation at the goal
+//        angles (planner_interface.cpp:1236-1238); xyz goal -- the identity
+//   joint_goal: 1 under a joint goal; JointDistHeuristic is 0 everywhere under any other (joint_dist_heuristic.cpp:78-81)
+enum { SMPLX_HEUR_BFS = 0, SMPLX_HEUR_EUCLID = 1, SMPLX_HEUR_JOINT_DIST = 2 };
+struct SmplxHeurDev {
+    int32_t kind, joint_goal;
+    double w[4];                  // EuclidDistHeuristic's x, y, z and rotation coefficients
+    double xyz[3];
+    double rot[9];
+    double angles[SMPLX_MAX_VARS];
+};
+
 #define SMPLX_BFS_REC 1024
 #define SMPLX_BFS_FACES 512
 #define SMPLX_BFS_EDGES 896
@@ -118,7 +135,15 @@ struct SmplxBfsDev {
     int32_t dim_x, dim_y, dim_z, dim_xy;     // padded dims (bfs3d.cpp:61-66): what inBounds compares with
     int32_t cost_per_cell, tag_word;
     int32_t nbx, nby, nbz, tag_mask;         // bricks per axis
-    const int32_t* dist;                      // nbx * nby * nbz records
+    // A space of a closed-form kind has no BFS grid: every field above is 0 in it, and dim_x == 0 is how the kernels tell
+    // (per space: the spaces of one grouped launch may differ in kind).  The pointer is then the space's heuristic record
+    // (SmplxSpaceDev::heur of the same device image), whose kind is SMPLX_HEUR_EUCLID or SMPLX_HEUR_JOINT_DIST.  One
+    // pointer and one test on a field the BFS arm reads anyway: the dispatch keeps nothing more alive across the
+    // planning-link chain than the BFS did alone (a second pointer cost the per-robot k_pipe_setup an occupancy step).
+    union {
+        const int32_t* dist;                  // dim_x > 0: nbx * nby * nbz records
+        const SmplxHeurDev* heur;             // dim_x == 0
+    };
 };
 
 // One goal of a BFS run that sets the goals of several spaces in shared launches (k_bfs_brick_seed_multi,
@@ -236,6 +261,7 @@ struct SmplxSpaceDev {
     SmplxTableDev table;
     SmplxSearchDev* search;       // device-resident ARA* of this query (null until the first device search)
     const SmplxBodiesDev* bodies; // attached bodies, null while the space has none
+    SmplxHeurDev heur;            // what a closed-form heuristic needs of the goal (bfs.heur points here in such a space)
 };
 
 // ---------------------------------------------------------------------------------------------------------------------

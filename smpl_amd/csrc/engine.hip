@@ -18,6 +18,7 @@
 
 #include "../../include/smpl_amd.h"
 #include "det_math.h"
+#include "heuristics.h"
 #include "device_types.h"
 #include "kernels.h"
 #include "model_compile.h"
@@ -68,6 +69,12 @@ bool host_check_limits(const SmplxModelDev& m, const double* q)
     return true;
 }
 
+static_assert(SMPLX_HEUR_BFS == SMPLX_H_BFS && SMPLX_HEUR_EUCLID == SMPLX_H_EUCLID && SMPLX_HEUR_JOINT_DIST == SMPLX_H_JOINT_DIST,
+              "the device's heuristic kinds are the public ones");
+
+// does the space plan with one of the closed forms of heuristics.h (no BFS: bfs_host.h is never entered for it)
+bool closed_form(const smplx_space* s) { return s->params.heuristic != SMPLX_H_BFS; }
+
 int run_heuristic(smplx_space* s, const double* q, int n, int32_t* h, double* xyz)
 {
     const int N = s->N;
@@ -75,7 +82,11 @@ int run_heuristic(smplx_space* s, const double* q, int n, int32_t* h, double* xy
     if (int e = s->b_h.reserve(n)) return e;
     if (int e = s->b_xyz.reserve((size_t)n * 3)) return e;
     HIP_TRY(hipMemcpyAsync(s->batch.b_q.p, q, sizeof(double) * n * N, hipMemcpyHostToDevice, s->stream));
-    KLAUNCH(s, K_HEURISTIC, k_heuristic, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space, s->batch.b_q.p, n,
+    if (closed_form(s))
+        KLAUNCH(s, K_HEURISTIC_CLOSED, k_heuristic_closed, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space,
+                s->batch.b_q.p, n, s->b_h.p, s->b_xyz.p);
+    else
+        KLAUNCH(s, K_HEURISTIC, k_heuristic, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), s->blob_bytes, s->stream, s->d_space, s->batch.b_q.p, n,
                        s->b_h.p, s->b_xyz.p);
     HIP_TRY(hipGetLastError());
     if (h) HIP_TRY(hipMemcpyAsync(h, s->b_h.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
@@ -256,6 +267,8 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
                        smplx_space** out)
 {
     if (!model || !grid || !mprim_text || !params || !out) return set_error(SMPLX_E_ARG, "null argument");
+    if (params->heuristic != SMPLX_H_BFS && params->heuristic != SMPLX_H_EUCLID && params->heuristic != SMPLX_H_JOINT_DIST)
+        return set_error(SMPLX_E_ARG, "smplx_params.heuristic: SMPLX_H_BFS, SMPLX_H_EUCLID or SMPLX_H_JOINT_DIST");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_error(SMPLX_E_HIP, "no HIP device: the engine has no CPU path");
     smplx_space* s = new smplx_space;
@@ -308,7 +321,7 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
         smplx::generic_kernels(s->ks);
         if (params->flags & SMPLX_SPACE_GENERIC_KERNELS) s->specialize_note = "disabled by SMPLX_SPACE_GENERIC_KERNELS";
         else if (env && env[0] == '0') s->specialize_note = "disabled by SMPLX_SPECIALIZE=0";
-        else if (!smplx::specialized_kernels(s->model.dev, s->ks, s->specialize_note) && env && env[0] == '2') {
+        else if (!smplx::specialized_kernels(s->model.dev, closed_form(s), s->ks, s->specialize_note) && env && env[0] == '2') {
             // SMPLX_SPECIALIZE=2: the per-robot build is required
             const std::string msg = "kernel specialisation failed: " + s->specialize_note;
             smplx_space_destroy(s);
@@ -326,24 +339,33 @@ int smplx_space_create(const smplx_model* model, const smplx_grid* grid, const c
     if ((e = hipEventCreateWithFlags(&s->batch.done, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
     if ((e = hipMalloc((void**)&s->d_space, sizeof(SmplxSpaceDev))) != hipSuccess) return bail(e, "hipMalloc space");
     const int dx = grid->n[0] + 2, dy = grid->n[1] + 2, dz = grid->n[2] + 2;
-    s->bfs.total = (int64_t)dx * dy * dz;
     for (int a = 0; a < 3; ++a) s->bfs.bricks[a] = (grid->n[a] + 7) / 8;
     const size_t nbricks = (size_t)s->bfs.bricks[0] * s->bfs.bricks[1] * s->bfs.bricks[2];
-    s->bfs.ints = (int64_t)nbricks * SMPLX_BFS_REC;
-    if ((e = hipMalloc((void**)&s->bfs.d_dist, sizeof(int32_t) * s->bfs.ints)) != hipSuccess) return bail(e, "hipMalloc bfs");
-    if ((e = hipMalloc((void**)&s->bfs.d_brick_queued, sizeof(int32_t) * 2 * nbricks + 64)) != hipSuccess) return bail(e, "hipMalloc bfs queued");
-    if ((e = hipMemset(s->bfs.d_brick_queued, 0, sizeof(int32_t) * 2 * nbricks + 64)) != hipSuccess) return bail(e, "hipMemset bfs queued");
-    if ((e = hipMalloc((void**)&s->bfs.d_queue, sizeof(int32_t) * (2 * 16 * nbricks + 64))) != hipSuccess) return bail(e, "hipMalloc bfs queue");
-    if ((e = hipMalloc((void**)&s->bfs.d_counts, sizeof(int32_t) * (3 * 16 * 32 + kBfsHistory))) != hipSuccess) return bail(e, "hipMalloc bfs counts");
-    s->hs.bfs.dim_x = dx; s->hs.bfs.dim_y = dy; s->hs.bfs.dim_z = dz; s->hs.bfs.dim_xy = dx * dy;
-    s->hs.bfs.cost_per_cell = params->cost_per_cell;
-    s->hs.bfs.nbx = s->bfs.bricks[0]; s->hs.bfs.nby = s->bfs.bricks[1]; s->hs.bfs.nbz = s->bfs.bricks[2];
-    s->hs.bfs.dist = s->bfs.d_dist;
-    s->hs.bfs.tag_mask = (int64_t)grid->n[0] * grid->n[1] * grid->n[2] < ((int64_t)1 << 28) ? (int32_t)0xF0000000u : 0;
-    s->hs.bfs.tag_word = 0;
-    // BfsHeuristic::syncGridAndBfs (bfs_heuristic.cpp:331-353), once, at init
-    hipLaunchKernelGGL(k_bfs_init, dim3(2048), dim3(256), 0, s->stream, grid->dev, s->bfs.wall_thr, s->bfs.bricks[0], s->bfs.bricks[1], s->bfs.bricks[2], s->bfs.d_dist);
-    if ((e = hipGetLastError()) != hipSuccess) return bail(e, "k_bfs_init");
+    s->hs.heur.kind = params->heuristic;
+    for (int k = 0; k < 4; ++k) s->hs.heur.w[k] = 1.0;          // euclid_dist_heuristic.h:77-80
+    for (int k = 0; k < 9; ++k) s->hs.heur.rot[k] = s->goal_rot[k];
+    if (closed_form(s)) {
+        // no BFS: no distance records, no brick lists, no wall sync (bfs.total stays 0, hs.bfs all zero); the kernels find
+        // the heuristic record of this space's device image through hs.bfs.heur (device_types.h SmplxBfsDev)
+        s->hs.bfs.heur = reinterpret_cast<const SmplxHeurDev*>(reinterpret_cast<const unsigned char*>(s->d_space) + offsetof(SmplxSpaceDev, heur));
+    } else {
+        s->bfs.total = (int64_t)dx * dy * dz;
+        s->bfs.ints = (int64_t)nbricks * SMPLX_BFS_REC;
+        if ((e = hipMalloc((void**)&s->bfs.d_dist, sizeof(int32_t) * s->bfs.ints)) != hipSuccess) return bail(e, "hipMalloc bfs");
+        if ((e = hipMalloc((void**)&s->bfs.d_brick_queued, sizeof(int32_t) * 2 * nbricks + 64)) != hipSuccess) return bail(e, "hipMalloc bfs queued");
+        if ((e = hipMemset(s->bfs.d_brick_queued, 0, sizeof(int32_t) * 2 * nbricks + 64)) != hipSuccess) return bail(e, "hipMemset bfs queued");
+        if ((e = hipMalloc((void**)&s->bfs.d_queue, sizeof(int32_t) * (2 * 16 * nbricks + 64))) != hipSuccess) return bail(e, "hipMalloc bfs queue");
+        if ((e = hipMalloc((void**)&s->bfs.d_counts, sizeof(int32_t) * (3 * 16 * 32 + kBfsHistory))) != hipSuccess) return bail(e, "hipMalloc bfs counts");
+        s->hs.bfs.dim_x = dx; s->hs.bfs.dim_y = dy; s->hs.bfs.dim_z = dz; s->hs.bfs.dim_xy = dx * dy;
+        s->hs.bfs.cost_per_cell = params->cost_per_cell;
+        s->hs.bfs.nbx = s->bfs.bricks[0]; s->hs.bfs.nby = s->bfs.bricks[1]; s->hs.bfs.nbz = s->bfs.bricks[2];
+        s->hs.bfs.dist = s->bfs.d_dist;
+        s->hs.bfs.tag_mask = (int64_t)grid->n[0] * grid->n[1] * grid->n[2] < ((int64_t)1 << 28) ? (int32_t)0xF0000000u : 0;
+        s->hs.bfs.tag_word = 0;
+        // BfsHeuristic::syncGridAndBfs (bfs_heuristic.cpp:331-353), once, at init
+        hipLaunchKernelGGL(k_bfs_init, dim3(2048), dim3(256), 0, s->stream, grid->dev, s->bfs.wall_thr, s->bfs.bricks[0], s->bfs.bricks[1], s->bfs.bricks[2], s->bfs.d_dist);
+        if ((e = hipGetLastError()) != hipSuccess) return bail(e, "k_bfs_init");
+    }
     {
         // Device copy of the state table (K5).  The K5 entry points and smplx_table_sync create it on first use.  The
         // planner's own batches use it only with SMPLX_DEVICE_TABLE=1: measured on MI355X (cfg 2 / cfg 4, bench.py) the
@@ -447,6 +469,29 @@ int smplx_test_set_search_capacity(smplx_space* s, int states)
     return SMPLX_OK;
 }
 
+int smplx_test_acos(const double* x, int n, double* out)
+{
+    if (!x || !out || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    for (int i = 0; i < n; ++i) out[i] = smplx_acos(x[i]);
+    return SMPLX_OK;
+}
+
+int smplx_test_goal_rotation(const smplx_space* s, double R[9])
+{
+    if (!s || !R) return set_error(SMPLX_E_ARG, "null argument");
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
+    for (int k = 0; k < 9; ++k) R[k] = s->goal_rot[k];
+    return SMPLX_OK;
+}
+
+int smplx_test_const_header(const smplx_model* m, int closed_form, char* out, int cap)
+{
+    if (!m) return set_error(SMPLX_E_ARG, "null argument");
+    const std::string h = smplx::model_const_header(m->hm.dev) + (closed_form ? smplx::kClosedFormDefine : "");
+    if (out && cap > 0) { std::strncpy(out, h.c_str(), cap - 1); out[cap - 1] = 0; }
+    return (int)h.size() + 1;
+}
+
 int smplx_search_counters(const smplx_space* s, int64_t out[16])
 {
     if (!s || !out) return set_error(SMPLX_E_ARG, "null argument");
@@ -516,6 +561,7 @@ int smplx_test_table_probe(int nvars, int slots, int one_home, const int32_t* in
 }
 
 int smplx_space_num_vars(const smplx_space* s) { return s ? s->N : 0; }
+int smplx_space_heuristic(const smplx_space* s) { return s ? s->params.heuristic : SMPLX_E_ARG; }
 int smplx_space_num_prims(const smplx_space* s) { return s ? s->M : 0; }
 
 int smplx_space_discretization(const smplx_space* s, int32_t* coord_vals, double* coord_deltas)
@@ -891,6 +937,15 @@ int smplx_cc_attached_positions(smplx_space* s, const double* q, int n, double* 
 static int begin_goal(smplx_space* s)
 {
     for (int a = 0; a < 3; ++a) s->hs.goal.xyz[a] = s->goal_xyz[a];
+    if (closed_form(s)) {
+        // what the closed form needs of the goal (device_types.h SmplxHeurDev); there is no BFS run to tag
+        SmplxHeurDev& H = s->hs.heur;
+        H.joint_goal = s->hs.goal.type == SMPLX_GOAL_JOINT ? 1 : 0;
+        for (int a = 0; a < 3; ++a) H.xyz[a] = s->goal_xyz[a];
+        for (int k = 0; k < 9; ++k) H.rot[k] = s->goal_rot[k];
+        for (int v = 0; v < SMPLX_MAX_VARS; ++v) H.angles[v] = H.joint_goal && v < s->N ? s->hs.goal.angles[v] : 0.0;
+        return upload_space(s);
+    }
     // the tag of this goal's BFS run (device_types.h SmplxBfsDev): 1..7, a reset of the records when they wrap
     if (s->hs.bfs.tag_mask != 0) {
         s->bfs.reset_due = s->bfs.tag == 7;
@@ -911,15 +966,17 @@ static void end_goal(smplx_space* s)
     s->att.epoch_goal = s->att.epoch;
     // a new goal starts a new query: the state table restarts (ids are per query)
     reset_lattice(s);
-    // heuristic of the goal id = BFS cost at the goal pose's cell (manip_lattice.cpp:1176-1190)
+    // heuristic of the goal id = BFS cost at the goal pose's cell (manip_lattice.cpp:1176-1190); the closed forms give the
+    // goal id 0 outright (euclid_dist_heuristic.cpp:120-122, joint_dist_heuristic.cpp:72-74)
     int c[3];
-    s->lat.h_of_id[0] = bfs_goal_cell(s, s->goal_xyz, c) ? 0 : 32767;   // the seeded cell has distance 0 (bfs3d.cpp:178)
+    s->lat.h_of_id[0] = closed_form(s) || bfs_goal_cell(s, s->goal_xyz, c) ? 0 : 32767;   // the seeded cell has distance 0 (bfs3d.cpp:178)
 }
 
 static int finish_goal(smplx_space* s)
 {
     if (int e = begin_goal(s)) return e;
-    if (int e = run_bfs(s, s->goal_xyz)) return e;
+    if (!closed_form(s))
+        if (int e = run_bfs(s, s->goal_xyz)) return e;
     end_goal(s);
     return SMPLX_OK;
 }
@@ -938,6 +995,8 @@ static void xyz_goal_record(smplx_space* s, const double xyz[3], const double to
     SmplxGoalDev& G = s->hs.goal;
     G.type = SMPLX_GOAL_XYZ;
     for (int a = 0; a < 3; ++a) { s->goal_xyz[a] = xyz[a]; G.xyz_tol[a] = tol[a]; }
+    // the Euclidean heuristic's goal rotation: the identity, what the reference makes of the pose {x, y, z, 0, 0, 0}
+    for (int k = 0; k < 9; ++k) s->goal_rot[k] = k % 4 == 0 ? 1.0 : 0.0;
 }
 
 // the bound of the device's orientation test (device_types.h SmplxGoalDev::rpy_c4): theta < tol, theta in [0, pi], is
@@ -969,6 +1028,7 @@ static void pose_goal_record(smplx_space* s, const double xyz[3], const double r
     SmplxGoalDev& G = s->hs.goal;
     G.type = SMPLX_GOAL_XYZ_RPY;
     rpy_matrix(rpy, G.rot);
+    for (int k = 0; k < 9; ++k) s->goal_rot[k] = G.rot[k];
     G.rpy_c4 = rpy_bound(rpy_tol);
     for (int a = 0; a < 3; ++a) s->goal_rpy[a] = rpy[a];
     s->goal_rpy_tol = rpy_tol;
@@ -984,6 +1044,17 @@ static bool sane_pose_goals(const double* xyz, const double* rpy, const double* 
     return true;
 }
 
+// the Euclidean heuristic's goal rotation under a joint goal: the planning link's at the goal angles
+// (planner_interface.cpp:1236-1238), by the FK that gave the goal position
+static int joint_goal_rotation(smplx_space* s, const double* angles)
+{
+    if (s->params.heuristic != SMPLX_H_EUCLID) return SMPLX_OK;
+    double T[12];
+    if (int e = smplx_planning_pose_batch(s, angles, 1, T)) return e;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) s->goal_rot[3 * r + c] = T[4 * r + c];
+    return SMPLX_OK;
+}
+
 int smplx_set_goal_joint(smplx_space* s, const double* angles, const double* tolerances)
 {
     if (!s || !angles || !tolerances) return set_error(SMPLX_E_ARG, "null argument");
@@ -992,6 +1063,7 @@ int smplx_set_goal_joint(smplx_space* s, const double* angles, const double* tol
     // goal pose = planning-link FK of the goal angles (planner_interface.cpp:1232-1235)
     int32_t h;
     if (int e = run_heuristic(s, angles, 1, &h, s->goal_xyz)) return e;
+    if (int e = joint_goal_rotation(s, angles)) return e;
     return finish_goal(s);
 }
 
@@ -1026,10 +1098,13 @@ static int check_goal_spaces(smplx_space* const* spaces, int nq)
 // ... and on the spaces: one device, the same bricks per axis (the goals share the launches of run_bfs_multi)
 static int check_goal_spaces_match(smplx_space* const* spaces, int nq)
 {
-    for (int q = 1; q < nq; ++q) {
+    const smplx_space* lead = nullptr;       // the first space that takes part in the shared BFS: a closed-form space does not
+    for (int q = 0; q < nq; ++q) {
         if (spaces[q]->device != spaces[0]->device) return set_error(SMPLX_E_ARG, "the spaces live on different devices");
+        if (closed_form(spaces[q])) continue;
+        if (!lead) lead = spaces[q];
         for (int a = 0; a < 3; ++a)
-            if (spaces[q]->bfs.bricks[a] != spaces[0]->bfs.bricks[a]) return set_error(SMPLX_E_ARG, "the spaces' grids differ in bricks per axis");
+            if (spaces[q]->bfs.bricks[a] != lead->bfs.bricks[a]) return set_error(SMPLX_E_ARG, "the spaces' grids differ in bricks per axis");
     }
     return SMPLX_OK;
 }
@@ -1039,7 +1114,10 @@ static int finish_goals_multi(smplx_space* const* spaces, int nq)
 {
     int e = SMPLX_OK;
     for (int q = 0; q < nq && e == SMPLX_OK; ++q) e = begin_goal(spaces[q]);
-    if (e == SMPLX_OK) e = run_bfs_multi(spaces, nq);
+    // the shared sweep is of the spaces that plan with the BFS; a closed-form space has its goal from begin_goal alone
+    std::vector<smplx_space*> with_bfs;
+    for (int q = 0; q < nq; ++q) if (!closed_form(spaces[q])) with_bfs.push_back(spaces[q]);
+    if (e == SMPLX_OK && !with_bfs.empty()) e = run_bfs_multi(with_bfs.data(), (int)with_bfs.size());
     if (e != SMPLX_OK) {
         for (int q = 0; q < nq; ++q) spaces[q]->goal_set = false;   // some grids are half written: no space keeps a goal
         return e;
@@ -1070,6 +1148,7 @@ int smplx_set_goals_joint_multi(smplx_space** spaces, int nq, const double* angl
     } else {
         for (int q = 0; q < nq && e == SMPLX_OK; ++q) e = run_heuristic(spaces[q], angles + (size_t)q * N, 1, nullptr, spaces[q]->goal_xyz);
     }
+    for (int q = 0; q < nq && e == SMPLX_OK; ++q) e = joint_goal_rotation(spaces[q], angles + (size_t)q * N);
     if (e != SMPLX_OK) {
         for (int q = 0; q < nq; ++q) spaces[q]->goal_set = false;
         return e;
@@ -1164,12 +1243,15 @@ int smplx_heuristic_batch(smplx_space* s, const double* q, int n, int32_t* h, do
     return run_heuristic(s, q, n, h, xyz);
 }
 
+static const char* const kNoBfs = "the space plans with a closed-form heuristic (smplx_params.heuristic): it has no BFS grid";
+
 int64_t smplx_bfs_size(const smplx_space* s) { return s ? s->bfs.total : 0; }
 int smplx_bfs_levels(const smplx_space* s) { return s ? s->bfs.levels : 0; }
 
 int smplx_bfs_copy(smplx_space* s, int32_t* out)
 {
     if (!s || !out) return set_error(SMPLX_E_ARG, "null argument");
+    if (closed_form(s)) return set_error(SMPLX_E_STATE, kNoBfs);
     // the device keeps brick-major records (device_types.h SmplxBfsDev); what goes out is the reference's padded array
     int32_t* tmp = nullptr;
     HIP_TRY(hipMalloc((void**)&tmp, sizeof(int32_t) * s->bfs.total));
@@ -1185,6 +1267,7 @@ int smplx_bfs_copy(smplx_space* s, int32_t* out)
 int smplx_bfs_metric_goal_distance(smplx_space* s, const double* xyz, int n, double* out)
 {
     if (!s || !xyz || !out || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (closed_form(s)) return set_error(SMPLX_E_STATE, kNoBfs);
     if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
     if (n == 0) return SMPLX_OK;
     if (!sane_values(xyz, (size_t)n * 3)) return set_error(SMPLX_E_ARG, "positions must be finite");
@@ -1203,6 +1286,7 @@ int smplx_bfs_metric_goal_distance(smplx_space* s, const double* xyz, int n, dou
 int smplx_bfs_metric_start_distance(smplx_space* s, const double* xyz, int n, double* out)
 {
     if (!s || !xyz || !out || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (closed_form(s)) return set_error(SMPLX_E_STATE, kNoBfs);
     if (s->lat.start_id < 0) return set_error(SMPLX_E_STATE, "start not set");
     // bfs_heuristic.cpp:103-127: Manhattan distance in cells between the start's planning-link cell and the point's
     const smplx_grid* g = s->grid;
@@ -1216,6 +1300,52 @@ int smplx_bfs_metric_start_distance(smplx_space* s, const double* xyz, int n, do
         cell(xyz + 3 * (size_t)i, c);
         out[i] = g->res * (double)(std::abs(sc[0] - c[0]) + std::abs(sc[1] - c[1]) + std::abs(sc[2] - c[2]));
     }
+    return SMPLX_OK;
+}
+
+int smplx_metric_goal_distance(smplx_space* s, const double* xyz, int n, double* out)
+{
+    if (!s || !xyz || !out || n < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (!closed_form(s)) return smplx_bfs_metric_goal_distance(s, xyz, n, out);
+    if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
+    if (!sane_values(xyz, (size_t)n * 3)) return set_error(SMPLX_E_ARG, "positions must be finite");
+    // euclid_dist_heuristic.cpp:98-102 / joint_dist_heuristic.cpp:52-55: host arithmetic, the kernels' own functions
+    for (int i = 0; i < n; ++i)
+        out[i] = s->params.heuristic == SMPLX_H_EUCLID ? smplx_point_dist(xyz + 3 * (size_t)i, s->goal_xyz) : 0.0;
+    return SMPLX_OK;
+}
+
+int smplx_set_euclid_weights(smplx_space* s, const double w[4])
+{
+    if (!s || !w) return set_error(SMPLX_E_ARG, "null argument");
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(w[k]) || w[k] < 0.0) return set_error(SMPLX_E_ARG, "weights must be finite and not negative");
+    if (s->params.heuristic != SMPLX_H_EUCLID) return set_error(SMPLX_E_STATE, "the space's heuristic is not SMPLX_H_EUCLID");
+    for (int k = 0; k < 4; ++k) s->hs.heur.w[k] = w[k];
+    // every h recorded so far used the old weights: the space has no goal until it is set again (which uploads the record
+    // and restarts the lattice)
+    s->goal_set = false;
+    return SMPLX_OK;
+}
+
+int smplx_pose_distance(const double Ta[12], const double Tb[12], const double w[4], double* dist)
+{
+    if (!Ta || !Tb || !w || !dist) return set_error(SMPLX_E_ARG, "null argument");
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(Ta[k]) || !std::isfinite(Tb[k])) return set_error(SMPLX_E_ARG, "transforms must be finite");
+    for (int k = 0; k < 4; ++k) if (!std::isfinite(w[k]) || w[k] < 0.0) return set_error(SMPLX_E_ARG, "weights must be finite and not negative");
+    double pa[3], pb[3], Ra[9], Rb[9];
+    for (int r = 0; r < 3; ++r) {
+        pa[r] = Ta[4 * r + 3]; pb[r] = Tb[4 * r + 3];
+        for (int c = 0; c < 3; ++c) { Ra[3 * r + c] = Ta[4 * r + c]; Rb[3 * r + c] = Tb[4 * r + c]; }
+    }
+    *dist = smplx_pose_dist(pa, Ra, pb, Rb, w);
+    return SMPLX_OK;
+}
+
+int smplx_joint_distance(const double* a, const double* b, int n, double* dist)
+{
+    if (!a || !b || !dist || n < 0 || n > SMPLX_MAX_VARS) return set_error(SMPLX_E_ARG, "bad argument (n: 0 to 16)");
+    for (int k = 0; k < n; ++k) if (!std::isfinite(a[k]) || !std::isfinite(b[k])) return set_error(SMPLX_E_ARG, "joint values must be finite");
+    *dist = smplx_joint_dist(a, b, n);
     return SMPLX_OK;
 }
 

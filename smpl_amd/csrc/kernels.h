@@ -65,7 +65,7 @@ static inline bool smplx_step_claim_fits(long long blocks)
     X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
     X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block) \
     X(STATE_CLEARANCE, k_state_clearance) X(EDGE_CLEARANCE, k_edge_clearance) X(LAZY_SUCCS, k_lazy_succs) \
-    X(TRUE_COST, k_true_cost)
+    X(TRUE_COST, k_true_cost) X(HEURISTIC_CLOSED, k_heuristic_closed)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
@@ -119,6 +119,7 @@ __global__ void k_edge_valid(const SmplxSpaceDev* S, const double* Aq, const dou
                              int* out_lookups, int* out_waypoints);
 __global__ void k_state_valid(const SmplxSpaceDev* S, const double* Q, int n, unsigned char* out, int* out_lookups);
 __global__ void k_heuristic(const SmplxSpaceDev* S, const double* Q, int n, int* out_h, double* out_xyz);
+__global__ void k_heuristic_closed(const SmplxSpaceDev* S, const double* Q, int n, int* out_h, double* out_xyz);
 __global__ void k_planning_pose(const SmplxSpaceDev* S, const double* Q, int n, double* out_T);
 __global__ void k_sphere_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);
 __global__ void k_attached_positions(const SmplxSpaceDev* S, const double* Q, int n, double* out);

@@ -7,6 +7,7 @@
 //   sphere_checks.h     voxel lookup, sphere tree vs grid, link pairs; the per-robot (SMPLX_CONST_MODEL) chain
 //   attached_bodies.h   bodies attached to links, checked behind the robot's own trees and pairs
 //   config_checks.h     config_valid (isStateValid), edge_waypoint_count, edge_valid (isStateToStateValid)
+//   heuristics.h        the two closed-form heuristics' arithmetic, host and device (det_math.h)
 //   lattice_steps.h     planning-link FK, goal distance, heuristic, limits, discretisation, the state table with
 //                       k_table_insert, successor_values, successor_goal_h: one definition each for every kernel below
 //   step_kernels.h      a frontier step.  Default: the waypoint-parallel pipeline k_pipe_setup -> k_pipe_configs ->
@@ -16,7 +17,7 @@
 //   step_block.h        k_step_block: the same step in ONE launch for a batch whose blocks are resident in one round;
 //                       each block owns 128 edges and keeps everything between its phases in LDS
 //   small_batch.h       k_small_batch: one block per state, and the lane functions k_search is built from
-//   query_kernels.h     k_edge_valid, k_state_valid, k_heuristic, k_planning_pose, k_sphere_positions,
+//   query_kernels.h     k_edge_valid, k_state_valid, k_heuristic, k_heuristic_closed, k_planning_pose, k_sphere_positions,
 //                       k_attached_positions, k_bfs_metric: batch queries of the C-ABI
 //   clearance.h         distance to collision of a configuration and of an edge: leaf spheres against the grid, branch
 //                       and bound over the checked pairs and the attached bodies

@@ -1,6 +1,7 @@
 // smpl_amd/csrc/lattice_steps.h -- the steps of ManipLattice::GetSuccs that are not collision checks, one definition
 // each for every expansion kernel.
-// Owns: planning_fk, world_to_cell, metric_goal_distance, bfs_cost_to_goal, check_joint_limits, var_to_coord;
+// Owns: planning_fk, world_to_cell, metric_goal_distance, bfs_cost_to_goal, check_joint_limits, var_to_coord; the dispatch
+// on the space's heuristic kind (closed_form_of, closed_form_goal_distance, closed_form_h; the arithmetic is heuristics.h);
 // the device copy of the state table (table_probe_issue / table_probe_resolve, table_lookup, the insert functions and
 // k_table_insert); mprim_gate / mprim_active, prim_has_action, successor_values, successor_goal_h.
 // Restates: kdl_robot_model.cpp:173-235, 400-423; bfs_heuristic.cpp:129-138, 355-366;
@@ -8,6 +9,7 @@
 #pragma once
 
 #include "bfs_record.h"
+#include "heuristics.h"
 #include "model_lds.h"
 #include "sphere_checks.h"   // const_planning_chain
 
@@ -74,14 +76,54 @@ __device__ __forceinline__ void world_to_cell(const SmplxGridDev& g, const doubl
     c[2] = (int)(g.inv_res * (p[2] - g.origin_minus_res[2]) + 0.5) - 1;
 }
 
+// The heuristic kind of a space (device_types.h SmplxBfsDev, SmplxHeurDev).  closed_form_of is null for a space that plans
+// with the BFS: the kernels test that one value, the same for every state of a space, and take the BFS code below
+// unchanged.  Otherwise it is the space's heuristic record, which says which closed form (heuristics.h) stands in for the
+// BFS's two functions:
+//   getMetricGoalDistance, the gate of the primitives -- Euclidean: the distance of the planning link to the goal position;
+//     joint distance: 0.0, so every state counts as "at the goal" (joint_dist_heuristic.cpp:52-55; kept, not repaired)
+//   GetGoalHeuristic -- (int)(1000 * distance) of the state's pose, or of its joint values, to the goal's
+// The generic kernels test at run time, per space.  A per-robot build knows when it compiles (specialize.cpp: a space of a
+// closed-form kind gets a build of its own, CM_CLOSED_FORM): the build of the BFS spaces holds no dispatch at all and is,
+// instruction for instruction, what it was without the closed forms (any test in front of or behind the chain cost the
+// per-robot k_pipe_setup its fifth wave: profiles/heuristic_kinds_ab.txt); the other build holds no BFS arm.  Hence
+// spaces that share a launch (smplx_plan_multi, multi_query.h same_scene_and_robot) are all BFS or all closed-form;
+// the two closed forms may mix, their kind is read from the record.
+__device__ __forceinline__ const SMPLX_GLOBAL_AS SmplxHeurDev* closed_form_of(const SmplxBfsDev& bfs)
+{
+#if defined(SMPLX_CONST_MODEL) && defined(CM_CLOSED_FORM)
+    return as_global(bfs.heur);
+#elif defined(SMPLX_CONST_MODEL)
+    return nullptr;
+#else
+    return bfs.dim_x == 0 ? as_global(bfs.heur) : nullptr;
+#endif
+}
+__device__ __forceinline__ bool closed_form_needs_fk(const SMPLX_GLOBAL_AS SmplxHeurDev* H) { return H->kind == SMPLX_HEUR_EUCLID; }
+__device__ __forceinline__ double closed_form_goal_distance(const SMPLX_GLOBAL_AS SmplxHeurDev* H, const double p[3])
+{
+    return smplx_point_dist(p, (const double*)H->xyz);
+}
+__device__ __forceinline__ int closed_form_h(const ModelLds* __restrict__ M, const SMPLX_GLOBAL_AS SmplxHeurDev* H, const double p[3],
+                                             const double R[9], const double* __restrict__ q)
+{
+    if (H->kind == SMPLX_HEUR_EUCLID)
+        return smplx_fixed_h(smplx_pose_dist(p, R, (const double*)H->xyz, (const double*)H->rot, (const double*)H->w));
+    if (!H->joint_goal) return 0;
+    return smplx_fixed_h(smplx_joint_dist(q, (const double*)H->angles, MV_NVARS(M)));
+}
+
 // BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) of the state with joint values q: the gate of its
 // primitives.  The one definition for every path; goal_distance_of_h (search_kernel.h) recovers the same value from a
 // state's heuristic and must keep the same distance for an unreachable cell.
 __device__ __forceinline__ double metric_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
                                                        const double* __restrict__ q)
 {
+    const SMPLX_GLOBAL_AS SmplxHeurDev* H = closed_form_of(bfs);
+    if (H && !closed_form_needs_fk(H)) return 0.0;
     double p[3];
     planning_fk(M, q, p);
+    if (H) return closed_form_goal_distance(H, p);
     int c[3];
     world_to_cell(grid, p, c);
     return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
@@ -93,8 +135,11 @@ __device__ __forceinline__ double metric_goal_distance_sc(const ModelLds* __rest
                                                           const double* __restrict__ q, const double* __restrict__ sn,
                                                           const double* __restrict__ cs)
 {
+    const SMPLX_GLOBAL_AS SmplxHeurDev* H = closed_form_of(bfs);
+    if (H && !closed_form_needs_fk(H)) return 0.0;
     double p[3];
     planning_fk_sc(M, q, sn, cs, p, nullptr);
+    if (H) return closed_form_goal_distance(H, p);
     int c[3];
     world_to_cell(grid, p, c);
     return !bfs_in_bounds(bfs, c) ? (double)0x7FFFFFFF * grid.res : (double)bfs_dist(bfs, c) * grid.res;
@@ -390,7 +435,8 @@ __device__ __forceinline__ bool successor_values(const ModelLds* __restrict__ M,
 }
 
 // Goal test and heuristic of the successor with joint values sq and coordinates sc: planning-link FK, isGoal, BFS cost of
-// its cell.  Returns h.  The one definition for every path; discretisation and the table probe stay with the callers.
+// its cell -- or, in a space of a closed-form kind, closed_form_h of the same pose.  Returns h.  The one definition for every path; discretisation and the table probe stay
+// with the callers.
 // SC (per-robot build): sn, cs = the sines and cosines the planning-link chain would evaluate (planning_fk_sc).
 template <bool SC = false>
 __device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, const SmplxGoalDev& G, const SmplxBfsDev& bfs,
@@ -421,6 +467,7 @@ __device__ __forceinline__ int successor_goal_h(const ModelLds* __restrict__ M, 
             is_goal = t > G.rpy_c4;
         }
     }
+    if (const SMPLX_GLOBAL_AS SmplxHeurDev* H = closed_form_of(bfs)) return closed_form_h(M, H, p, R, sq);
     int c[3];
     world_to_cell(grid, p, c);
     return bfs_cost_to_goal(bfs, c);

@@ -310,8 +310,10 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
 // two spaces that can share launches: the same scene (grid handle), model image, primitives and expansion mode
 bool same_scene_and_robot(const smplx_space* a, const smplx_space* b)
 {
+    // (BFS or closed-form: a constant of the per-robot build, lattice_steps.h closed_form_of; Euclidean and joint distance may share)
     return a->grid == b->grid && a->blob_bytes == b->blob_bytes && std::memcmp(a->hs.model_blob, b->hs.model_blob, a->blob_bytes) == 0 &&
-           std::memcmp(&a->hs.actions, &b->hs.actions, sizeof(SmplxActionsDev)) == 0 && a->step.fused_mode == b->step.fused_mode;
+           std::memcmp(&a->hs.actions, &b->hs.actions, sizeof(SmplxActionsDev)) == 0 && a->step.fused_mode == b->step.fused_mode &&
+           (a->params.heuristic == SMPLX_H_BFS) == (b->params.heuristic == SMPLX_H_BFS);
 }
 
 int read_counters(smplx_space* s, size_t cw, unsigned long long counters[4])

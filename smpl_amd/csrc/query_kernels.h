@@ -1,8 +1,8 @@
 // smpl_amd/csrc/query_kernels.h -- the batch queries of the C-ABI, one thread per row.
 // Owns: k_edge_valid, k_state_valid (CollisionChecker::isStateToStateValid, isStateValid), k_heuristic
-// (BfsHeuristic::GetGoalHeuristic), k_planning_pose (computePlanningLinkFK), k_bfs_metric
-// (BfsHeuristic::getMetricGoalDistance, bfs_heuristic.cpp:129-138), k_sphere_positions and k_attached_positions
-// (debug / parity).
+// (BfsHeuristic::GetGoalHeuristic), k_heuristic_closed (GetGoalHeuristic of the two closed-form kinds), k_planning_pose
+// (computePlanningLinkFK), k_bfs_metric (BfsHeuristic::getMetricGoalDistance, bfs_heuristic.cpp:129-138),
+// k_sphere_positions and k_attached_positions (debug / parity).
 #pragma once
 
 #include "config_checks.h"
@@ -69,6 +69,27 @@ k_heuristic(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, i
     int c[3];
     world_to_cell(S->grid, p, c);
     out_h[i] = bfs_cost_to_goal(S->bfs, c);
+    if (out_xyz) { out_xyz[3 * i] = p[0]; out_xyz[3 * i + 1] = p[1]; out_xyz[3 * i + 2] = p[2]; }
+}
+
+// k_heuristic for a space of a closed-form kind (lattice_steps.h closed_form_of; the host picks the kernel, engine.hip
+// run_heuristic): the same chain with its rotation, the h every expansion kernel gives the state.  A kernel of its own
+// because the rotation and the goal record cost the per-robot k_heuristic 28 VGPRs and three occupancy steps when the
+// two shared one body; k_heuristic is the text it was.
+extern "C" __global__ void __launch_bounds__(BLOCK)
+k_heuristic_closed(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, int n, int* __restrict__ out_h,
+                   double* __restrict__ out_xyz)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const ModelLds Mv = setup_model_only(S, smem);
+    const ModelLds* M = &Mv;
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const SMPLX_GLOBAL_AS SmplxHeurDev* H = closed_form_of(S->bfs);
+    const double* q = Q + (size_t)i * MV_NVARS(M);
+    double p[3], R[9];
+    planning_fk(M, q, p, R);
+    out_h[i] = H ? closed_form_h(M, H, p, R, q) : 0;      // (never launched for a BFS space)
     if (out_xyz) { out_xyz[3 * i] = p[0]; out_xyz[3 * i + 1] = p[1]; out_xyz[3 * i + 2] = p[2]; }
 }
 

@@ -613,7 +613,9 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
         // the goal distance of a state follows from its heuristic when h = cost_per_cell * BFS distance is invertible
         // (bfs_heuristic.cpp:129-138 / 355-366: both read the BFS cell of the same planning-link position)
         const int cpc = bfs.cost_per_cell;
-        const bool gd_from_h = cpc > 0 && (32767 % cpc) != 0;
+        // -- of the BFS kind only: a closed-form h says nothing of the gate's distance (lattice_steps.h closed_form_of), so
+        // such a space takes the path beside it, metric_goal_distance: the FK (Euclidean) or the constant 0 (joint distance)
+        const bool gd_from_h = closed_form_of(bfs) == nullptr && cpc > 0 && (32767 % cpc) != 0;
         // The next expansion, started early.  An evaluation round (barrier A .. barrier B) keeps the config waves busy for
         // ~14 us while this wave only fills in the bookkeeping, and committing and relaxing a step (~7 us) plus the next pop
         // (~4 us) kept THEM idle.  GetSuccs is a pure function of a state's joint values, so as soon as the verdicts of a

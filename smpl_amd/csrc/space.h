@@ -233,6 +233,7 @@ struct smplx_space {
     double goal_xyz[3] = {0, 0, 0};
     double goal_rpy[3] = {0, 0, 0};   // of a pose goal (SMPLX_GOAL_XYZ_RPY), as the caller gave them
     double goal_rpy_tol = 0;
+    double goal_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // the goal rotation the Euclidean heuristic measures against (SmplxHeurDev::rot)
     double start_xyz[3] = {0, 0, 0};   // planning-link position of the start state (getMetricStartDistance)
     int status = SMPLX_OK;            // sticky: first error of a call that has no way to report one (smplx_space_status)
     std::string status_msg;

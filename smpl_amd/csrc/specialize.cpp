@@ -144,10 +144,12 @@ void generic_kernels(KernelSet& ks)
     ks.specialized = false;
 }
 
-bool specialized_kernels(const SmplxModelDev& model, KernelSet& ks, std::string& why)
+bool specialized_kernels(const SmplxModelDev& model, bool closed_form, KernelSet& ks, std::string& why)
 {
     generic_kernels(ks);
-    const std::string header = model_const_header(model);
+    // the heuristic kind is a constant of the build, like the robot (lattice_steps.h closed_form_of): the header is part of
+    // the cache key, so the two builds of a robot are two code objects
+    const std::string header = model_const_header(model) + (closed_form ? kClosedFormDefine : "");
     uint64_t h = 0xCBF29CE484222325ull;
     h = fnv1a(h, header);
     h = fnv1a(h, kRootSource);

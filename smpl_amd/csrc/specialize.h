@@ -36,8 +36,11 @@ struct KernelSet {
 void generic_kernels(KernelSet& ks);
 
 // fills ks with the per-robot kernels for `model` on the current device; on failure returns false with the reason
-// in `why` and leaves ks generic.  Thread-safe.
-bool specialized_kernels(const SmplxModelDev& model, KernelSet& ks, std::string& why);
+// in `why` and leaves ks generic.  Thread-safe.  closed_form: the build for spaces that plan with a closed-form
+// heuristic instead of the BFS (lattice_steps.h closed_form_of), a code object of its own.
+// what the closed-form build's constants header holds behind the model's (the one place that spells it)
+static const char* const kClosedFormDefine = "#define CM_CLOSED_FORM 1\n";
+bool specialized_kernels(const SmplxModelDev& model, bool closed_form, KernelSet& ks, std::string& why);
 
 // Launch with the kernel's own parameter types: every argument is converted to the declared type first, then
 // passed by address (hipModuleLaunchKernel / hipLaunchKernel take untyped argument arrays).

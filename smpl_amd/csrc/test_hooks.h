@@ -63,6 +63,18 @@ int smplx_test_set_search_capacity(smplx_space* s, int states);
  * as it does for robots whose block would exceed 512 threads with one); 1 restores the default. */
 int smplx_test_set_search_helper(smplx_space* s, int on);
 
+/* The host build of smplx_acos (det_math.h) at n arguments: what the accuracy statement in its comment is measured on.
+ * Needs no GPU. */
+int smplx_test_acos(const double* x, int n, double* out);
+
+/* The goal rotation a SMPLX_H_EUCLID space measures against (row-major 3x3), as the engine holds it: the identity under an
+ * xyz goal, the rotation it built from a pose goal's rpy, its own FK of a joint goal's angles.  SMPLX_E_STATE without a goal. */
+int smplx_test_goal_rotation(const smplx_space* s, double R[9]);
+
+/* smplx_model_const_header for either flavour of the per-robot build: closed_form = 1 gives the header a closed-form space's
+ * build is compiled against (specialize.h kClosedFormDefine appended).  Returns the size needed, including the NUL. */
+int smplx_test_const_header(const smplx_model* m, int closed_form, char* out, int cap);
+
 #ifdef __cplusplus
 }
 #endif
