@@ -1041,7 +1041,7 @@ class Space:
         return int(lib().smplx_test_table_slots(self.h))
 
     def set_search_capacity(self, states):
-        """Test hook (csrc/test_hooks.h): first capacity of the device search's buffers."""
+        """Test hook (csrc/test_hooks.h): first capacity of the device search's buffers; its path buffer then starts at 64 ids."""
         lib().smplx_test_set_search_capacity.argtypes = [C.c_void_p, C.c_int]
         _chk(lib().smplx_test_set_search_capacity(self.h, int(states)))
 

@@ -303,7 +303,7 @@ int search_begin(smplx_space* s, const smplx_time_params* p, bool resume, double
     c.log = (int)(bound >= 0 ? std::min<long long>(bound + 1, 1LL << 26) : 1LL << 17);
     if (D.test_capacity > 0) c.log = std::min(c.log, std::max(64, D.test_capacity / 8));
     c.succ = (int)std::min<long long>((long long)c.log * std::min(s->M, 24), 1LL << 28);
-    c.path = 1 << 16;
+    c.path = D.test_capacity > 0 ? 64 : 1 << 16;
     if (int e = search_reserve(s, c)) return e;
     if (int e = search_push_lattice(s)) return e;
     if (int e = search_fill_table(s, have - (int)(s->dt.pending_ins.size() / ((size_t)s->N + 2)), have)) return e;

@@ -56,7 +56,9 @@ long long smplx_test_table_slots(const smplx_space* s);
 /* First capacity (states) of the device-resident search's buffers, so that a test can make a search outgrow them
  * (SMPLX_SS_GROW: the host enlarges and launches again); 0 restores the default sizing.  A state table that the search
  * allocates while the hook is set starts at the smallest size that holds this capacity half full (instead of 2^16 slots),
- * so it is outgrown and filled again along with the buffers. */
+ * so it is outgrown and filled again along with the buffers.  The path buffer of a search that starts while the hook is set
+ * holds 64 ids at first (instead of 2^16): a longer solution does not fit, and the host doubles the buffer and launches
+ * again for the path alone (grow_what = 3). */
 int smplx_test_set_search_capacity(smplx_space* s, int states);
 
 /* on = 0: the device-resident search runs WITHOUT its helper wave (the search wave does the successors' bookkeeping inline,

@@ -87,19 +87,29 @@ class AraStarLoop:
             s.f = INF; s.eg = INF; s.closed = 0; s.call = self.call; s.bp = -1; s.incons = False
         return s
 
-    def replan(self, start, goal, eps0, eps_final, eps_delta, max_init=0, max_rep=0):
-        """dict(solved, cost, expansions, satisfied_eps, path, log): a bounded search when max_init > 0 (expansion budgets
-        of the first and of the later iterations, TimeParameters::EXPANSIONS)"""
-        self.heap = [0]; self.incons = []; self.log = []
-        self.call += 1
-        self.eps = eps0
-        self._reinit(start); self._reinit(goal)
-        s = self.n[start]
-        s.g = 0
-        s.f = self._key(s)
-        self._push(start)
-        iteration, num, satisfied = 1, 0, math.inf
+    def replan(self, start, goal, eps0, eps_final, eps_delta, max_init=0, max_rep=0, allow_partial=False, resume=False):
+        """dict(solved, cost, expansions, satisfied_eps, path, log, result, call_expansions): a bounded search when
+        max_init > 0 (expansion budgets of the first and of the later iterations, TimeParameters::EXPANSIONS).  result is the
+        ReplanResultCode the call's last improvePath ended with (0 SUCCESS, 4 TIMED_OUT, 5 EXHAUSTED_OPEN_LIST; 0 when the
+        call had nothing to improve).  allow_partial: a search without a solution returns the bp chain of OPEN's minimum,
+        where OPEN has one (arastar.cpp:204-209), with solved = 1 and satisfied_eps = inf.  resume: the call continues the
+        search of the call before it (the same start: arastar.cpp:128 is not taken) -- OPEN, INCONS, epsilons and log stay,
+        the call's own expansion count starts at 0 and `expansions` goes on counting"""
+        if not resume:
+            for i in self.heap[1:]:              # intrusive_heap.hpp clear(): what an earlier call left in OPEN is out of it
+                self.n[i].heap_index = 0
+            self.heap = [0]; self.incons = []; self.log = []
+            self.call += 1
+            self.eps = eps0
+            self._reinit(start); self._reinit(goal)
+            s = self.n[start]
+            s.g = 0
+            s.f = self._key(s)
+            self._push(start)
+            self.iteration, self.satisfied, self.total = 1, math.inf, 0
+        iteration, num, satisfied = self.iteration, 0, self.satisfied
         fin = max(eps_final, 1.0)
+        err = 0
         while satisfied > fin:
             if self.eps == satisfied:
                 iteration += 1
@@ -116,13 +126,18 @@ class AraStarLoop:
             if err:
                 break
             satisfied = self.eps
-        out = dict(solved=int(satisfied != math.inf), cost=0, expansions=num, satisfied_eps=satisfied, path=[], log=list(self.log))
-        if out["solved"]:
-            i = goal
+        self.iteration, self.satisfied = iteration, satisfied
+        self.total += num
+        out = dict(solved=int(satisfied != math.inf), cost=0, expansions=self.total, satisfied_eps=satisfied, path=[],
+                   log=list(self.log), result=err, call_expansions=num)
+        last = goal if out["solved"] else self.heap[1] if allow_partial and len(self.heap) > 1 else -1
+        if last >= 0:
+            i = last
             while i >= 0:
                 out["path"].insert(0, i)
                 i = self.n[i].bp
-            out["cost"] = self.n[goal].g
+            out["cost"] = self.n[last].g
+            out["solved"] = 1
         return out
 
     def _improve(self, goal, iteration, elapsed, satisfied, max_init, max_rep):

@@ -1,7 +1,8 @@
 // tests/cpp/arastar_facade_driver.cpp -- drives smpl_amd::GpuARAStar (include/smpl_amd/plugin.hpp), the mirror of smpl's
 // ARAStar over the engine's own search, the way an anytime caller does: expansion-bounded chunks that continue one search,
 // replan(0.0) with and without partial solutions, and force_planning_from_scratch + replan(allowed_time) to completion.
-// Prints one line per call; tests/test_gpu_arastar_facade.py compares them with the C-ABI and the oracle.
+// A query file with a second goal selects another run instead: an unbounded replan for a goal that no state satisfies, then
+// one for the second goal.  Prints one line per call; tests/test_gpu_arastar_facade.py compares them with the C-ABI and the oracle.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -52,6 +53,39 @@ int main(int argc, char** argv)
     auto print_path = [](const std::vector<int>& p) { for (int id : p) printf(" %d", id); printf("\n"); };
     std::vector<int> path;
     int cost = 0;
+
+    // A query file that goes on behind `chunk` with a 1 and a second goal: the first goal is one that no state satisfies.
+    // An unbounded replan for it ends with an empty OPEN: it returns 0 and touches neither the solution nor the cost; the
+    // same planner then plans to the second goal on the same space.
+    int unreachable = 0;
+    if (q >> unreachable && unreachable == 1) {
+        RobotState second(nv);
+        for (double& v : second) q >> v;
+        if (!q) return 3;
+        GpuARAStar e(&ctx);
+        e.set_initialsolution_eps(5.0);
+        e.setTargetEpsilon(1.0);
+        e.setDeltaEpsilon(1.0);
+        GpuARAStar::TimeParameters tp = e.timeParameters();
+        tp.bounded = false;
+        tp.type = GpuARAStar::TimeParameters::EXPANSIONS;
+        path.assign(2, -7);
+        cost = -3;
+        int ret = e.replan(tp, &path, &cost);
+        const smplx_replan_stats st = e.lastCallStats();
+        printf("exhausted %d %d %d %d %d %d %d %.17g", ret, st.result, st.call_expansions, e.get_n_expands(), st.s.solved, st.s.path_len, cost,
+               e.get_solution_eps());
+        print_path(path);
+        if (!lattice.setGoalConfiguration(second, tol)) return 4;
+        if (!lattice.setStart(start)) return 5;
+        path.clear();
+        ret = e.replan(tp, &path, &cost);
+        printf("second %d %d %d %d %d %.17g", ret, e.lastCallStats().result, e.lastCallStats().resumed, cost, e.get_n_expands(),
+               e.get_solution_eps());
+        print_path(path);
+        printf("done\n");
+        return 0;
+    }
 
     // 1. set_search_mode(false): every call bounded by `chunk` expansions; the search continues between calls
     GpuARAStar a(&ctx);

@@ -1,7 +1,8 @@
 """smpl_amd::GpuARAStar (include/smpl_amd/plugin.hpp), the mirror of smpl's ARAStar over the engine's own anytime search,
 driven from C++ (tests/cpp/arastar_facade_driver.cpp) and compared line by line with the C-ABI and the oracle: chunks
 bounded by expansions that continue one search, replan(0.0) with and without partial solutions, and
-force_planning_from_scratch + replan(allowed_time) to completion."""
+force_planning_from_scratch + replan(allowed_time) to completion; and a goal no state satisfies, where replan returns 0 with
+an empty OPEN and leaves the caller's solution alone."""
 import os
 import subprocess
 
@@ -56,4 +57,55 @@ def test_gpu_arastar_facade_matches_the_c_abi_and_the_oracle(small_cfg, tmp_path
     timed = next(ln for ln in lines if ln.startswith("timed ")).split()
     assert timed[1:5] == ["1", str(capi.ARA_SUCCESS), str(eo["cost"]), str(eo["expansions"])]
     assert float(timed[5]) == eo["eps"] and " ".join(timed[6:]) == path
+    assert lines[-1] == "done"
+
+
+@pytest.mark.parametrize("side", ["device", "host"])
+def test_gpu_arastar_facade_on_an_exhausted_open_list(tmp_path, side):
+    """GpuARAStar::replan for a goal that no state of the one-joint chain satisfies (width_cases.unreachable_goal): the
+    search pops every reachable state and ends with an empty OPEN, so replan returns 0 (arastar.cpp:204-210) and touches
+    neither the solution vector nor the cost; get_n_expands() is the oracle's count.  The same planner then plans to the
+    reachable goal on the same space.  The result code expected of the engine is the plain loop's (arastar_loop.py)."""
+    import dataclasses
+
+    import numpy as np
+
+    import width_cases as wc
+    from arastar_loop import AraStarLoop
+    from oracle_binding import Oracle
+    from smpl_amd.plugin_tools import build_driver, write_query
+    cfg = wc.width_case(1)
+    bad = wc.unreachable_goal(1)
+    exe = build_driver("arastar_facade_driver", tmp_path)
+    write_query(dataclasses.replace(cfg, goal=bad), tmp_path, [0, 1, *[float(x) for x in cfg.goal]])
+    out = subprocess.run([exe, str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120,
+                         env=dict(os.environ, SMPLX_SEARCH=side))
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    lines = out.stdout.decode().splitlines()
+    print("\n".join(ln[:200] for ln in lines))
+
+    o = Oracle(cfg)
+    o.set_goal_joint(bad, cfg.goal_tol)
+    sid = o.set_start(cfg.start)
+    o.search_params(5.0, 1.0, 1.0, True, False, 0, 0)
+    eo = o.plan()
+    p = Oracle(cfg)
+    p.set_goal_joint(bad, cfg.goal_tol); p.set_start(cfg.start)
+    want = AraStarLoop(p.get_succs, lambda i: 0 if i == 0 else p.heuristic_q(p.get_state(i)[0])).replan(sid, 0, 5.0, 1.0, 1.0)
+    assert want["result"] == capi.ARA_EXHAUSTED and want["solved"] == 0 and np.array_equal(want["log"], eo["expansion_log"])
+    n = eo["expansions"]
+    # ret, result, call_expansions, get_n_expands, solved, path_len, the caller's cost, get_solution_eps, the caller's vector
+    assert next(ln for ln in lines if ln.startswith("exhausted ")).split() == \
+        ["exhausted", "0", str(want["result"]), str(n), str(n), "0", "0", "-3", "inf", "-7", "-7"]
+
+    r = Oracle(cfg)
+    r.set_goal_joint(cfg.goal, cfg.goal_tol); r.set_start(cfg.start)
+    r.search_params(5.0, 1.0, 1.0, True, False, 0, 0)
+    er = r.plan()
+    assert er["ok"] == 1
+    second = next(ln for ln in lines if ln.startswith("second ")).split()
+    # ret, result, resumed, cost, get_n_expands, get_solution_eps, then the path: ids of this space, whose lattice started
+    # over with the new goal -- held to its length, its ends and, through the cost, its edges
+    assert second[1:6] == ["1", str(capi.ARA_SUCCESS), "0", str(er["cost"]), str(er["expansions"])] and float(second[6]) == er["eps"]
+    assert len(second[7:]) == len(er["path"]) and second[7] == str(sid) and second[-1] == "0"
     assert lines[-1] == "done"

@@ -335,6 +335,14 @@ def width_case(nv: int, rows=None, seed=None) -> scenes.Config:
                          [1.5 * r for r in res], boxes)
 
 
+def unreachable_goal(nv):
+    """width_case(nv)'s joint goal with variable 0 five cells below its lower limit: no state inside the limits satisfies it
+    (the tolerance is a cell and a half), and the lattice inside the limits is finite, so a search for it pops every
+    reachable state once and ends with an empty OPEN (tests/test_arastar_loop.py, tests/test_gpu_search_endings.py)"""
+    cfg = width_case(nv)
+    return [chain_limits(nv)[0][0] - 5 * cfg.params.resolutions[0]] + list(cfg.goal[1:])
+
+
 def case_config(name):
     """the Config of an entry of ALL_CASES"""
     for n, nv, rows in ALL_CASES:
