@@ -377,8 +377,10 @@ int smplx_cc_edge_clearance_batch(smplx_space* s, const double* a, const double*
 /* ---- attached collision bodies (CollisionSpace::processAttachedCollisionObject -> attachObject / detachObject,
  * sbpl_collision_checking/src/collision_space.cpp:119-124, 297-345) ----
  * A body is a set of spheres (n x {x, y, z, r}, metres, in the frame of `link`) rigidly attached to a link of the
- * collision group.  The engine builds its bounding sphere tree as it builds a link's (base_collision_models.cpp:337-444;
- * voxelising shapes into spheres is the caller's part) and from then on every state and edge check -- smplx_cc_*, the
+ * collision group.  The caller passes the spheres themselves (smplx_attach_body) or, as the reference's attachObject
+ * does, shapes at poses that the engine voxelises into spheres on the GPU (smplx_attach_object, below).  The engine
+ * builds the body's bounding sphere tree as it builds a link's (base_collision_models.cpp:337-444) and from then on every
+ * state and edge check -- smplx_cc_*, the
  * start check of smplx_set_start, successor evaluation and both searches -- also checks the body:
  *   - against the grid, with the space's padding (collision_operations.h:67-77);
  *   - against every tree of the robot whose link is not in `allowed`, and against every other body unless either
@@ -394,6 +396,34 @@ int smplx_cc_edge_clearance_batch(smplx_space* s, const double* a, const double*
  * work (launches on the caller's streams included) before it changes the bodies' image. */
 int smplx_attach_body(smplx_space* s, const char* id, const char* link, const double* spheres, int n, const char* const* allowed,
                       int nallowed);
+/* CollisionSpace::attachObject(id, shapes, transforms, link_name) (collision_space.cpp:297-304): the object arrives as
+ * shapes at poses in the frame of `link` (smplx_shape as for world objects, its pose relative to the link instead of the
+ * world) and its sphere model is made on the GPU as AttachedBodiesCollisionModel::generateSpheresModel makes it
+ * (attached_bodies_collision_model.cpp:264-313).  For shapes 0 .. n-1 in order: the mesh of the shape as for a world
+ * object, its vertices through the pose; the SURFACE voxelised (fill = false) at res = radius / sqrt(2) on a
+ * PivotVoxelGrid with pivot (0, 0, 0) that covers the mesh's own bounding box (voxelize.cpp:1008-1035; index range
+ * [discretize(min), discretize(min + (max - min))], voxel_grid.h:174-196), indices negative where the mesh is, no cell
+ * dropped; every filled voxel (i, j, k) in ExtractVoxels order gives the sphere {i * res, j * res, k * res, radius}.  The
+ * shapes' lists lie back to back: a voxel two shapes fill gives two spheres.  The reference's radius is the constant
+ * SMPLX_ATTACHED_SPHERE_RADIUS.
+ * smplx_attach_object then leaves the space exactly as smplx_attach_body with those rows would: same nodes, same
+ * `allowed`, same EDITS AND SPACES rule, same wait for the device; detach and the three queries below serve both kinds.
+ * SMPLX_E_ARG: whatever smplx_attach_body refuses of id and link; whatever the world-object calls refuse of shapes (n < 1,
+ * an unknown type, non-finite numbers, a dimension <= 0, bad mesh arrays); a radius that is not finite or <= 0; and
+ * shapes that give no sphere at all (only degenerate triangles) -- the reference would attach an empty model that is never
+ * checked, this refuses it.  SMPLX_E_LIMIT as for smplx_attach_body, the text giving the number of spheres the shapes
+ * made, and for shapes whose index ranges hold more than 2^28 voxels.  A refused call changes nothing: bodies, device
+ * image and query state stay, smplx_get_succs keeps working.
+ * What fits: a surface makes about one sphere per 2 cm^2 at radius 0.025, and one body may have 512 spheres (1023 nodes),
+ * so about 1000 cm^2 of surface: a 6 x 4 x 10 cm box makes 122 spheres, a 20 cm cube 1172 and is refused. */
+#define SMPLX_ATTACHED_SPHERE_RADIUS 0.025
+int smplx_attach_object(smplx_space* s, const char* id, const char* link, const smplx_shape* shapes, int n, double radius,
+                        const char* const* allowed, int nallowed);
+/* what smplx_attach_object would attach; changes nothing: first[k] .. first[k + 1] is shape k's range, the first
+ * min(cap, first[n]) rows {x, y, z, r} are copied (xyzr may be NULL with cap 0).  Shapes that give no sphere are
+ * SMPLX_OK here, with first[n] == 0.  Uses the space's voxeliser work space: one such call at a time per space */
+int smplx_object_spheres(smplx_space* s, const smplx_shape* shapes, int n, double radius, double* xyzr, int cap,
+                         int32_t* first /* n+1 */);
 int smplx_detach_body(smplx_space* s, const char* id);            /* SMPLX_E_ARG for an id not attached */
 /* the attached bodies in attach order: returns their number; names gets one "id link\n" line per body (cap bytes,
  * NUL-terminated, may be NULL with cap 0); first_node / nnodes (SMPLX_MAX_BODIES entries each, may be NULL): each body's

@@ -255,6 +255,15 @@ struct CollisionObject {
     std::vector<Shape> shapes;
     std::vector<Pose> shape_poses;
 };
+// moveit_msgs::AttachedCollisionObject as CollisionSpace::processAttachedCollisionObject reads it (collision_space.cpp:
+// 318-348): the object (its shape poses in the frame of link_name), the link, the touch links and the operation, which
+// the message keeps in object.operation
+struct AttachedCollisionObject {
+    CollisionObject object;
+    std::string link_name;
+    std::vector<std::string> touch_links;
+    enum Operation { ADD, REMOVE, APPEND, MOVE } operation = ADD;
+};
 
 // One query context on one GPU.  Owns the C-ABI handles; the three plugin facades below share it, the
 // way the reference's lattice, heuristic and checker share one OccupancyGrid and one RobotModel.
@@ -383,7 +392,37 @@ public:
         return smplx_attach_body(ctx_->space(), id.c_str(), link_name.c_str(), xyzr.data(), (int)spheres.size(), names.data(),
                                  (int)names.size()) == SMPLX_OK;
     }
+    // collision_space.cpp:297-304, the reference's own signature plus the allowed list: shapes at poses in the frame of
+    // link_name, voxelised on the GPU into spheres of SMPLX_ATTACHED_SPHERE_RADIUS exactly as generateSpheresModel makes them
+    // (smplx_attach_object in include/smpl_amd.h).  False for shapes and transforms of different lengths and wherever the
+    // C call fails: an id already attached, a link unknown or outside the group, a bad shape, shapes that make no sphere,
+    // an object of more than 512 spheres.
+    bool attachObject(const std::string& id, const std::vector<Shape>& shapes, const std::vector<Pose>& transforms,
+                      const std::string& link_name, const std::vector<std::string>& allowed = {})
+    {
+        std::vector<smplx_shape> flat;
+        if (!flatten(shapes, transforms, flat)) return false;
+        std::vector<const char*> names;
+        for (const std::string& a : allowed) names.push_back(a.c_str());
+        return smplx_attach_object(ctx_->space(), id.c_str(), link_name.c_str(), flat.data(), (int)flat.size(), SMPLX_ATTACHED_SPHERE_RADIUS,
+                                   names.data(), (int)names.size()) == SMPLX_OK;
+    }
     bool detachObject(const std::string& id) { return smplx_detach_body(ctx_->space(), id.c_str()) == SMPLX_OK; }
+    // collision_space.cpp:318-348: ADD attaches the object's shapes to link_name, REMOVE detaches the id; APPEND and MOVE
+    // return false where the reference throws "unimplemented".  Difference: the reference ignores the touch links
+    // ("TODO: handle touch links", :331) and so checks the object against the link that holds it; here they are passed
+    // as the allowed list.
+    bool processAttachedCollisionObject(const AttachedCollisionObject& ao)
+    {
+        switch (ao.operation) {
+        case AttachedCollisionObject::ADD:
+            return attachObject(ao.object.id, ao.object.shapes, ao.object.shape_poses, ao.link_name, ao.touch_links);
+        case AttachedCollisionObject::REMOVE:
+            return detachObject(ao.object.id);
+        default:
+            return false;
+        }
+    }
     // collision_space.cpp:228-275 over world_collision_model.cpp:193-280: world objects, voxelised on the GPU as the
     // reference voxelises them (smplx_world_* in include/smpl_amd.h).  False with the reason in smplx_last_error() where the
     // reference returns false (an id already in the world, an unknown id, shapes and poses of different lengths) and for
@@ -474,15 +513,16 @@ public:
 
 private:
     // checkObjectInsert (world_collision_model.cpp:401-404): one pose per shape
-    static bool flatten(const CollisionObject& object, std::vector<smplx_shape>& out)
+    static bool flatten(const CollisionObject& object, std::vector<smplx_shape>& out) { return flatten(object.shapes, object.shape_poses, out); }
+    static bool flatten(const std::vector<Shape>& shapes, const std::vector<Pose>& poses, std::vector<smplx_shape>& out)
     {
-        if (object.shapes.size() != object.shape_poses.size()) return false;
-        for (size_t i = 0; i < object.shapes.size(); ++i) {
-            const Shape& s = object.shapes[i];
+        if (shapes.size() != poses.size()) return false;
+        for (size_t i = 0; i < shapes.size(); ++i) {
+            const Shape& s = shapes[i];
             smplx_shape c = {};
             c.type = (int32_t)s.type;
             for (int k = 0; k < 3; ++k) c.dims[k] = s.dims[k];
-            for (int k = 0; k < 12; ++k) c.pose[k] = object.shape_poses[i][k];
+            for (int k = 0; k < 12; ++k) c.pose[k] = poses[i][k];
             c.vertices = s.vertices.data(); c.nvertices = (int32_t)(s.vertices.size() / 3);
             c.triangles = s.triangles.data(); c.ntriangles = (int32_t)(s.triangles.size() / 3);
             if (s.type == Shape::MESH && (s.vertices.size() % 3 != 0 || s.triangles.size() % 3 != 0)) return false;   // voxelize.cpp:1016-1019

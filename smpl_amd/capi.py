@@ -49,7 +49,11 @@ SYMBOLS = [
     "smplx_grid_put_body", "smplx_grid_take_body", "smplx_grid_body_cells",
     "smplx_set_euclid_weights", "smplx_metric_goal_distance", "smplx_pose_distance", "smplx_joint_distance",
     "smplx_space_heuristic",
+    "smplx_attach_object", "smplx_object_spheres",
 ]
+
+# SMPLX_ATTACHED_SPHERE_RADIUS (include/smpl_amd.h): the reference's radius of an attached object's spheres
+ATTACHED_SPHERE_RADIUS = 0.025
 
 # smplx_params.heuristic (include/smpl_amd.h)
 H_BFS, H_EUCLID, H_JOINT_DIST = 0, 1, 2
@@ -675,6 +679,32 @@ class Space:
         L = lib()
         L.smplx_attach_body.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _dp, C.c_int, C.POINTER(C.c_char_p), C.c_int]
         _chk(L.smplx_attach_body(self.h, str(body_id).encode(), str(link).encode(), _p(sp, _dp), sp.shape[0], arr, len(names)))
+
+    def attach_object(self, body_id, link, shapes, allowed=(), radius=ATTACHED_SPHERE_RADIUS):
+        """CollisionSpace::attachObject: shapes (box() / sphere() / cylinder() / cone() / mesh(), poses in the frame of
+        `link`) voxelised on the GPU into spheres of `radius`, then attached like attach_body's"""
+        arr, n, keep = _shape_array(shapes)
+        names = [str(a).encode() for a in allowed]
+        al = (C.c_char_p * max(1, len(names)))(*names)
+        L = lib()
+        L.smplx_attach_object.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(ShapeStruct), C.c_int, C.c_double,
+                                          C.POINTER(C.c_char_p), C.c_int]
+        _chk(L.smplx_attach_object(self.h, str(body_id).encode(), str(link).encode(), arr, n, float(radius), al, len(names)))
+
+    def object_spheres(self, shapes, radius=ATTACHED_SPHERE_RADIUS):
+        """what attach_object would attach, changing nothing: (xyzr (m x 4), first (n + 1): shape k owns rows
+        first[k]:first[k + 1])"""
+        arr, n, keep = _shape_array(shapes)
+        L = lib()
+        L.smplx_object_spheres.argtypes = [C.c_void_p, C.POINTER(ShapeStruct), C.c_int, C.c_double, _dp, C.c_int, _ip]
+        first = np.zeros(n + 1, np.int32)
+        cap = 1024
+        while True:
+            xyzr = np.zeros((cap, 4))
+            _chk(L.smplx_object_spheres(self.h, arr, n, float(radius), _p(xyzr, _dp), cap, _p(first, _ip)))
+            if first[n] <= cap:
+                return xyzr[:first[n]].copy(), first
+            cap = int(first[n])
 
     def detach_body(self, body_id):
         lib().smplx_detach_body.argtypes = [C.c_void_p, C.c_char_p]

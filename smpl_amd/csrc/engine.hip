@@ -193,6 +193,9 @@ void smplx_grid_destroy(smplx_grid* g)
 
 // error text for the other translation units of the library (field.hip)
 int smplx_internal_set_error(int code, const char* msg) { return set_error(code, msg ? msg : ""); }
+// ... and field.hip owns the voxeliser: the sphere rows of an object attached by shape (world_objects.h)
+int smplx_internal_object_spheres(void** work, size_t* work_bytes, const smplx_shape* shapes, int n, double radius, std::vector<double>* rows,
+                                  std::vector<int32_t>* first);
 
 int smplx_model_create(const char* robot_text, smplx_model** out)
 {
@@ -395,6 +398,7 @@ void smplx_space_destroy(smplx_space* s)
     if (s->bfs.d_brick_queued) (void)hipFree(s->bfs.d_brick_queued);
     if (s->dt.d_table) (void)hipFree(s->dt.d_table);
     if (s->att.d_bodies) (void)hipFree(s->att.d_bodies);
+    if (s->att.d_vox) (void)hipFree(s->att.d_vox);
     for (StepLaunch::WorkCounters& w : s->step.work_counters) (void)hipFree(w.p);
     (void)search_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -819,17 +823,17 @@ int upload_bodies(smplx_space* s)
 
 }  // namespace
 
-int smplx_attach_body(smplx_space* s, const char* id, const char* link, const double* spheres, int n, const char* const* allowed,
-                      int nallowed)
+namespace {
+
+// the checks every attach starts with, in the order of the reference's attachBody: the id, then the link.  Fills B.id,
+// B.link and B.joint.
+int attach_target(smplx_space* s, const char* id, const char* link, AttachedBodies::Body& B)
 {
-    if (!s || !id || !link || !spheres || n <= 0 || nallowed < 0 || (nallowed > 0 && !allowed))
-        return set_error(SMPLX_E_ARG, "bad argument");
     const std::string sid(id);
     if (sid.empty() || sid.size() > 255 || sid.find_first_of(" \t\r\n") != std::string::npos)
         return set_error(SMPLX_E_ARG, "a body id is 1 to 255 characters without white space");
     for (const AttachedBodies::Body& b : s->att.bodies)
         if (b.id == sid) return set_error(SMPLX_E_ARG, "a body with id " + sid + " is attached already");
-    AttachedBodies::Body B;
     B.id = sid;
     B.link = link;
     const smplx::HostModel& hm = s->model;
@@ -842,22 +846,76 @@ int smplx_attach_body(smplx_space* s, const char* id, const char* link, const do
     // the reference never checks a body on a link outside the group (attached_bodies_collision_model.cpp:124-135): refused
     if (std::find(hm.group_links.begin(), hm.group_links.end(), B.link) == hm.group_links.end())
         return set_error(SMPLX_E_ARG, "link " + B.link + " is outside the collision group: a body there would never be checked");
-    for (int i = 0; i < 4 * n; ++i)
-        if (!std::isfinite(spheres[i]) || std::fabs(spheres[i]) >= 1e6 || (i % 4 == 3 && spheres[i] < 0.0))
-            return set_error(SMPLX_E_ARG, "spheres: finite x y z r with |value| < 1e6 and r >= 0");
+    return SMPLX_OK;
+}
+
+int attach_allowed(const char* const* allowed, int nallowed, AttachedBodies::Body& B)
+{
     for (int i = 0; i < nallowed; ++i) {
         if (!allowed[i]) return set_error(SMPLX_E_ARG, "null name in the allowed list");
         B.allowed.emplace_back(allowed[i]);
     }
-    if ((int)s->att.bodies.size() >= SMPLX_MAX_BODIES) return set_error(SMPLX_E_LIMIT, "more than SMPLX_MAX_BODIES (8) attached bodies");
+    return SMPLX_OK;
+}
+
+// the limits, then the body joins the space: n rows {x, y, z, r} in the link's frame.  `made` ends the text of a refusal
+// (what made the rows, for an object attached by shape).
+int attach_rows(smplx_space* s, AttachedBodies::Body& B, const double* rows, int n, const std::string& made)
+{
+    if ((int)s->att.bodies.size() >= SMPLX_MAX_BODIES) return set_error(SMPLX_E_LIMIT, "more than SMPLX_MAX_BODIES (8) attached bodies" + made);
     int used = 0;
     for (const AttachedBodies::Body& b : s->att.bodies) used += b.count;
     if ((long long)used + 2ll * n - 1 > SMPLX_MAX_BODY_NODES)
-        return set_error(SMPLX_E_LIMIT, "the attached bodies need more than SMPLX_MAX_BODY_NODES (1024) tree nodes");
-    B.xyzr.assign(spheres, spheres + 4 * (size_t)n);
+        return set_error(SMPLX_E_LIMIT, "the attached bodies need more than SMPLX_MAX_BODY_NODES (1024) tree nodes" + made);
+    B.xyzr.assign(rows, rows + 4 * (size_t)n);
     s->att.bodies.push_back(std::move(B));
     if (int e = upload_bodies(s)) { const std::string m = g_error; s->att.bodies.pop_back(); (void)upload_bodies(s); return set_error(e, m); }
     ++s->att.epoch;
+    return SMPLX_OK;
+}
+
+}  // namespace
+
+int smplx_attach_body(smplx_space* s, const char* id, const char* link, const double* spheres, int n, const char* const* allowed,
+                      int nallowed)
+{
+    if (!s || !id || !link || !spheres || n <= 0 || nallowed < 0 || (nallowed > 0 && !allowed))
+        return set_error(SMPLX_E_ARG, "bad argument");
+    AttachedBodies::Body B;
+    if (int e = attach_target(s, id, link, B)) return e;
+    for (int i = 0; i < 4 * n; ++i)
+        if (!std::isfinite(spheres[i]) || std::fabs(spheres[i]) >= 1e6 || (i % 4 == 3 && spheres[i] < 0.0))
+            return set_error(SMPLX_E_ARG, "spheres: finite x y z r with |value| < 1e6 and r >= 0");
+    if (int e = attach_allowed(allowed, nallowed, B)) return e;
+    return attach_rows(s, B, spheres, n, "");
+}
+
+int smplx_attach_object(smplx_space* s, const char* id, const char* link, const smplx_shape* shapes, int n, double radius,
+                        const char* const* allowed, int nallowed)
+{
+    if (!s || !id || !link || !shapes || n <= 0 || nallowed < 0 || (nallowed > 0 && !allowed))
+        return set_error(SMPLX_E_ARG, "bad argument");
+    AttachedBodies::Body B;
+    if (int e = attach_target(s, id, link, B)) return e;
+    if (int e = attach_allowed(allowed, nallowed, B)) return e;
+    std::vector<double> rows;
+    std::vector<int32_t> first;
+    if (int e = smplx_internal_object_spheres(&s->att.d_vox, &s->att.vox_bytes, shapes, n, radius, &rows, &first)) return e;
+    const int made = (int)(rows.size() / 4);
+    // the reference would attach an empty model that is never checked
+    if (made == 0) return set_error(SMPLX_E_ARG, "the shapes make no sphere: every triangle is degenerate");
+    return attach_rows(s, B, rows.data(), made, ": the shapes made " + std::to_string(made) + " spheres of radius " + std::to_string(radius));
+}
+
+int smplx_object_spheres(smplx_space* s, const smplx_shape* shapes, int n, double radius, double* xyzr, int cap, int32_t* first)
+{
+    if (!s || !shapes || n <= 0 || !first || cap < 0 || (cap > 0 && !xyzr)) return set_error(SMPLX_E_ARG, "bad argument");
+    std::vector<double> rows;
+    std::vector<int32_t> f;
+    if (int e = smplx_internal_object_spheres(&s->att.d_vox, &s->att.vox_bytes, shapes, n, radius, &rows, &f)) return e;
+    for (int k = 0; k <= n; ++k) first[k] = f[(size_t)k];
+    const int take = std::min(cap, f[(size_t)n]);
+    if (take > 0) std::memcpy(xyzr, rows.data(), sizeof(double) * 4 * (size_t)take);
     return SMPLX_OK;
 }
 

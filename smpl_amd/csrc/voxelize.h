@@ -76,6 +76,15 @@ SMPLX_HD int vox_discretize(double w, double pivot, double res, int n)
     if (f > (double)n) f = (double)n;
     return (int)f;
 }
+// the same index for a lattice whose kept range is [lo, hi] (indices may be negative): clamped to [lo - 1, hi + 1], which
+// for the occupancy grid's range [0, n - 1] is vox_discretize
+SMPLX_HD int vox_discretize_in(double w, double pivot, double res, int lo, int hi)
+{
+    double f = floor((w - pivot) / res + 0.5);
+    if (f < (double)lo - 1.0) f = (double)lo - 1.0;
+    if (f > (double)hi + 1.0) f = (double)hi + 1.0;
+    return (int)f;
+}
 SMPLX_HD double vox_continuize(int i, double pivot, double res) { return pivot + i * res; }
 
 // HalfResDiscretizer (discretize.h:94-113), the lattice of the gridless VoxelizeMesh (voxelize.cpp:962-986) that makes a

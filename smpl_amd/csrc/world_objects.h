@@ -17,10 +17,13 @@
 // applies the cells to the occupancy bytes (and reference counts) when the call is an edit.
 // The call's arrays live in one work space kept on the grid (smplx_grid::d_vox) that only grows: device allocations cost
 // more than the kernels (tools/voxelize_time.py), so a call makes one only for the cell list an object keeps.
+// k_vox_spheres turns a compacted list into the sphere rows of an attached object's model (object_spheres.h): one thread
+// per cell; those calls use a work space kept on the space (AttachedBodies::d_vox) in the same way.
 #pragma once
 
 #include <climits>
 
+#include "object_spheres.h"
 #include "voxelize.h"
 
 namespace {
@@ -117,6 +120,20 @@ k_vox_compact(const unsigned char* __restrict__ mask, const VoxShape* __restrict
         __syncthreads();
     }
     if (!Write && threadIdx.x == 0) chunk_n[chunk] = base;
+}
+
+// one thread per cell of a compacted list: the sphere an attached object's model has at that voxel (object_spheres.h),
+// a 32-byte row {x, y, z, r}
+__global__ void __launch_bounds__(FIELD_BLOCK)
+k_vox_spheres(const int* __restrict__ cells, int n, double res, double radius, double* __restrict__ rows)
+{
+    const int i = blockIdx.x * FIELD_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int c[3] = {cells[3 * (size_t)i], cells[3 * (size_t)i + 1], cells[3 * (size_t)i + 2]};
+    double r[4];
+    smplx_object_host::sphere_row(c, res, radius, r);
+    double* out = rows + 4 * (size_t)i;
+    out[0] = r[0]; out[1] = r[1]; out[2] = r[2]; out[3] = r[3];
 }
 
 struct DevBuf {
@@ -299,8 +316,8 @@ int voxelize_meshes(void** work, size_t* work_bytes, const VoxLattice& L, const 
                     tl[a] = std::max(cl[a], vox_half_discretize(mn, L.res));
                     th[a] = std::min(cl[3 + a], vox_half_discretize(mx, L.res));
                 } else {
-                    tl[a] = std::max(cl[a], vox_discretize(mn, L.offset[a], L.res, cl[3 + a] + 1));
-                    th[a] = std::min(cl[3 + a], vox_discretize(mx, L.offset[a], L.res, cl[3 + a] + 1));
+                    tl[a] = std::max(cl[a], vox_discretize_in(mn, L.offset[a], L.res, cl[a], cl[3 + a]));
+                    th[a] = std::min(cl[3 + a], vox_discretize_in(mx, L.offset[a], L.res, cl[a], cl[3 + a]));
                 }
                 any = any && th[a] >= tl[a];
             }
@@ -404,6 +421,48 @@ int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, uns
     }
     const VoxLattice L{{g->origin[0], g->origin[1], g->origin[2]}, g->res, false};
     return voxelize_meshes(&g->d_vox, &g->vox_bytes, L, meshes, clip, occ, counts, g->n[1], g->n[2], out);
+}
+
+// the sphere model of an attached object (generateSpheresModel, attached_bodies_collision_model.cpp:264-313): every
+// shape's surface voxelised on the lattice of object_spheres.h -- pivot 0, resolution radius / sqrt(2), candidates clipped
+// to the index range of the shape's own bounding box, negative indices kept -- and one row {x, y, z, radius} per filled
+// voxel, the shapes' lists back to back (a voxel two shapes fill gives two rows).  work / work_bytes: the caller's work
+// space; it holds the voxeliser's arrays and then the rows, which are copied back once.  Waits for the device.
+int object_spheres_run(void** work, size_t* work_bytes, const std::vector<WorldShape>& shapes, double radius, std::vector<double>& rows,
+                       std::vector<int32_t>& first)
+{
+    const double res = smplx_object_host::resolution(radius);
+    std::vector<Mesh> meshes(shapes.size());
+    std::vector<int> clip(6 * shapes.size());
+    long long cells = 0;
+    for (size_t s = 0; s < shapes.size(); ++s) {
+        shape_mesh(shapes[s], meshes[s]);
+        smplx_object_host::clip_range(meshes[s].v.data(), meshes[s].v.size() / 3, res, &clip[6 * s]);
+        cells += smplx_object_host::range_cells(&clip[6 * s]);
+        if (cells > smplx_object_host::kMaxRangeCells)
+            return smplx_internal_set_error(SMPLX_E_LIMIT, "the shapes' bounding boxes hold more than 2^28 voxels at this radius");
+    }
+    const VoxLattice L{{0.0, 0.0, 0.0}, res, false};
+    VoxLists lists;
+    if (int e = voxelize_meshes(work, work_bytes, L, meshes, clip, nullptr, nullptr, 0, 0, lists)) return e;
+    DevBuf d_cells;
+    d_cells.p = lists.d_cells;
+    first.assign(lists.first.begin(), lists.first.end());
+    const int total = lists.first.back();
+    rows.assign(4 * (size_t)total, 0.0);
+    if (total == 0) return SMPLX_OK;
+    const size_t need = sizeof(double) * 4 * (size_t)total;
+    if (need > *work_bytes) {          // the voxeliser's arrays are done with: the rows may take a new block
+        if (*work) (void)hipFree(*work);
+        *work = nullptr; *work_bytes = 0;
+        FIELD_TRY(hipMalloc(work, need));
+        *work_bytes = need;
+    }
+    hipLaunchKernelGGL(k_vox_spheres, dim3((total + FIELD_BLOCK - 1) / FIELD_BLOCK), dim3(FIELD_BLOCK), 0, 0, (const int*)d_cells.p, total, res, radius,
+                       (double*)*work);
+    FIELD_TRY(hipGetLastError());
+    FIELD_TRY(hipMemcpy(rows.data(), *work, need, hipMemcpyDeviceToHost));
+    return SMPLX_OK;
 }
 
 // takes the stored lists of an object out of the occupancy (removePointsFromField per shape, world_collision_model.cpp:
@@ -551,6 +610,17 @@ int smplx_world_voxelize(const smplx_grid* g, const smplx_shape* shapes, int n, 
     if (lists.d_cells) (void)hipFree(lists.d_cells);
     if (e != hipSuccess) return smplx_internal_set_error(SMPLX_E_HIP, (std::string("cell download: ") + hipGetErrorString(e)).c_str());
     return rc;
+}
+
+// for engine.hip (smplx_attach_object / smplx_object_spheres), not part of the ABI: checks the shapes and the radius and
+// makes the sphere rows of the object; work / work_bytes is the voxeliser work space of the calling space
+int smplx_internal_object_spheres(void** work, size_t* work_bytes, const smplx_shape* shapes, int n, double radius, std::vector<double>* rows,
+                                  std::vector<int32_t>* first)
+{
+    std::vector<WorldShape> ws;
+    if (int e = take_shapes(shapes, n, ws)) return e;
+    if (!(radius > 0.0 && radius < 1.0e6)) return smplx_internal_set_error(SMPLX_E_ARG, "the sphere radius must be positive and finite (< 1e6)");
+    return object_spheres_run(work, work_bytes, ws, radius, *rows, *first);
 }
 
 }  // extern "C"

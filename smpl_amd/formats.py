@@ -256,7 +256,8 @@ def urdf_to_body_text(urdf_xml: str, collision_yaml_text: str, group: str, meshe
 def box_spheres(center, size, pitch, radius):
     """Spheres of one radius on a regular grid that spans a box, corners included, at most `pitch` apart (centre and size
     in a link's frame, metres): n x (x, y, z, r) for Space.attach_body.  Not the reference's mesh voxeliser
-    (attached_bodies_collision_model.cpp:264-313 voxelises the shape's surface): a plain filled box."""
+    (attached_bodies_collision_model.cpp:264-313 voxelises the shape's surface; Space.attach_object makes that model):
+    a plain filled box."""
     import math
     import numpy as np
     axes = []
