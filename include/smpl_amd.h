@@ -108,13 +108,32 @@ int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2);
  * -- where the reference keeps the outside points and addPointsToMap skips them (distance_map.hpp:312-316); the field is
  * the same and a huge off-grid mesh cannot ask for an unbounded mask.
  *
- * pose: 3x4 row major (rotation | translation), world frame, like smplx_planning_pose_batch.  Planes and octomaps are
- * not supported (SMPLX_E_ARG, like any unknown type).
+ * An OCTREE (the planning scene's octomap: collision_space.cpp:154-156, 285-288, world_collision_model.cpp:303-330,
+ * 434-470) is no mesh.  It holds the occupied leaves of an octree as rows {cx, cy, cz, size} -- centre and edge length in
+ * the octree's own frame, in the order the caller's octomap library yields them (begin_leafs()); the engine links no
+ * octomap code and reads no .bt / .ot files -- and is voxelised as VoxelizeOcTree does it (voxel_operations.cpp:405-436),
+ * in binary64 without fused multiply-add, leaf by leaf: a leaf with size <= res gives one point, its centre; any other
+ * gives c = ceil(size / res) * res and three nested loops, x outermost and z innermost, each
+ * `for (v = centre - c; v < centre + c; v += res)`, so the value at step k is the k-fold running sum and the trips are
+ * what that sum yields against `<` (2 c / res, or one more).  The reference samples twice the leaf's width; so does
+ * this.  Every point goes through the pose like a mesh vertex (R v + t) and through the point rule of
+ * smplx_grid_add_points (OccupancyGrid::worldToGrid) to a cell; points whose cell lies outside the grid are dropped (the
+ * deliberate difference above).  The cell list of an OCTREE is the remaining cells in that generation order, DUPLICATES
+ * KEPT -- the reference stores and adds every point -- so on a reference-counted grid a cell hit k times counts k, and
+ * remove takes the same k out again.  Only the leaf rows cross to the device: trips, prefix sums, points and the
+ * order-preserving compaction are kernels (smpl_amd/csrc/octree_points.h, world_objects.h).
+ *
+ * pose: 3x4 row major (rotation | translation), world frame, like smplx_planning_pose_batch.  Planes are not supported
+ * (SMPLX_E_ARG, like any unknown type; the reference's VoxelizeShape does not voxelise them either).
  * Refused with SMPLX_E_ARG: a null pointer, an empty id or one with a line break, n < 1, an unknown shape type,
  * non-finite numbers (|x| >= 1e6), a dimension <= 0, a MESH without vertices or triangles or with an index outside
- * [0, nvertices), an id already in the world (checkObjectInsert, world_collision_model.cpp:394-407) and, for remove
- * and move, an id that is not (checkObjectRemove :414-417).  SMPLX_E_STATE: a grid created from a finished field
- * (smplx_grid_create), which refuses objects as it refuses points.  A refused call changes nothing.
+ * [0, nvertices), an OCTREE without leaves (null vertices or nvertices < 1), with triangles (non-null, or ntriangles
+ * != 0) or with a leaf of size <= 0, an id already in the world (checkObjectInsert, world_collision_model.cpp:394-407)
+ * and, for remove and move, an id that is not (checkObjectRemove :414-417).  SMPLX_E_STATE: a grid created from a
+ * finished field (smplx_grid_create), which refuses objects as it refuses points.  SMPLX_E_LIMIT, before anything is
+ * allocated or launched: an OCTREE leaf with size / res > 1024, more than 2^28 leaves in one call, or a bound on the
+ * call's sample points -- (2 ceil(size / res) + 1)^3 summed over its leaves, 1 for a leaf of size <= res -- above the
+ * voxeliser's cap of 2^31 / 3 cells in one call.  A refused call changes nothing.
  *
  * insert adds each shape's list in order (:227-231): on a reference-counted grid a cell covered by two shapes counts
  * twice.  remove takes the stored lists out again (:241-262): WITHOUT reference counts this frees cells another object
@@ -123,13 +142,14 @@ int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2);
  * then the field is updated once over the union of the two windows; field and counts equal remove followed by insert.
  * Every edit follows EDITS AND SPACES above; an object whose shapes lie wholly outside the grid is a valid edit that
  * changes no cell.  Cell lists stay on the device; smplx_world_object_cells copies one on request. */
-enum { SMPLX_SHAPE_BOX = 1, SMPLX_SHAPE_SPHERE = 2, SMPLX_SHAPE_CYLINDER = 3, SMPLX_SHAPE_CONE = 4, SMPLX_SHAPE_MESH = 5 };
+enum { SMPLX_SHAPE_BOX = 1, SMPLX_SHAPE_SPHERE = 2, SMPLX_SHAPE_CYLINDER = 3, SMPLX_SHAPE_CONE = 4, SMPLX_SHAPE_MESH = 5,
+       SMPLX_SHAPE_OCTREE = 6 };
 typedef struct {
-    int32_t type;            /* SMPLX_SHAPE_BOX / SPHERE / CYLINDER / CONE / MESH */
-    double dims[3];          /* box: x y z;  sphere: r;  cylinder, cone: r, height */
-    double pose[12];         /* 3x4 row major, world frame, like smplx_planning_pose_batch */
-    const double* vertices;  int32_t nvertices;    /* MESH only */
-    const int32_t* triangles; int32_t ntriangles;  /* MESH only: ntriangles x 3 indices */
+    int32_t type;            /* SMPLX_SHAPE_BOX / SPHERE / CYLINDER / CONE / MESH / OCTREE */
+    double dims[3];          /* box: x y z;  sphere: r;  cylinder, cone: r, height;  mesh, octree: ignored */
+    double pose[12];         /* 3x4 row major, world frame, like smplx_planning_pose_batch; OCTREE: the octomap's origin */
+    const double* vertices;  int32_t nvertices;    /* MESH: nvertices x 3;  OCTREE: nvertices leaf rows of cx, cy, cz, size */
+    const int32_t* triangles; int32_t ntriangles;  /* MESH only: ntriangles x 3 indices;  OCTREE: NULL and 0 */
 } smplx_shape;
 int smplx_world_insert_object(smplx_grid* g, const char* id, const smplx_shape* shapes, int n);
 int smplx_world_remove_object(smplx_grid* g, const char* id);
@@ -139,7 +159,9 @@ int smplx_world_remove_all(smplx_grid* g);
  * small) may be NULL with cap 0 */
 int smplx_world_objects(const smplx_grid* g, char* names, int cap, int* n);  /* '\n'-separated, insertion order */
 /* the cell list of one shape of an object: *n = its length, the first min(cap, *n) cells are copied (cells may be NULL
- * with cap 0); SMPLX_E_ARG for an unknown id or shape index */
+ * with cap 0); SMPLX_E_ARG for an unknown id or shape index.  The analytic shapes and meshes list each cell once, in
+ * ExtractVoxels order; an OCTREE lists one cell per sample point inside the grid, in generation order, so a cell appears
+ * as often as points fell into it */
 int smplx_world_object_cells(const smplx_grid* g, const char* id, int shape, int32_t* cells /* n x 3 */, int cap, int* n);
 /* runs the voxeliser and changes nothing (any grid, also one from a finished field): first[s] .. first[s + 1] is the
  * range of shape s in the lists laid back to back; the first min(cap, first[n]) cells are copied.  Like the edits it
@@ -409,7 +431,8 @@ int smplx_attach_body(smplx_space* s, const char* id, const char* link, const do
  * smplx_attach_object then leaves the space exactly as smplx_attach_body with those rows would: same nodes, same
  * `allowed`, same EDITS AND SPACES rule, same wait for the device; detach and the three queries below serve both kinds.
  * SMPLX_E_ARG: whatever smplx_attach_body refuses of id and link; whatever the world-object calls refuse of shapes (n < 1,
- * an unknown type, non-finite numbers, a dimension <= 0, bad mesh arrays); a radius that is not finite or <= 0; and
+ * an unknown type, non-finite numbers, a dimension <= 0, bad mesh arrays); an OCTREE shape (nobody holds an octomap in a
+ * gripper: octrees are world objects only, and the text names them); a radius that is not finite or <= 0; and
  * shapes that give no sphere at all (only degenerate triangles) -- the reference would attach an empty model that is never
  * checked, this refuses it.  SMPLX_E_LIMIT as for smplx_attach_body, the text giving the number of spheres the shapes
  * made, and for shapes whose index ranges hold more than 2^28 voxels.  A refused call changes nothing: bodies, device

@@ -235,13 +235,17 @@ private:
 
 // sbpl::collision::Object (sbpl_collision_checking/include/sbpl_collision_checking/shapes.h, world_collision_model.h): an
 // id, shapes and one pose per shape.  A Shape is the flat form of the reference's shapes::Shape hierarchy: box size, sphere
-// radius, cylinder / cone radius and length, or a mesh's vertices and index triples.  Planes and octrees are not supported.
+// radius, cylinder / cone radius and length, a mesh's vertices and index triples, or an octree's occupied leaves (shapes::
+// OcTree: rows {cx, cy, cz, size} in the order the octomap's begin_leafs() yields them; world objects only).  Planes are
+// not supported.
 struct Shape {
-    enum Type { BOX = SMPLX_SHAPE_BOX, SPHERE = SMPLX_SHAPE_SPHERE, CYLINDER = SMPLX_SHAPE_CYLINDER, CONE = SMPLX_SHAPE_CONE, MESH = SMPLX_SHAPE_MESH };
+    enum Type { BOX = SMPLX_SHAPE_BOX, SPHERE = SMPLX_SHAPE_SPHERE, CYLINDER = SMPLX_SHAPE_CYLINDER, CONE = SMPLX_SHAPE_CONE, MESH = SMPLX_SHAPE_MESH,
+                OCTREE = SMPLX_SHAPE_OCTREE };
     Type type = BOX;
     double dims[3] = {0.0, 0.0, 0.0};      // box: x y z;  sphere: r;  cylinder, cone: r, length
-    std::vector<double> vertices;          // MESH: 3 per vertex
+    std::vector<double> vertices;          // MESH: 3 per vertex;  OCTREE: 4 per leaf
     std::vector<int32_t> triangles;        // MESH: 3 per triangle
+    static Shape OcTree(std::vector<double> leaves) { Shape s; s.type = OCTREE; s.vertices = std::move(leaves); return s; }
     static Shape Box(double x, double y, double z) { Shape s; s.type = BOX; s.dims[0] = x; s.dims[1] = y; s.dims[2] = z; return s; }
     static Shape Sphere(double r) { Shape s; s.type = SPHERE; s.dims[0] = r; return s; }
     static Shape Cylinder(double r, double length) { Shape s; s.type = CYLINDER; s.dims[0] = r; s.dims[1] = length; return s; }
@@ -443,6 +447,20 @@ public:
     }
     virtual bool insertShapes(const CollisionObject& object) { return moveShapes(object); }
     virtual bool removeShapes(const CollisionObject& object) { return moveShapes(object); }
+    // CollisionSpace::processOctomapMsg (collision_space.cpp:285-288) -> WorldCollisionModel::insertOctomap
+    // (world_collision_model.cpp:303-318): the octomap becomes a world object of one octree shape at its origin pose.  The
+    // caller walks their octomap's begin_leafs() and passes the occupied leaves, 4 doubles each {cx, cy, cz, size}.  False
+    // where checkInsertOctomap (:553-572) refuses -- an id already in the world (the frame and the binary flag of the
+    // message have no counterpart here) -- and for leaves the engine refuses.  The object is removed and moved like any
+    // other (removeObject, moveShapes with Shape::OcTree).
+    virtual bool processOctomapMsg(const std::string& id, const std::vector<double>& leaves, const Pose& origin)
+    {
+        CollisionObject object;
+        object.id = id;
+        object.shapes.push_back(Shape::OcTree(leaves));
+        object.shape_poses.push_back(origin);
+        return insertObject(object);
+    }
     // The robot's links outside the planning group as obstacles (smplx_body_* in include/smpl_amd.h; the reference keeps
     // them in the grid through SelfCollisionModelImpl::updateVoxelsStates, self_collision_model.cpp:770-837).
     // attachRobotBody builds the voxel models of a body text and places them; setJointPosition
@@ -526,6 +544,11 @@ private:
             c.vertices = s.vertices.data(); c.nvertices = (int32_t)(s.vertices.size() / 3);
             c.triangles = s.triangles.data(); c.ntriangles = (int32_t)(s.triangles.size() / 3);
             if (s.type == Shape::MESH && (s.vertices.size() % 3 != 0 || s.triangles.size() % 3 != 0)) return false;   // voxelize.cpp:1016-1019
+            if (s.type == Shape::OCTREE) {         // leaf rows of four doubles, no triangles
+                if (s.vertices.empty() || s.vertices.size() % 4 != 0 || !s.triangles.empty()) return false;
+                c.nvertices = (int32_t)(s.vertices.size() / 4);
+                c.triangles = nullptr;
+            }
             out.push_back(c);
         }
         return true;

@@ -215,7 +215,7 @@ def table_probe(nvars, slots, one_home, inserted, queries):
 
 
 # smplx_shape.type (include/smpl_amd.h)
-SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER, SHAPE_CONE, SHAPE_MESH = 1, 2, 3, 4, 5
+SHAPE_BOX, SHAPE_SPHERE, SHAPE_CYLINDER, SHAPE_CONE, SHAPE_MESH, SHAPE_OCTREE = 1, 2, 3, 4, 5, 6
 E_ARG = -1
 
 
@@ -266,6 +266,16 @@ def mesh(vertices, triangles, pose=None):
     return _shape(SHAPE_MESH, [], pose, vertices=v.reshape(-1, 3), triangles=t.reshape(-1, 3))
 
 
+def octree(leaves, pose=None):
+    """shapes::OcTree: leaves is n x 4, one row {cx, cy, cz, size} per occupied leaf (centre and edge length in the
+    octree's frame, in the order the octomap's begin_leafs() yields them); pose is the octomap's origin.  Anything that
+    is not n x 4 with n >= 1 is refused here; scenes.octree_leaves makes such rows from a point cloud."""
+    v = _f64(leaves)
+    if v.ndim != 2 or v.shape[1] != 4 or v.shape[0] < 1:
+        raise SmplxError(E_ARG, "octree leaves come as n x 4 rows of cx, cy, cz, size")
+    return _shape(SHAPE_OCTREE, [], pose, leaves=v)
+
+
 def _shape_array(shapes):
     """-> (smplx_shape array, the numpy arrays it points into: keep them alive over the call)"""
     shapes = list(shapes)
@@ -278,6 +288,10 @@ def _shape_array(shapes):
             v = _f64(s["vertices"]).reshape(-1, 3); t = np.ascontiguousarray(s["triangles"], dtype=np.int32).reshape(-1, 3)
             keep += [v, t]
             a.vertices, a.nvertices, a.triangles, a.ntriangles = _p(v, _dp), v.shape[0], _p(t, _ip), t.shape[0]
+        elif "leaves" in s:      # an octree's rows travel through `vertices`, four doubles each
+            v = _f64(s["leaves"]).reshape(-1, 4)
+            keep.append(v)
+            a.vertices, a.nvertices = _p(v, _dp), v.shape[0]
     return arr, len(shapes), keep
 
 
@@ -351,7 +365,7 @@ class Grid:
         return out
 
     # ---- world objects (include/smpl_amd.h "world objects"): shapes are what box() / sphere() / cylinder() / cone() /
-    # mesh() above return
+    # mesh() / octree() above return
     def insert_object(self, object_id, shapes):
         arr, n, keep = _shape_array(shapes)
         lib().smplx_world_insert_object.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ShapeStruct), C.c_int]
@@ -386,7 +400,8 @@ class Grid:
             cap *= 4
 
     def object_cells(self, object_id, shape=0):
-        """the cells (n x 3) shape `shape` of the object was voxelised into, in ExtractVoxels order"""
+        """the cells (n x 3) shape `shape` of the object was voxelised into, in ExtractVoxels order; for an octree one
+        cell per sample point inside the grid, in generation order, duplicates kept"""
         L = lib()
         L.smplx_world_object_cells.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _ip, C.c_int, C.POINTER(C.c_int)]
         n = C.c_int(0)

@@ -38,6 +38,7 @@
 
 #include "../../include/smpl_amd.h"
 #include "grid_handle.h"
+#include "octree_points.h"
 
 namespace {
 
@@ -225,7 +226,7 @@ Window edit_window(const smplx_grid* g, const Window& box)
 }
 
 // OccupancyGrid::worldToGrid (distance_map.hpp:520-527)
-inline int world_to_cell(const smplx_grid* g, double w, int a) { return (int)(g->dev.inv_res * (w - g->dev.origin_minus_res[a]) + 0.5) - 1; }
+inline int world_to_cell(const smplx_grid* g, double w, int a) { return oct_world_to_cell(w, g->dev.origin_minus_res[a], g->dev.inv_res); }
 
 inline bool finite_coords(const double* v, size_t n)
 {

@@ -1,0 +1,62 @@
+// smpl_amd/csrc/octree_points.h -- the sample points of an octree's occupied leaves (world objects, SMPLX_SHAPE_OCTREE),
+// included by field.hip.  What it stands behind: sbpl::collision::VoxelizeOcTree
+// (sbpl_collision_checking/src/voxel_operations.cpp:405-436) followed by OccupancyGrid::worldToGrid
+// (smpl/include/smpl/distance_map/detail/distance_map.hpp:520-527).
+//
+// A leaf is a row {cx, cy, cz, size}.  size <= res: one point, the centre (:415-418).  Otherwise c = ceil(size / res) * res
+// and three nested loops (x outermost, z innermost), each `for (v = centre - c; v < centre + c; v += res)` (:420-423): the
+// value at step k is the k-fold RUNNING SUM, and the number of trips is whatever that sum yields against `<` -- 2 c / res,
+// or one more where the rounding of the sum leaves the last value just below the bound.  The reference samples twice the
+// leaf's width; so does this.  The arithmetic is restated in binary64 under the contract of det_math.h (no fused
+// multiply-add; host and device compile this one source): oct_axis_trips and oct_axis_value run on the device, and the host
+// compiler builds the same source for tests/cpp/octree_host_driver.cpp.
+//
+// Limits (world_objects.h refuses a call beyond them with SMPLX_E_LIMIT before it allocates or launches anything):
+// size / res <= OCT_MAX_RATIO per leaf, and the bound on the call's sample points, (2 ceil(size / res) + 1)^3 summed over
+// its leaves (1 for a leaf of size <= res), at most OCT_MAX_POINTS -- the voxeliser's cap on the cells of one call.
+// oct_axis_trips stops at the bound's 2 ceil(size / res) + 1 trips.  The running sum reaches that only where res is
+// below about 2^-41 of the coordinates (its rounding errors, at most half an ulp of the coordinate per step over at most
+// 2049 steps, would have to add up to res), which is where the reference's loop stops advancing altogether.
+#pragma once
+
+#include "det_math.h"
+
+#define OCT_MAX_RATIO 1024.0
+#define OCT_MAX_POINTS (2147483647LL / 3)
+#define OCT_MAX_LEAVES (1LL << 28)    // of one call: three threads a leaf must fit an int
+
+// :415
+SMPLX_HD bool oct_single(double size, double res) { return size <= res; }
+// :420
+SMPLX_HD double oct_half_width(double size, double res) { return ceil(size / res) * res; }
+// the most trips one loop of the leaf can make (rounding included): the per-axis factor of the bound above
+SMPLX_HD int oct_axis_bound(double size, double res) { return oct_single(size, res) ? 1 : 2 * (int)ceil(size / res) + 1; }
+
+// the trips of one of the three loops (:421-423) of a leaf that is not single
+SMPLX_HD int oct_axis_trips(double centre, double size, double res)
+{
+    const double c = oct_half_width(size, res);
+    const int most = oct_axis_bound(size, res);
+    int n = 0;
+    for (double v = centre - c; v < centre + c && n < most; v += res) ++n;
+    return n;
+}
+
+// the value of the loop variable at trip k
+SMPLX_HD double oct_axis_value(double centre, double size, double res, int k)
+{
+    if (oct_single(size, res)) return centre;
+    double v = centre - oct_half_width(size, res);
+    for (int i = 0; i < k; ++i) v += res;
+    return v;
+}
+
+// OccupancyGrid::worldToGrid (distance_map.hpp:520-527): the C cast truncates towards zero.  The value is clamped to
+// +-2^30 in double before the cast: beyond the grid only "outside" matters, and a far point must not overflow an int.
+SMPLX_HD int oct_world_to_cell(double w, double origin_minus_res, double inv_res)
+{
+    double f = inv_res * (w - origin_minus_res) + 0.5;
+    if (f < -1073741824.0) f = -1073741824.0;
+    if (f > 1073741824.0) f = 1073741824.0;
+    return (int)f - 1;
+}

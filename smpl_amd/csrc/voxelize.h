@@ -47,6 +47,12 @@ struct VoxShape {
 
 SMPLX_HD double vox_dot(const double* a, const double* b) { return a[0] * b[0] + (a[1] * b[1] + a[2] * b[2]); }
 SMPLX_HD void vox_sub(const double* a, const double* b, double* o) { o[0] = a[0] - b[0]; o[1] = a[1] - b[1]; o[2] = a[2] - b[2]; }
+// Affine3d * Vector3d (TransformVertices, voxelize.cpp:608-615; `pose * pt`, voxel_operations.cpp:417, 426): R v + t for a
+// 3x4 row-major pose
+SMPLX_HD void vox_transform(const double* pose, const double* v, double* o)
+{
+    for (int r = 0; r < 3; ++r) o[r] = vox_dot(pose + 4 * r, v) + pose[4 * r + 3];
+}
 SMPLX_HD void vox_cross(const double* a, const double* b, double* o)
 {
     o[0] = a[1] * b[2] - a[2] * b[1];

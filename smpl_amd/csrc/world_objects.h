@@ -19,11 +19,21 @@
 // more than the kernels (tools/voxelize_time.py), so a call makes one only for the cell list an object keeps.
 // k_vox_spheres turns a compacted list into the sphere rows of an attached object's model (object_spheres.h): one thread
 // per cell; those calls use a work space kept on the space (AttachedBodies::d_vox) in the same way.
+//
+// Octrees (SMPLX_SHAPE_OCTREE; voxel_operations.cpp:405-436, arithmetic in octree_points.h) are no meshes: a leaf is
+// sampled at points, every point becomes a cell, and the list keeps them in generation order with duplicates.  Only the
+// leaf rows (32 bytes each) cross to the device.  k_oct_trips gives every (leaf, axis) the trips of its loop; their
+// products are scanned on the device (k_scan_tiles / k_scan_add, level by level); k_oct_points gives one thread one
+// sample point and compacts the in-grid cells in order the way k_vox_compact does -- chunk counts first, then, after the
+// device scan of the counts, the write -- recomputing the point in the second pass instead of storing it.  The list is
+// then added with k_occ_points.  The host reads back 32 bytes: the number of cells (to allocate the list) and the
+// list's bounding range (for the edit window).
 #pragma once
 
 #include <climits>
 
 #include "object_spheres.h"
+#include "octree_points.h"
 #include "voxelize.h"
 
 namespace {
@@ -136,6 +146,120 @@ k_vox_spheres(const int* __restrict__ cells, int n, double res, double radius, d
     out[0] = r[0]; out[1] = r[1]; out[2] = r[2]; out[3] = r[3];
 }
 
+// ---- octrees (octree_points.h): the sample points of the leaves, mapped to cells, in generation order, duplicates kept
+
+// one thread per (leaf, axis): the trips of that loop, by the loop's own arithmetic.  The first six threads also empty
+// the call's bounding range (x0 y0 z0 x1 y1 z1).
+__global__ void __launch_bounds__(FIELD_BLOCK)
+k_oct_trips(const double* __restrict__ leaves, int nleaves, double res, int* __restrict__ trips, int* __restrict__ box)
+{
+    const int i = blockIdx.x * FIELD_BLOCK + threadIdx.x;
+    if (i < 6) box[i] = i < 3 ? INT_MAX : INT_MIN;
+    if (i >= 3 * nleaves) return;
+    const double* L = leaves + 4 * (size_t)(i / 3);
+    trips[i] = oct_single(L[3], res) ? 1 : oct_axis_trips(L[i % 3], L[3], res);
+}
+
+// exclusive scan, in place, of every tile of FIELD_BLOCK entries of v; sums[tile] = the tile's total.  With trips the
+// entries are not read but made: entry i < n - 1 is the points of leaf i, the product of its trips, and entry n - 1 is 0
+// (the scan turns it into the total).
+__global__ void __launch_bounds__(FIELD_BLOCK)
+k_scan_tiles(long long* __restrict__ v, int n, long long* __restrict__ sums, const int* __restrict__ trips)
+{
+    __shared__ long long s[2][FIELD_BLOCK];
+    const int i = blockIdx.x * FIELD_BLOCK + threadIdx.x;
+    long long own = 0;
+    if (trips) { if (i < n - 1) own = (long long)trips[3 * (size_t)i] * trips[3 * (size_t)i + 1] * trips[3 * (size_t)i + 2]; }
+    else if (i < n) own = v[i];
+    int cur = 0;
+    s[0][threadIdx.x] = own;
+    __syncthreads();
+    for (int d = 1; d < FIELD_BLOCK; d <<= 1) {          // Hillis-Steele: after the step with d, s holds sums of 2d entries
+        s[cur ^ 1][threadIdx.x] = s[cur][threadIdx.x] + ((int)threadIdx.x >= d ? s[cur][threadIdx.x - d] : 0);
+        cur ^= 1;
+        __syncthreads();
+    }
+    if (i < n) v[i] = s[cur][threadIdx.x] - own;
+    if (threadIdx.x == FIELD_BLOCK - 1) sums[blockIdx.x] = s[cur][threadIdx.x];
+}
+
+// adds the scanned tile totals back: v[i] += sums[tile of i]
+__global__ void __launch_bounds__(FIELD_BLOCK)
+k_scan_add(long long* __restrict__ v, int n, const long long* __restrict__ sums)
+{
+    const int i = blockIdx.x * FIELD_BLOCK + threadIdx.x;
+    if (i < n) v[i] += sums[blockIdx.x];
+}
+
+// a chunk is one point a thread: the search for a point's leaf is a chain of dependent loads, so a thread that walks
+// several points one after another (as k_vox_compact walks mask bytes) pays that latency several times over while a
+// small octree leaves most of the device idle (profiles/octree_ab.txt)
+#define OCT_CHUNK FIELD_BLOCK
+
+struct OctGrid { double pose[12]; double origin_minus_res[3]; double inv_res, res; int n[3]; };
+
+// one block per chunk of OCT_CHUNK sample points, one thread per point: the point's leaf by a search over the prefix, its
+// (i, j, k) from the leaf's trips, the coordinates by the running sums, the pose, the cell.  The host launches a block
+// for every chunk the BOUND on the points asks for (it never learns their number); a block past the last point has
+// nothing to do.  Write == false: chunk_n[chunk] = points of the chunk whose cell lies inside the grid, entry gridDim.x is
+// 0 (the scan turns it into the total), and box (x0 y0 z0 x1 y1 z1) grows to hold those cells.  Write == true: chunk_n
+// holds the exclusive scan; the cells go to cells[chunk_n[chunk] + rank], in generation order (each wavefront ranks its
+// cells by ballot).
+template <bool Write>
+__global__ void __launch_bounds__(FIELD_BLOCK)
+k_oct_points(const double* __restrict__ leaves, const int* __restrict__ trips, const long long* __restrict__ first, int nleaves, OctGrid G,
+             long long* __restrict__ chunk_n, int* __restrict__ cells, int* __restrict__ box)
+{
+    __shared__ int wave_n[FIELD_BLOCK / 64];
+    __shared__ int sbox[6];
+    const long long total = first[nleaves];
+    const long long begin = (long long)blockIdx.x * OCT_CHUNK;
+    if (!Write && blockIdx.x == 0 && threadIdx.x == 0) chunk_n[gridDim.x] = 0;
+    if (begin >= total) {                                  // the whole block alike
+        if (!Write && threadIdx.x == 0) chunk_n[blockIdx.x] = 0;
+        return;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (!Write && threadIdx.x < 6) sbox[threadIdx.x] = threadIdx.x < 3 ? INT_MAX : INT_MIN;
+    const long long p = begin + threadIdx.x;
+    int c[3] = {-1, -1, -1};
+    if (p < total) {
+        int lo = 0, hi = nleaves;                          // first[lo] <= p < first[hi]; leaves without points are passed over
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (first[mid] <= p) lo = mid; else hi = mid;
+        }
+        const double* L = leaves + 4 * (size_t)lo;
+        const int* t = trips + 3 * (size_t)lo;
+        const long long local = p - first[lo];
+        const int k[3] = {(int)(local / ((long long)t[2] * t[1])), (int)(local / t[2] % t[1]), (int)(local % t[2])};
+        const double v[3] = {oct_axis_value(L[0], L[3], G.res, k[0]), oct_axis_value(L[1], L[3], G.res, k[1]), oct_axis_value(L[2], L[3], G.res, k[2])};
+        double w[3];
+        vox_transform(G.pose, v, w);
+        for (int a = 0; a < 3; ++a) c[a] = oct_world_to_cell(w[a], G.origin_minus_res[a], G.inv_res);
+    }
+    const bool on = c[0] >= 0 && c[1] >= 0 && c[2] >= 0 && c[0] < G.n[0] && c[1] < G.n[1] && c[2] < G.n[2];
+    const unsigned long long b = __ballot(on);
+    if (lane == 0) wave_n[wave] = __popcll(b);
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int w = 0; w < FIELD_BLOCK / 64; ++w) { before += w < wave ? wave_n[w] : 0; all += wave_n[w]; }
+    if (Write) {
+        if (on) {
+            int* out = cells + 3 * (size_t)(chunk_n[blockIdx.x] + before + __popcll(b & ((1ull << lane) - 1ull)));
+            out[0] = c[0]; out[1] = c[1]; out[2] = c[2];
+        }
+        return;
+    }
+    if (on)
+        for (int a = 0; a < 3; ++a) { atomicMin(&sbox[a], c[a]); atomicMax(&sbox[3 + a], c[a]); }
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_n[blockIdx.x] = all;
+    if (threadIdx.x < 6) {
+        if (threadIdx.x < 3) atomicMin(&box[threadIdx.x], sbox[threadIdx.x]); else atomicMax(&box[threadIdx.x], sbox[threadIdx.x]);
+    }
+}
+
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
@@ -219,7 +343,7 @@ void shape_mesh(const WorldShape& s, Mesh& m)
     // TransformVertices (voxelize.cpp:608-615): R v + t
     for (size_t i = 0; i + 2 < m.v.size(); i += 3) {
         const double v[3] = {m.v[i], m.v[i + 1], m.v[i + 2]};
-        for (int r = 0; r < 3; ++r) m.v[i + r] = vox_dot(s.pose + 4 * r, v) + s.pose[4 * r + 3];
+        vox_transform(s.pose, v, &m.v[i]);
     }
 }
 
@@ -237,14 +361,23 @@ int take_shapes(const smplx_shape* shapes, int n, std::vector<WorldShape>& out)
         case SMPLX_SHAPE_BOX: nd = 3; break;
         case SMPLX_SHAPE_SPHERE: nd = 1; break;
         case SMPLX_SHAPE_CYLINDER: case SMPLX_SHAPE_CONE: nd = 2; break;
-        case SMPLX_SHAPE_MESH: nd = 0; break;
-        default: return smplx_internal_set_error(SMPLX_E_ARG, "unknown shape type (planes and octomaps are not supported)");
+        case SMPLX_SHAPE_MESH: case SMPLX_SHAPE_OCTREE: nd = 0; break;
+        default: return smplx_internal_set_error(SMPLX_E_ARG, "unknown shape type (planes are not supported)");
         }
         for (int k = 0; k < 3; ++k) w.dims[k] = k < nd ? s.dims[k] : 0.0;
         if (!finite_coords(w.dims, 3) || !finite_coords(s.pose, 12)) return smplx_internal_set_error(SMPLX_E_ARG, "shape dimensions and pose must be finite (|x| < 1e6)");
         for (int k = 0; k < nd; ++k)
             if (!(w.dims[k] > 0.0)) return smplx_internal_set_error(SMPLX_E_ARG, "shape dimensions must be positive");
         std::memcpy(w.pose, s.pose, sizeof(w.pose));
+        if (s.type == SMPLX_SHAPE_OCTREE) {
+            if (!s.vertices || s.nvertices < 1 || s.triangles || s.ntriangles != 0)
+                return smplx_internal_set_error(SMPLX_E_ARG, "an octree needs leaves (vertices: rows of cx cy cz size) and takes no triangles");
+            if (!finite_coords(s.vertices, (size_t)s.nvertices * 4)) return smplx_internal_set_error(SMPLX_E_ARG, "octree leaves must be finite (|x| < 1e6)");
+            for (size_t k = 0; k < (size_t)s.nvertices; ++k)
+                if (!(s.vertices[4 * k + 3] > 0.0)) return smplx_internal_set_error(SMPLX_E_ARG, "the size of an octree leaf must be positive");
+            w.vertices.assign(s.vertices, s.vertices + (size_t)s.nvertices * 4);
+            continue;
+        }
         if (s.type != SMPLX_SHAPE_MESH) continue;
         if (!s.vertices || !s.triangles || s.nvertices < 1 || s.ntriangles < 1) return smplx_internal_set_error(SMPLX_E_ARG, "a mesh needs vertices and triangles");
         if (!finite_coords(s.vertices, (size_t)s.nvertices * 3)) return smplx_internal_set_error(SMPLX_E_ARG, "mesh vertices must be finite (|x| < 1e6)");
@@ -366,7 +499,6 @@ int voxelize_meshes(void** work, size_t* work_bytes, const VoxLattice& L, const 
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     if (g_vox_timing) { for (hipEvent_t& e : ev) FIELD_TRY(hipEventCreate(&e)); FIELD_TRY(hipEventRecord(ev[0], 0)); }
     struct EvFree { hipEvent_t* e; ~EvFree() { for (int i = 0; i < 4; ++i) if (e[i]) (void)hipEventDestroy(e[i]); } } ev_free{ev};
-    g_vox_kernel_ms = 0.0;
     hipLaunchKernelGGL(k_vox_setup, dim3((ntri + FIELD_BLOCK - 1) / FIELD_BLOCK), dim3(FIELD_BLOCK), 0, 0, (const double*)d_verts.p, (const VoxItem*)d_items.p,
                        ntri, L.res, (VoxTri*)d_tris.p);
     hipLaunchKernelGGL(k_vox_fill, dim3(blocks_of((size_t)first.back())), dim3(FIELD_BLOCK), 0, 0, (const VoxTri*)d_tris.p, (const long long*)d_first.p,
@@ -402,25 +534,208 @@ int voxelize_meshes(void** work, size_t* work_bytes, const VoxLattice& L, const 
         float a = 0.f, b = 0.f;
         FIELD_TRY(hipEventElapsedTime(&a, ev[0], ev[1]));
         FIELD_TRY(hipEventElapsedTime(&b, ev[2], ev[3]));
-        g_vox_kernel_ms = (double)a + (double)b;
+        g_vox_kernel_ms += (double)a + (double)b;
     }
     out.d_cells = (int32_t*)d_cells.p;
     d_cells.p = nullptr;
     return SMPLX_OK;
 }
 
+// the limits of octree_points.h over the octree shapes of one call, checked before anything is allocated or launched
+int octree_limits(const std::vector<WorldShape>& shapes, double res)
+{
+    long long bound = 0, leaves = 0;
+    for (const WorldShape& s : shapes) {
+        if (s.type != SMPLX_SHAPE_OCTREE) continue;
+        leaves += (long long)(s.vertices.size() / 4);
+        if (leaves > OCT_MAX_LEAVES) return smplx_internal_set_error(SMPLX_E_LIMIT, "more than 2^28 octree leaves in one call");
+        for (size_t k = 3; k < s.vertices.size(); k += 4) {
+            if (!(s.vertices[k] / res <= OCT_MAX_RATIO)) return smplx_internal_set_error(SMPLX_E_LIMIT, "an octree leaf is wider than 1024 cells of the grid");
+            const long long b = oct_axis_bound(s.vertices[k], res);
+            bound += b * b * b;
+            if (bound > OCT_MAX_POINTS) return smplx_internal_set_error(SMPLX_E_LIMIT, "the octree leaves may sample more than 2^31 / 3 points at this resolution");
+        }
+    }
+    return SMPLX_OK;
+}
+
+// entries of scratch an exclusive scan of n entries needs: the tile totals of every level
+size_t scan_scratch(size_t n)
+{
+    size_t total = 0;
+    do { n = (n + FIELD_BLOCK - 1) / FIELD_BLOCK; total += n; } while (n > 1);
+    return total;
+}
+
+// exclusive scan of v[0 .. n) in place on the device: tiles of FIELD_BLOCK, their totals scanned the same way, added back.
+// With trips, v is first filled with the leaves' points (k_scan_tiles).
+void scan_exclusive(long long* v, int n, long long* scratch, const int* trips = nullptr)
+{
+    const int tiles = (n + FIELD_BLOCK - 1) / FIELD_BLOCK;
+    hipLaunchKernelGGL(k_scan_tiles, dim3(tiles), dim3(FIELD_BLOCK), 0, 0, v, n, scratch, trips);
+    if (tiles == 1) return;
+    scan_exclusive(scratch, tiles, scratch + tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3(tiles), dim3(FIELD_BLOCK), 0, 0, v, n, (const long long*)scratch);
+}
+
+// with the test hook on, the time between begin() and end() is added to g_vox_kernel_ms; end() also reports launch errors
+struct VoxTimer {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~VoxTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t begin()
+    {
+        if (!g_vox_timing) return hipSuccess;
+        if (!a) { if (hipError_t e = hipEventCreate(&a)) return e; if (hipError_t e = hipEventCreate(&b)) return e; }
+        return hipEventRecord(a, 0);
+    }
+    hipError_t end()
+    {
+        if (hipError_t e = hipGetLastError()) return e;
+        if (!g_vox_timing) return hipSuccess;
+        if (hipError_t e = hipEventRecord(b, 0)) return e;
+        if (hipError_t e = hipEventSynchronize(b)) return e;
+        float ms = 0.f;
+        if (hipError_t e = hipEventElapsedTime(&ms, a, b)) return e;
+        g_vox_kernel_ms += (double)ms;
+        return hipSuccess;
+    }
+};
+
+struct OctList {
+    int32_t* d_cells = nullptr;       // owned by the caller after a successful run
+    int n = 0;
+    int box[6] = {0, 0, 0, -1, -1, -1};
+};
+
+// the cell list of one octree shape (VoxelizeOcTree, voxel_operations.cpp:405-436, then worldToGrid): the cells of its
+// sample points that lie inside the grid, in generation order, duplicates kept.  The leaves' trips, the prefix of their
+// point counts and the chunk counts of the compaction live in the grid's work space; the only allocation is the list.
+// One upload (the leaf rows) and one download (the number of cells and their bounding range, 32 bytes): the number of
+// sample points stays on the device, the chunks being launched for their bound.  With occ the cells also become
+// obstacles through k_occ_points (the caller updates the field).  Waits for the device.
+int octree_run(const smplx_grid* g, const WorldShape& s, unsigned char* occ, int* counts, OctList& out)
+{
+    const int nl = (int)(s.vertices.size() / 4);
+    long long bound = 0;                               // octree_limits has held it to OCT_MAX_POINTS
+    for (size_t k = 3; k < s.vertices.size(); k += 4) { const long long b = oct_axis_bound(s.vertices[k], g->res); bound += b * b * b; }
+    const int nchunks = (int)((bound + OCT_CHUNK - 1) / OCT_CHUNK);
+    struct Found { long long ncells; int box[6]; } found;      // as they lie behind the chunk counts
+    const size_t bytes[5] = {sizeof(double) * 4 * (size_t)nl, sizeof(int) * 3 * (size_t)nl, sizeof(long long) * ((size_t)nl + 1),
+                             sizeof(long long) * (size_t)nchunks + sizeof(Found), sizeof(long long) * scan_scratch((size_t)std::max(nl, nchunks) + 1)};
+    size_t at[5], need = 0;
+    for (int i = 0; i < 5; ++i) { at[i] = need; need += (bytes[i] + 255) & ~(size_t)255; }
+    if (need > g->vox_bytes) {
+        if (g->d_vox) (void)hipFree(g->d_vox);
+        g->d_vox = nullptr; g->vox_bytes = 0;
+        FIELD_TRY(hipMalloc(&g->d_vox, need));
+        g->vox_bytes = need;
+    }
+    char* const base = (char*)g->d_vox;
+    double* const d_leaves = (double*)(base + at[0]);
+    int* const d_trips = (int*)(base + at[1]);
+    long long* const d_first = (long long*)(base + at[2]);
+    long long* const d_chunk = (long long*)(base + at[3]);
+    long long* const d_scratch = (long long*)(base + at[4]);
+    int* const d_box = (int*)(d_chunk + nchunks + 1);
+    OctGrid G;
+    std::memcpy(G.pose, s.pose, sizeof(G.pose));
+    for (int a = 0; a < 3; ++a) { G.origin_minus_res[a] = g->dev.origin_minus_res[a]; G.n[a] = g->n[a]; }
+    G.inv_res = g->dev.inv_res; G.res = g->res;
+    FIELD_TRY(hipMemcpy(d_leaves, s.vertices.data(), bytes[0], hipMemcpyHostToDevice));
+    VoxTimer timer;
+    // 1. every leaf's trips, the prefix of the leaves' points, the in-grid points of every chunk and their prefix
+    FIELD_TRY(timer.begin());
+    hipLaunchKernelGGL(k_oct_trips, dim3((3 * nl + FIELD_BLOCK - 1) / FIELD_BLOCK), dim3(FIELD_BLOCK), 0, 0, (const double*)d_leaves, nl, g->res, d_trips, d_box);
+    scan_exclusive(d_first, nl + 1, d_scratch, d_trips);
+    hipLaunchKernelGGL(k_oct_points<false>, dim3(nchunks), dim3(FIELD_BLOCK), 0, 0, (const double*)d_leaves, (const int*)d_trips, (const long long*)d_first, nl, G,
+                       d_chunk, (int*)nullptr, d_box);
+    scan_exclusive(d_chunk, nchunks + 1, d_scratch);
+    FIELD_TRY(timer.end());
+    FIELD_TRY(hipMemcpy(&found, d_chunk + nchunks, sizeof(found), hipMemcpyDeviceToHost));
+    if (found.ncells <= 0) return SMPLX_OK;
+    if (found.ncells > bound) return smplx_internal_set_error(SMPLX_E_HIP, "octree: more cells than the bound on the sample points");
+    // 2. the list, and with occ its cells as obstacles
+    DevBuf d_cells;
+    FIELD_TRY(d_cells.alloc(sizeof(int32_t) * 3 * (size_t)found.ncells));
+    FIELD_TRY(timer.begin());
+    hipLaunchKernelGGL(k_oct_points<true>, dim3(nchunks), dim3(FIELD_BLOCK), 0, 0, (const double*)d_leaves, (const int*)d_trips, (const long long*)d_first, nl, G,
+                       d_chunk, (int*)d_cells.p, (int*)nullptr);
+    if (occ)
+        hipLaunchKernelGGL(k_occ_points, dim3((unsigned)((found.ncells + FIELD_BLOCK - 1) / FIELD_BLOCK)), dim3(FIELD_BLOCK), 0, 0, occ, counts, g->n[0], g->n[1],
+                           g->n[2], (const int*)d_cells.p, (int)found.ncells, 1);
+    FIELD_TRY(timer.end());
+    FIELD_TRY(hipDeviceSynchronize());
+    out.n = (int)found.ncells;
+    std::copy(found.box, found.box + 6, out.box);
+    out.d_cells = (int32_t*)d_cells.p;
+    d_cells.p = nullptr;
+    return SMPLX_OK;
+}
+
 // voxelises the shapes on the grid's lattice: the pivot is the grid's origin and the candidates are clipped to the grid.
-// With occ the cells also become obstacles (an edit; the caller updates the field).  Waits for the device.
+// Meshes and the shapes that become meshes go through voxelize_meshes together, every octree through octree_run; with
+// both kinds in one call the lists are then laid back to back in shape order.  With occ the cells also become obstacles
+// (an edit; the caller updates the field).  Waits for the device.
 int voxelize_run(const smplx_grid* g, const std::vector<WorldShape>& shapes, unsigned char* occ, int* counts, VoxLists& out)
 {
-    std::vector<Mesh> meshes(shapes.size());
+    const size_t ns = shapes.size();
+    std::vector<Mesh> meshes;
     std::vector<int> clip;
-    for (size_t s = 0; s < shapes.size(); ++s) {
-        shape_mesh(shapes[s], meshes[s]);
+    for (size_t s = 0; s < ns; ++s) {
+        if (shapes[s].type == SMPLX_SHAPE_OCTREE) continue;
+        meshes.emplace_back();
+        shape_mesh(shapes[s], meshes.back());
         clip.insert(clip.end(), {0, 0, 0, g->n[0] - 1, g->n[1] - 1, g->n[2] - 1});
     }
     const VoxLattice L{{g->origin[0], g->origin[1], g->origin[2]}, g->res, false};
-    return voxelize_meshes(&g->d_vox, &g->vox_bytes, L, meshes, clip, occ, counts, g->n[1], g->n[2], out);
+    g_vox_kernel_ms = 0.0;
+    if (meshes.size() == ns) return voxelize_meshes(&g->d_vox, &g->vox_bytes, L, meshes, clip, occ, counts, g->n[1], g->n[2], out);
+    if (int e = octree_limits(shapes, g->res)) return e;
+    VoxLists part;
+    DevBuf mesh_cells;
+    if (!meshes.empty()) {
+        if (int e = voxelize_meshes(&g->d_vox, &g->vox_bytes, L, meshes, clip, occ, counts, g->n[1], g->n[2], part)) return e;
+        mesh_cells.p = part.d_cells;
+    }
+    std::vector<OctList> octs(ns);
+    std::vector<DevBuf> oct_cells(ns);
+    out.first.assign(ns + 1, 0);
+    out.box.assign(ns * 6, 0);
+    long long total = 0;
+    for (size_t s = 0, m = 0; s < ns; ++s) {
+        int n = 0;
+        if (shapes[s].type == SMPLX_SHAPE_OCTREE) {
+            if (int e = octree_run(g, shapes[s], occ, counts, octs[s])) return e;
+            oct_cells[s].p = octs[s].d_cells;
+            n = octs[s].n;
+            std::copy(octs[s].box, octs[s].box + 6, &out.box[6 * s]);
+        } else {
+            n = part.first[m + 1] - part.first[m];
+            std::copy(&part.box[6 * m], &part.box[6 * m] + 6, &out.box[6 * s]);
+            ++m;
+        }
+        total += n;
+        if (total > INT_MAX / 3) return smplx_internal_set_error(SMPLX_E_LIMIT, "too many cells in one call");
+        out.first[s + 1] = (int)total;
+    }
+    if (total == 0) return SMPLX_OK;
+    if (ns == 1) {                                     // one octree: its list is the call's
+        out.d_cells = octs[0].d_cells;
+        oct_cells[0].p = nullptr;
+        return SMPLX_OK;
+    }
+    DevBuf d_cells;
+    FIELD_TRY(d_cells.alloc(sizeof(int32_t) * 3 * (size_t)total));
+    for (size_t s = 0, m = 0; s < ns; ++s) {
+        const bool oct = shapes[s].type == SMPLX_SHAPE_OCTREE;
+        const int32_t* from = oct ? octs[s].d_cells : part.d_cells + 3 * (size_t)part.first[m];
+        const int n = out.first[s + 1] - out.first[s];
+        if (!oct) ++m;
+        if (n > 0) FIELD_TRY(hipMemcpy((int32_t*)d_cells.p + 3 * (size_t)out.first[s], from, sizeof(int32_t) * 3 * (size_t)n, hipMemcpyDeviceToDevice));
+    }
+    out.d_cells = (int32_t*)d_cells.p;
+    d_cells.p = nullptr;
+    return SMPLX_OK;
 }
 
 // the sphere model of an attached object (generateSpheresModel, attached_bodies_collision_model.cpp:264-313): every
@@ -444,6 +759,7 @@ int object_spheres_run(void** work, size_t* work_bytes, const std::vector<WorldS
     }
     const VoxLattice L{{0.0, 0.0, 0.0}, res, false};
     VoxLists lists;
+    g_vox_kernel_ms = 0.0;
     if (int e = voxelize_meshes(work, work_bytes, L, meshes, clip, nullptr, nullptr, 0, 0, lists)) return e;
     DevBuf d_cells;
     d_cells.p = lists.d_cells;
@@ -473,8 +789,9 @@ void remove_lists(smplx_grid* g, const WorldObject& o, Window& box)
     for (size_t s = 0; s + 1 < o.first.size(); ++s) {
         const int n = o.first[s + 1] - o.first[s];
         if (n <= 0) continue;
-        hipLaunchKernelGGL(k_occ_points, dim3(blocks_of((size_t)n)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2],
-                           (const int*)(o.d_cells + 3 * (size_t)o.first[s]), n, 0);
+        // one thread per cell: an octree's list can hold more cells than blocks_of() gives threads
+        hipLaunchKernelGGL(k_occ_points, dim3((unsigned)(((size_t)n + FIELD_BLOCK - 1) / FIELD_BLOCK)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1],
+                           g->n[2], (const int*)(o.d_cells + 3 * (size_t)o.first[s]), n, 0);
         const int* b = &o.box[6 * s];
         box.x0 = std::min(box.x0, b[0]); box.y0 = std::min(box.y0, b[1]); box.z0 = std::min(box.z0, b[2]);
         box.x1 = std::max(box.x1, b[3]); box.y1 = std::max(box.y1, b[4]); box.z1 = std::max(box.z1, b[5]);
@@ -486,6 +803,7 @@ const char* const kNotEditable = "the grid was created from a finished field (sm
 // insert (old < 0) or move: remove the old lists, voxelise and add the new ones, update the field once
 int put_object(smplx_grid* g, const char* id, int old, std::vector<WorldShape>& shapes)
 {
+    if (int e = octree_limits(shapes, g->res)) return e;      // before the old lists go: a refused call changes nothing
     Window box{1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
     if (old >= 0) remove_lists(g, g->objects[(size_t)old], box);
     VoxLists lists;
@@ -512,7 +830,8 @@ int put_object(smplx_grid* g, const char* id, int old, std::vector<WorldShape>& 
 
 extern "C" {
 
-// test hooks, not part of the ABI: time of the three voxelisation launches of the last call, in milliseconds
+// test hooks, not part of the ABI: time of the voxelisation launches of the last call (an octree's k_occ_points
+// included), in milliseconds
 void smplx_test_voxelize_timing(int on) { g_vox_timing = on != 0; }
 double smplx_test_voxelize_kernel_ms(void) { return g_vox_kernel_ms; }
 
@@ -619,6 +938,8 @@ int smplx_internal_object_spheres(void** work, size_t* work_bytes, const smplx_s
 {
     std::vector<WorldShape> ws;
     if (int e = take_shapes(shapes, n, ws)) return e;
+    for (const WorldShape& w : ws)
+        if (w.type == SMPLX_SHAPE_OCTREE) return smplx_internal_set_error(SMPLX_E_ARG, "octrees cannot be attached: an attached object has no octree shapes");
     if (!(radius > 0.0 && radius < 1.0e6)) return smplx_internal_set_error(SMPLX_E_ARG, "the sphere radius must be positive and finite (< 1e6)");
     return object_spheres_run(work, work_bytes, ws, radius, *rows, *first);
 }

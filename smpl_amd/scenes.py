@@ -274,6 +274,41 @@ def build_grid(origin, dims, res, max_dist, boxes) -> Grid:
     return Grid(tuple(origin), tuple(dims), res, max_dist, np.ascontiguousarray(d2[1:-1, 1:-1, 1:-1]))
 
 
+def octree_leaves(points, res: float, depth: int = 16) -> np.ndarray:
+    """The occupied leaves of a pruned octree over a point cloud, as the rows capi.octree takes: n x {cx, cy, cz, size}.
+
+    The octomap convention: a point has the key floor(x / res) per axis at the finest level, the tree spans the keys
+    [-2^(depth-1), 2^(depth-1)) about the origin, and the finest leaf of key k is centred on (k + 0.5) * res.  Eight
+    occupied siblings merge into their parent (edge 2 res), repeatedly.  Rows come in depth-first order, children 0..7
+    with x in bit 0, y in bit 1 and z in bit 2 of the child index -- the order begin_leafs() walks such a tree.
+    A convenience and a test generator: it reads no octomap file."""
+    half = 1 << (depth - 1)
+    keys = np.floor(np.asarray(points, dtype=np.float64).reshape(-1, 3) / res).astype(np.int64) + half
+    if keys.size and (keys.min() < 0 or keys.max() >= 2 * half):
+        raise ValueError("a point lies outside the octree: |x| must stay below 2^(depth-1) * res")
+    level = {tuple(int(v) for v in k) for k in keys}
+    found = []                                     # (level, x, y, z), indices at that level
+    for lv in range(depth + 1):
+        siblings = {}
+        for (x, y, z) in level:
+            siblings[(x >> 1, y >> 1, z >> 1)] = siblings.get((x >> 1, y >> 1, z >> 1), 0) + 1
+        full = {p for p, c in siblings.items() if c == 8} if lv < depth else set()
+        found += [(lv, x, y, z) for (x, y, z) in level if (x >> 1, y >> 1, z >> 1) not in full]
+        level = full
+
+    def morton(node):                              # of the node's lowest finest cell: z, y, x from the top bit down
+        lv, x, y, z = node
+        code = 0
+        for b in range(depth - 1, -1, -1):
+            code = (code << 3) | ((((z << lv) >> b) & 1) << 2) | ((((y << lv) >> b) & 1) << 1) | (((x << lv) >> b) & 1)
+        return code
+
+    found.sort(key=morton)
+    rows = [[((x + 0.5) * (1 << lv) - half) * res, ((y + 0.5) * (1 << lv) - half) * res, ((z + 0.5) * (1 << lv) - half) * res, (1 << lv) * res]
+            for (lv, x, y, z) in found]
+    return np.asarray(rows, dtype=np.float64).reshape(-1, 4)
+
+
 def random_boxes(rng: np.random.Generator, n, origin, dims, res, keep_clear, clear_radius, edge=(0.05, 0.30)):
     """n random boxes, rejecting those within clear_radius of any keep_clear point."""
     size = np.asarray(dims) * res
