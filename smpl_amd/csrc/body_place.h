@@ -1,5 +1,5 @@
 // smpl_amd/csrc/body_place.h -- the robot body on a grid (include/smpl_amd.h "robot body"), the tail of field.hip behind
-// world_objects.h: the voxel models of a body's links (built once, by the voxeliser's kernels on the HalfRes lattice), the
+// world_objects.h: the voxel models of a body's links (built once, by mesh_voxelizer.h on the HalfRes lattice), the
 // kernel that places them under the current link transforms, and the bookkeeping of updateVoxelsStates.  Reference:
 // sbpl_collision_checking/src/robot_collision_model.cpp:959-1073 (voxelizeLink), smpl/src/geometry/voxelize.cpp:962-986
 // (the gridless VoxelizeMesh), include/sbpl_collision_checking/robot_collision_state.h:473-497 (updateVoxelsState),
@@ -9,13 +9,14 @@
 // k_body_place: one thread per point of all states placed by one put.  The thread finds its state by a search over the
 // prefix (as k_vox_fill finds its triangle), reads the state's 12 doubles from memory (a wavefront inside one state reads
 // one address), evaluates p = T v as Affine3d * Vector3d is evaluated elsewhere (row dot product a0 b0 + (a1 b1 + a2 b2),
-// then the translation), applies the point rule (world_to_cell) and writes the cell, or (-1, -1, -1) -- which k_occ_points
+// then the translation), applies the point rule (world_to_cell) and writes the cell, or (-1, -1, -1) -- which occ_points
 // skips -- for a point outside the grid.  Each state's bounding cell range is reduced per wavefront by shuffles and
 // finished with atomicMin / atomicMax on six ints; a wavefront that straddles two states lets its lanes do their own.
 #pragma once
 
 #include <cstdint>
 
+#include "mesh_voxelizer.h"
 #include "robot_body.h"
 
 struct smplx_body {
@@ -23,7 +24,7 @@ struct smplx_body {
     uint64_t serial = 0;
     std::vector<int> point_first;     // models + 1: model m's points are [point_first[m], point_first[m + 1])
     std::vector<double> points;       // link-frame points of all models, back to back
-    double* d_points = nullptr;       // the same on the device
+    DevPtr<double> d_points;          // the same on the device
 };
 
 namespace {
@@ -98,21 +99,10 @@ int body_model_meshes(const smplx_body_host::Body& rec, int link, double res, st
         if (g.link != link) continue;
         meshes.emplace_back();
         Mesh& m = meshes.back();
-        switch (g.type) {
-        case SMPLX_SHAPE_BOX: box_mesh(g.dims[0], g.dims[1], g.dims[2], m); break;
-        case SMPLX_SHAPE_SPHERE: sphere_mesh(g.dims[0], 7, 8, m); break;
-        case SMPLX_SHAPE_CYLINDER: cylinder_mesh(g.dims[0], g.dims[1], m); break;
-        default: m.v = g.v; m.t = g.t; break;
-        }
+        if (!primitive_mesh(g.type, g.dims, m)) { m.v = g.v; m.t = g.t; }
+        transform_vertices(g.origin, m);
         double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
-        for (size_t i = 0; i + 2 < m.v.size(); i += 3) {   // TransformVertices (voxelize.cpp:608-615): R v + t
-            const double v[3] = {m.v[i], m.v[i + 1], m.v[i + 2]};
-            for (int r = 0; r < 3; ++r) {
-                const double w = vox_dot(g.origin + 4 * r, v) + g.origin[4 * r + 3];
-                m.v[i + r] = w;
-                mn[r] = std::min(mn[r], w); mx[r] = std::max(mx[r], w);
-            }
-        }
+        for (size_t i = 0; i < m.v.size(); ++i) { mn[i % 3] = std::min(mn[i % 3], m.v[i]); mx[i % 3] = std::max(mx[i % 3], m.v[i]); }
         // VoxelGrid(origin = min, size = max - min) (voxel_grid.h:187-193): discretize(min) .. discretize(min + size)
         long long cells = 1;
         for (int a = 0; a < 3; ++a) {
@@ -136,8 +126,7 @@ int body_build_models(smplx_body* b)
     const int nm = (int)rec.models.size();
     std::vector<std::vector<double>> pts((size_t)nm);
     std::vector<unsigned char> done((size_t)nm, 0);
-    DevBuf work;
-    size_t work_bytes = 0;
+    WorkSpace work;
     for (int m0 = 0; m0 < nm; ++m0) {
         if (done[(size_t)m0]) continue;
         const double res = rec.models[(size_t)m0].res;
@@ -153,9 +142,7 @@ int body_build_models(smplx_body* b)
         if (meshes.empty()) continue;
         VoxLists lists;
         const VoxLattice L{{0.5 * res, 0.5 * res, 0.5 * res}, res, true};
-        if (int e = voxelize_meshes(&work.p, &work_bytes, L, meshes, clip, nullptr, nullptr, 0, 0, lists)) return e;
-        DevBuf cells_owner;
-        cells_owner.p = lists.d_cells;
+        if (int e = voxelize_meshes(work, L, meshes, clip, nullptr, nullptr, 0, 0, lists)) return e;
         const int total = lists.first.back();
         std::vector<int32_t> cells(3 * (size_t)total);
         if (total > 0) FIELD_TRY(hipMemcpy(cells.data(), lists.d_cells, sizeof(int32_t) * cells.size(), hipMemcpyDeviceToHost));
@@ -173,36 +160,17 @@ int body_build_models(smplx_body* b)
         b->point_first[(size_t)m + 1] = (int)(b->points.size() / 3);
     }
     if (!b->points.empty()) {
-        FIELD_TRY(hipMalloc((void**)&b->d_points, sizeof(double) * b->points.size()));
+        FIELD_TRY(b->d_points.alloc(b->points.size()));
         FIELD_TRY(hipMemcpy(b->d_points, b->points.data(), sizeof(double) * b->points.size(), hipMemcpyHostToDevice));
     }
     return SMPLX_OK;
-}
-
-void free_grid_body(smplx_grid* g)
-{
-    GridBody* gb = g->body;
-    if (!gb) return;
-    if (gb->d_cells) (void)hipFree(gb->d_cells);
-    if (gb->d_points) (void)hipFree(gb->d_points);
-    if (gb->d_states) (void)hipFree(gb->d_states);
-    delete gb;
-    g->body = nullptr;
-}
-
-void grow_box(Window& box, const int* b)
-{
-    if (b[3] < b[0]) return;
-    box.x0 = std::min(box.x0, b[0]); box.y0 = std::min(box.y0, b[1]); box.z0 = std::min(box.z0, b[2]);
-    box.x1 = std::max(box.x1, b[3]); box.y1 = std::max(box.y1, b[4]); box.z1 = std::max(box.z1, b[5]);
 }
 
 // the grid's record of a body: lists for the outside models, its own copy of the points
 int make_grid_body(smplx_grid* g, const smplx_body* b)
 {
     const int nm = (int)b->rec.models.size();
-    GridBody* gb = new GridBody;
-    g->body = gb;
+    std::unique_ptr<GridBody> gb(new GridBody);
     gb->serial = b->serial;
     gb->first.assign((size_t)nm + 1, 0);
     for (int m = 0; m < nm; ++m)
@@ -212,14 +180,12 @@ int make_grid_body(smplx_grid* g, const smplx_body* b)
     gb->box.assign((size_t)nm * 6, 0);
     for (int m = 0; m < nm; ++m) gb->box[6 * (size_t)m + 3] = -1;
     gb->point_first = b->point_first;
-    hipError_t e = hipSuccess;
-    if (gb->first.back() > 0) e = hipMalloc((void**)&gb->d_cells, sizeof(int32_t) * 3 * 2 * (size_t)gb->first.back());
-    if (e == hipSuccess && !b->points.empty()) e = hipMalloc((void**)&gb->d_points, sizeof(double) * b->points.size());
-    if (e == hipSuccess && !b->points.empty()) e = hipMemcpy(gb->d_points, b->d_points, sizeof(double) * b->points.size(), hipMemcpyDeviceToDevice);
-    if (e != hipSuccess) {
-        free_grid_body(g);
-        return smplx_internal_set_error(SMPLX_E_HIP, (std::string("body placement: ") + hipGetErrorString(e)).c_str());
+    if (gb->first.back() > 0) FIELD_TRY(gb->d_cells.alloc(3 * 2 * (size_t)gb->first.back()));
+    if (!b->points.empty()) {
+        FIELD_TRY(gb->d_points.alloc(b->points.size()));
+        FIELD_TRY(hipMemcpy(gb->d_points, b->d_points, sizeof(double) * b->points.size(), hipMemcpyDeviceToDevice));
     }
+    g->body = std::move(gb);
     return SMPLX_OK;
 }
 
@@ -244,8 +210,6 @@ int smplx_body_create(const char* body_text, smplx_body** out)
 
 void smplx_body_destroy(smplx_body* b)
 {
-    if (!b) return;
-    if (b->d_points) (void)hipFree(b->d_points);
     delete b;
 }
 
@@ -326,7 +290,7 @@ int smplx_grid_put_body(smplx_grid* g, smplx_body* b)
     if (todo.empty()) return SMPLX_OK;
     if (!g->body)
         if (int e = make_grid_body(g, b)) return e;
-    GridBody* gb = g->body;
+    GridBody* gb = g->body.get();
     const long long half_cells = gb->first.back();
 
     std::vector<double> T(12 * rec.links.size());
@@ -348,35 +312,25 @@ int smplx_grid_put_body(smplx_grid* g, smplx_body* b)
     std::vector<int> boxes((size_t)ns * 6);
     for (int s = 0; s < ns; ++s)
         for (int a = 0; a < 3; ++a) { boxes[6 * (size_t)s + a] = INT_MAX; boxes[6 * (size_t)s + 3 + a] = INT_MIN; }
-    Window box{1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
+    Window box = empty_box();
     if (ns > 0) {
         const size_t bytes[3] = {sizeof(PlaceState) * (size_t)ns, sizeof(int) * first.size(), sizeof(int) * boxes.size()};
-        size_t at[3], need = 0;
-        for (int i = 0; i < 3; ++i) { at[i] = need; need += (bytes[i] + 255) & ~(size_t)255; }
-        if (need > gb->states_bytes) {
-            if (gb->d_states) (void)hipFree(gb->d_states);
-            gb->d_states = nullptr; gb->states_bytes = 0;
-            FIELD_TRY(hipMalloc(&gb->d_states, need));
-            gb->states_bytes = need;
-        }
-        char* const base = (char*)gb->d_states;
+        size_t at[3];
+        FIELD_TRY(gb->states.carve(bytes, at));
+        char* const base = gb->states.base;
         FIELD_TRY(hipMemcpy(base + at[0], states.data(), bytes[0], hipMemcpyHostToDevice));
         FIELD_TRY(hipMemcpy(base + at[1], first.data(), bytes[1], hipMemcpyHostToDevice));
         FIELD_TRY(hipMemcpy(base + at[2], boxes.data(), bytes[2], hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_body_place, dim3(blocks_of((size_t)first.back())), dim3(FIELD_BLOCK), 0, 0, (const PlaceState*)(base + at[0]),
-                           (const int*)(base + at[1]), ns, (const double*)gb->d_points, (int*)gb->d_cells, (int*)(base + at[2]), g->dev.inv_res,
+                           (const int*)(base + at[1]), ns, (const double*)gb->d_points, gb->d_cells.p, (int*)(base + at[2]), g->dev.inv_res,
                            g->dev.origin_minus_res[0], g->dev.origin_minus_res[1], g->dev.origin_minus_res[2], g->n[0], g->n[1], g->n[2]);
         // updateVoxelsStates (self_collision_model.cpp:770-837), state by state: the old list out, the new one in
-        int* counts = g->ref_counted ? g->d_counts : nullptr;
         for (int s = 0; s < ns; ++s) {
             const int m = owner[(size_t)s], count = first[(size_t)s + 1] - first[(size_t)s];
             const int32_t* old_list = gb->d_cells + 3 * (gb->first[(size_t)m] + (gb->half[(size_t)m] ? half_cells : 0));
             const int32_t* new_list = gb->d_cells + 3 * states[(size_t)s].dst;
-            if (gb->placed[(size_t)m])
-                hipLaunchKernelGGL(k_occ_points, dim3(blocks_of((size_t)count)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2],
-                                   (const int*)old_list, count, 0);
-            hipLaunchKernelGGL(k_occ_points, dim3(blocks_of((size_t)count)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2],
-                               (const int*)new_list, count, 1);
+            if (gb->placed[(size_t)m]) occ_points(g, old_list, (size_t)count, 0, true);
+            occ_points(g, new_list, (size_t)count, 1, true);
         }
         FIELD_TRY(hipGetLastError());
         FIELD_TRY(hipMemcpy(boxes.data(), base + at[2], bytes[2], hipMemcpyDeviceToHost));
@@ -399,21 +353,19 @@ int smplx_grid_take_body(smplx_grid* g)
 {
     if (!g) return smplx_internal_set_error(SMPLX_E_ARG, "null grid");
     if (!g->d_occ) return smplx_internal_set_error(SMPLX_E_STATE, kNotEditable);
-    GridBody* gb = g->body;
+    GridBody* gb = g->body.get();
     if (!gb) return smplx_internal_set_error(SMPLX_E_STATE, "the grid holds no body");
     const long long half_cells = gb->first.back();
-    int* counts = g->ref_counted ? g->d_counts : nullptr;
-    Window box{1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
+    Window box = empty_box();
     for (size_t m = 0; m + 1 < gb->first.size(); ++m) {
         const int count = gb->first[m + 1] - gb->first[m];
         if (!gb->placed[m] || count == 0) continue;
-        hipLaunchKernelGGL(k_occ_points, dim3(blocks_of((size_t)count)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2],
-                           (const int*)(gb->d_cells + 3 * (gb->first[m] + (gb->half[m] ? half_cells : 0))), count, 0);
+        occ_points(g, gb->d_cells + 3 * (gb->first[m] + (gb->half[m] ? half_cells : 0)), (size_t)count, 0, true);
         grow_box(box, &gb->box[6 * m]);
     }
     FIELD_TRY(hipGetLastError());
     FIELD_TRY(hipDeviceSynchronize());
-    free_grid_body(g);
+    g->body.reset();
     if (box.x1 < 0) return SMPLX_OK;
     return field_update(g, edit_window(g, box));
 }
@@ -422,7 +374,7 @@ int smplx_grid_body_cells(const smplx_grid* g, int model, int32_t* cells, int ca
 {
     if (n) *n = 0;
     if (!g || !n || cap < 0 || (cap > 0 && !cells) || model < 0) return smplx_internal_set_error(SMPLX_E_ARG, "bad argument");
-    const GridBody* gb = g->body;
+    const GridBody* gb = g->body.get();
     if (!gb) return SMPLX_OK;
     if (model + 1 >= (int)gb->first.size()) return smplx_internal_set_error(SMPLX_E_ARG, "model index outside the body");
     if (!gb->placed[(size_t)model]) return SMPLX_OK;

@@ -160,7 +160,7 @@ int smplx_grid_create(const double origin[3], int nx, int ny, int nz, double res
                 const size_t brick = ((size_t)(x >> 2) * by + (y >> 2)) * bz + (z >> 2);
                 tiled[brick * 64 + ((x & 3) << 4) + ((y & 3) << 2) + (z & 3)] = (uint16_t)v;
             }
-    hipError_t e = hipMalloc((void**)&g->d_d2, tiled.size() * sizeof(uint16_t));
+    hipError_t e = g->d_d2.alloc(tiled.size());
     if (e == hipSuccess) e = hipMemcpy(g->d_d2, tiled.data(), tiled.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
     if (e != hipSuccess) { delete g; return set_error(SMPLX_E_HIP, std::string("grid upload: ") + hipGetErrorString(e)); }
     for (int a = 0; a < 3; ++a) { g->origin[a] = origin[a]; g->dev.origin_minus_res[a] = origin[a] - res; g->dev.n[a] = g->n[a]; }
@@ -175,26 +175,13 @@ int smplx_grid_create(const double origin[3], int nx, int ny, int nz, double res
 void smplx_grid_destroy(smplx_grid* g)
 {
     if (!g) return;
-    if (g->d_d2) (void)hipFree(g->d_d2);
-    if (g->d_occ) (void)hipFree(g->d_occ);
-    if (g->d_tmp) (void)hipFree(g->d_tmp);
-    if (g->d_counts) (void)hipFree(g->d_counts);
-    for (WorldObject& o : g->objects)
-        if (o.d_cells) (void)hipFree(o.d_cells);
-    if (g->d_vox) (void)hipFree(g->d_vox);
-    if (g->body) {
-        if (g->body->d_cells) (void)hipFree(g->body->d_cells);
-        if (g->body->d_points) (void)hipFree(g->body->d_points);
-        if (g->body->d_states) (void)hipFree(g->body->d_states);
-        delete g->body;
-    }
-    delete g;
+    delete g;      // every device array is owned by a member (grid_handle.h)
 }
 
 // error text for the other translation units of the library (field.hip)
 int smplx_internal_set_error(int code, const char* msg) { return set_error(code, msg ? msg : ""); }
-// ... and field.hip owns the voxeliser: the sphere rows of an object attached by shape (world_objects.h)
-int smplx_internal_object_spheres(void** work, size_t* work_bytes, const smplx_shape* shapes, int n, double radius, std::vector<double>* rows,
+// ... and field.hip owns the voxeliser: the sphere rows of an object attached by shape (object_sphere_rows.h)
+int smplx_internal_object_spheres(WorkSpace* work, const smplx_shape* shapes, int n, double radius, std::vector<double>* rows,
                                   std::vector<int32_t>* first);
 
 int smplx_model_create(const char* robot_text, smplx_model** out)
@@ -398,7 +385,6 @@ void smplx_space_destroy(smplx_space* s)
     if (s->bfs.d_brick_queued) (void)hipFree(s->bfs.d_brick_queued);
     if (s->dt.d_table) (void)hipFree(s->dt.d_table);
     if (s->att.d_bodies) (void)hipFree(s->att.d_bodies);
-    if (s->att.d_vox) (void)hipFree(s->att.d_vox);
     for (StepLaunch::WorkCounters& w : s->step.work_counters) (void)hipFree(w.p);
     (void)search_free(s);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -900,7 +886,7 @@ int smplx_attach_object(smplx_space* s, const char* id, const char* link, const 
     if (int e = attach_allowed(allowed, nallowed, B)) return e;
     std::vector<double> rows;
     std::vector<int32_t> first;
-    if (int e = smplx_internal_object_spheres(&s->att.d_vox, &s->att.vox_bytes, shapes, n, radius, &rows, &first)) return e;
+    if (int e = smplx_internal_object_spheres(&s->att.vox, shapes, n, radius, &rows, &first)) return e;
     const int made = (int)(rows.size() / 4);
     // the reference would attach an empty model that is never checked
     if (made == 0) return set_error(SMPLX_E_ARG, "the shapes make no sphere: every triangle is degenerate");
@@ -912,7 +898,7 @@ int smplx_object_spheres(smplx_space* s, const smplx_shape* shapes, int n, doubl
     if (!s || !shapes || n <= 0 || !first || cap < 0 || (cap > 0 && !xyzr)) return set_error(SMPLX_E_ARG, "bad argument");
     std::vector<double> rows;
     std::vector<int32_t> f;
-    if (int e = smplx_internal_object_spheres(&s->att.d_vox, &s->att.vox_bytes, shapes, n, radius, &rows, &f)) return e;
+    if (int e = smplx_internal_object_spheres(&s->att.vox, shapes, n, radius, &rows, &f)) return e;
     for (int k = 0; k <= n; ++k) first[k] = f[(size_t)k];
     const int take = std::min(cap, f[(size_t)n]);
     if (take > 0) std::memcpy(xyzr, rows.data(), sizeof(double) * 4 * (size_t)take);

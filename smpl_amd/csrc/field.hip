@@ -12,7 +12,7 @@
 // dmax = ceil(max_dist / res) (distance_map.hpp:126); the cells of the one-cell border layer around the grid count as
 // obstacles (:560-606).  Checked against a brute-force nearest-obstacle search and against the host builder of the
 // test scenes (tests/test_gpu_field.py).  Parity with the reference's own propagation: unpinned.  What IS pinned to the
-// reference is the step before it, the voxelisation of world objects into cells (voxelize.h, world_objects.h).
+// reference is the step before it, the voxelisation of world objects into cells (voxelize.h, mesh_voxelizer.h).
 //
 // Method: the squared Euclidean distance separates by axes,
 //     d2(x,y,z) = min_x' (x-x')^2 + [ min_y' (y-y')^2 + [ min_z' over occupied (x',y',z') of (z-z')^2 ] ],
@@ -46,6 +46,14 @@ namespace {
 
 // a box of cells, inclusive
 struct Window { int x0, y0, z0, x1, y1, z1; };
+// the box of no cell (x1 < 0), and a box grown to hold the range b = {x0 y0 z0 x1 y1 z1} (b[3] < b[0]: an empty range)
+inline Window empty_box() { return Window{1 << 30, 1 << 30, 1 << 30, -1, -1, -1}; }
+inline void grow_box(Window& box, const int* b)
+{
+    if (b[3] < b[0]) return;
+    box.x0 = std::min(box.x0, b[0]); box.y0 = std::min(box.y0, b[1]); box.z0 = std::min(box.z0, b[2]);
+    box.x1 = std::max(box.x1, b[3]); box.y1 = std::max(box.y1, b[4]); box.z1 = std::max(box.z1, b[5]);
+}
 __host__ __device__ inline long long window_cells(const Window& w) { return (long long)(w.x1 - w.x0 + 1) * (w.y1 - w.y0 + 1) * (w.z1 - w.z0 + 1); }
 __device__ __forceinline__ void window_cell(const Window& w, long long i, int& x, int& y, int& z)
 {
@@ -77,11 +85,11 @@ k_occ_boxes(unsigned char* __restrict__ occ, int* __restrict__ counts, int nx, i
 // OccupancyGrid::addPointsToField / removePointsFromField for a list of cells (occupancy_grid.cpp:357-406).  Without
 // reference counts a cell simply becomes occupied / free.  With them every point counts (a cell listed twice is counted
 // twice, as the reference's sequential loop does): the cell becomes occupied when its count leaves 0 and free when it
-// returns to 0; a removal from a cell with count 0 does nothing.
+// returns to 0; a removal from a cell with count 0 does nothing.  One cell a thread, no loop: launched by occ_points alone.
 __global__ void __launch_bounds__(FIELD_BLOCK)
-k_occ_points(unsigned char* __restrict__ occ, int* __restrict__ counts, int nx, int ny, int nz, const int* __restrict__ cells, int n, int add)
+k_occ_points(unsigned char* __restrict__ occ, int* __restrict__ counts, int nx, int ny, int nz, const int* __restrict__ cells, size_t n, int add)
 {
-    const int i = blockIdx.x * FIELD_BLOCK + threadIdx.x;
+    const size_t i = (size_t)blockIdx.x * FIELD_BLOCK + threadIdx.x;
     if (i >= n) return;
     const int x = cells[3 * i], y = cells[3 * i + 1], z = cells[3 * i + 2];
     if (x < 0 || y < 0 || z < 0 || x >= nx || y >= ny || z >= nz) return;   // out of bounds: skipped (:366, :390; distance_map.hpp:312-316)
@@ -192,6 +200,8 @@ extern "C" int smplx_internal_set_error(int code, const char* msg);
 
 namespace {
 
+const char* const kNotEditable = "the grid was created from a finished field (smplx_grid_create), not on the GPU";
+
 // the three passes on a window of cells (the whole grid: what a new field needs)
 int field_update(smplx_grid* g, const Window& w)
 {
@@ -200,15 +210,25 @@ int field_update(smplx_grid* g, const Window& w)
     unsigned short* t1 = g->d_tmp;
     unsigned short* t2 = g->d_tmp + total;
     const int nb = blocks_of((size_t)window_cells(w));
-    hipLaunchKernelGGL(k_edt_z, dim3(nb), dim3(FIELD_BLOCK), 0, 0, g->d_occ, t1, nx, ny, nz, g->dmax_int, w);
+    hipLaunchKernelGGL(k_edt_z, dim3(nb), dim3(FIELD_BLOCK), 0, 0, (const unsigned char*)g->d_occ, t1, nx, ny, nz, g->dmax_int, w);
     hipLaunchKernelGGL(k_edt_axis<false>, dim3(nb), dim3(FIELD_BLOCK), 0, 0, t1, t2, nx, ny, nz, 1, g->dmax_int, g->dev.bricks[1], g->dev.bricks[2], w);
-    hipLaunchKernelGGL(k_edt_axis<true>, dim3(nb), dim3(FIELD_BLOCK), 0, 0, t2, (unsigned short*)g->d_d2, nx, ny, nz, 0, g->dmax_int, g->dev.bricks[1],
+    hipLaunchKernelGGL(k_edt_axis<true>, dim3(nb), dim3(FIELD_BLOCK), 0, 0, t2, g->d_d2.p, nx, ny, nz, 0, g->dmax_int, g->dev.bricks[1],
                        g->dev.bricks[2], w);
     FIELD_TRY(hipGetLastError());
     FIELD_TRY(hipDeviceSynchronize());
     g->last_window_cells = window_cells(w);
     ++g->epoch;
     return SMPLX_OK;
+}
+
+// adds (add != 0) or removes n cells listed on the device, the only launch of k_occ_points: a block for every FIELD_BLOCK
+// cells, however many (the cap of blocks_of() is for kernels that loop).  The reference counts take part when the grid
+// keeps them and the caller's edit counts.  The caller checks for launch errors and waits.
+void occ_points(const smplx_grid* g, const int32_t* cells, size_t n, int add, bool counted)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(k_occ_points, dim3((unsigned)((n + FIELD_BLOCK - 1) / FIELD_BLOCK)), dim3(FIELD_BLOCK), 0, 0, g->d_occ.p,
+                       counted && g->ref_counted ? g->d_counts.p : nullptr, g->n[0], g->n[1], g->n[2], (const int*)cells, n, add);
 }
 
 Window whole_grid(const smplx_grid* g) { return Window{0, 0, 0, g->n[0] - 1, g->n[1] - 1, g->n[2] - 1}; }
@@ -253,11 +273,11 @@ int smplx_grid_create_empty(const double origin[3], int nx, int ny, int nz, doub
     g->n[0] = nx; g->n[1] = ny; g->n[2] = nz;
     const int bx = (nx + 3) / 4, by = (ny + 3) / 4, bz = (nz + 3) / 4;
     const size_t total = (size_t)nx * ny * nz, tiled = (size_t)bx * by * bz * 64;
-    hipError_t e = hipMalloc((void**)&g->d_d2, tiled * sizeof(uint16_t));
+    hipError_t e = g->d_d2.alloc(tiled);
     if (e == hipSuccess) e = hipMemset(g->d_d2, 0, tiled * sizeof(uint16_t));
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_occ, total);
+    if (e == hipSuccess) e = g->d_occ.alloc(total);
     if (e == hipSuccess) e = hipMemset(g->d_occ, 0, total);
-    if (e == hipSuccess) e = hipMalloc((void**)&g->d_tmp, 2 * total * sizeof(uint16_t));
+    if (e == hipSuccess) e = g->d_tmp.alloc(2 * total);
     if (e != hipSuccess) {
         const std::string msg = std::string("grid allocation: ") + hipGetErrorString(e);
         smplx_grid_destroy(g);
@@ -275,16 +295,15 @@ int smplx_grid_create_empty(const double origin[3], int nx, int ny, int nz, doub
 
 int smplx_grid_set_ref_counted(smplx_grid* g, int on)
 {
-    if (!g || !g->d_occ) return smplx_internal_set_error(SMPLX_E_STATE, "the grid was created from a finished field (smplx_grid_create), not on the GPU");
+    if (!g || !g->d_occ) return smplx_internal_set_error(SMPLX_E_STATE, kNotEditable);
     if (!on) {
-        if (g->d_counts) (void)hipFree(g->d_counts);
-        g->d_counts = nullptr;
+        g->d_counts.reset();
         g->ref_counted = false;
         return SMPLX_OK;
     }
     const size_t total = (size_t)g->n[0] * g->n[1] * g->n[2];
-    if (!g->d_counts) FIELD_TRY(hipMalloc((void**)&g->d_counts, sizeof(int32_t) * total));
-    hipLaunchKernelGGL(k_counts_init, dim3(blocks_of(total)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, g->d_counts, total);   // initRefCounts
+    if (!g->d_counts) FIELD_TRY(g->d_counts.alloc(total));
+    hipLaunchKernelGGL(k_counts_init, dim3(blocks_of(total)), dim3(FIELD_BLOCK), 0, 0, (const unsigned char*)g->d_occ, g->d_counts.p, total);   // initRefCounts
     FIELD_TRY(hipGetLastError());
     FIELD_TRY(hipDeviceSynchronize());
     g->ref_counted = true;
@@ -293,32 +312,26 @@ int smplx_grid_set_ref_counted(smplx_grid* g, int on)
 
 static int change_cells(smplx_grid* g, const int* host, int n, int width, int add, bool counted)
 {
-    if (!g || !g->d_occ) return smplx_internal_set_error(SMPLX_E_STATE, "the grid was created from a finished field (smplx_grid_create), not on the GPU");
+    if (!g || !g->d_occ) return smplx_internal_set_error(SMPLX_E_STATE, kNotEditable);
     if (n <= 0) return SMPLX_OK;
     // the cells that can change: inside the bounding box of the listed cells / boxes
-    Window box{1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
+    Window box = empty_box();
     for (int i = 0; i < n; ++i) {
         const int* c = host + (size_t)i * width;
-        const int hi[3] = {width == 6 ? c[3] : c[0], width == 6 ? c[4] : c[1], width == 6 ? c[5] : c[2]};
+        const int range[6] = {c[0], c[1], c[2], width == 6 ? c[3] : c[0], width == 6 ? c[4] : c[1], width == 6 ? c[5] : c[2]};
         if (width == 3 && (c[0] < 0 || c[1] < 0 || c[2] < 0 || c[0] >= g->n[0] || c[1] >= g->n[1] || c[2] >= g->n[2])) continue;
-        box.x0 = std::min(box.x0, c[0]); box.y0 = std::min(box.y0, c[1]); box.z0 = std::min(box.z0, c[2]);
-        box.x1 = std::max(box.x1, hi[0]); box.y1 = std::max(box.y1, hi[1]); box.z1 = std::max(box.z1, hi[2]);
+        grow_box(box, range);
     }
     if (box.x1 < 0) return SMPLX_OK;      // nothing inside the grid
-    int* d = nullptr;
-    FIELD_TRY(hipMalloc((void**)&d, sizeof(int) * (size_t)n * width));
-    hipError_t e = hipMemcpy(d, host, sizeof(int) * (size_t)n * width, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const size_t total = (size_t)g->n[0] * g->n[1] * g->n[2];
-        int* counts = counted && g->ref_counted ? g->d_counts : nullptr;
-        (void)total;
-        if (width == 6) hipLaunchKernelGGL(k_occ_boxes, dim3(blocks_of((size_t)window_cells(box))), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2], d, n, box);
-        else hipLaunchKernelGGL(k_occ_points, dim3(blocks_of((size_t)n)), dim3(FIELD_BLOCK), 0, 0, g->d_occ, counts, g->n[0], g->n[1], g->n[2], d, n, add);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-    }
-    (void)hipFree(d);
-    if (e != hipSuccess) return smplx_internal_set_error(SMPLX_E_HIP, (std::string("occupancy update: ") + hipGetErrorString(e)).c_str());
+    DevPtr<int> d;
+    FIELD_TRY(d.alloc((size_t)n * width));
+    FIELD_TRY(hipMemcpy(d, host, sizeof(int) * (size_t)n * width, hipMemcpyHostToDevice));
+    if (width == 6)
+        hipLaunchKernelGGL(k_occ_boxes, dim3(blocks_of((size_t)window_cells(box))), dim3(FIELD_BLOCK), 0, 0, g->d_occ.p,
+                           counted && g->ref_counted ? g->d_counts.p : nullptr, g->n[0], g->n[1], g->n[2], (const int*)d, n, box);
+    else occ_points(g, d, (size_t)n, add, counted);
+    FIELD_TRY(hipGetLastError());
+    FIELD_TRY(hipDeviceSynchronize());
     return field_update(g, edit_window(g, box));
 }
 
@@ -411,19 +424,19 @@ int smplx_grid_copy_d2(const smplx_grid* g, int32_t* d2)
 {
     if (!g || !d2) return smplx_internal_set_error(SMPLX_E_ARG, "null argument");
     const size_t total = (size_t)g->n[0] * g->n[1] * g->n[2];
-    int* d = nullptr;
-    FIELD_TRY(hipMalloc((void**)&d, sizeof(int) * total));
-    hipLaunchKernelGGL(k_untile, dim3(blocks_of(total)), dim3(FIELD_BLOCK), 0, 0, g->d_d2, d, g->n[0], g->n[1], g->n[2], g->dev.bricks[1], g->dev.bricks[2]);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpy(d2, d, sizeof(int) * total, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return smplx_internal_set_error(SMPLX_E_HIP, (std::string("field download: ") + hipGetErrorString(e)).c_str());
+    DevPtr<int> d;
+    FIELD_TRY(d.alloc(total));
+    hipLaunchKernelGGL(k_untile, dim3(blocks_of(total)), dim3(FIELD_BLOCK), 0, 0, (const unsigned short*)g->d_d2, d.p, g->n[0], g->n[1], g->n[2], g->dev.bricks[1],
+                       g->dev.bricks[2]);
+    FIELD_TRY(hipGetLastError());
+    FIELD_TRY(hipMemcpy(d2, d, sizeof(int) * total, hipMemcpyDeviceToHost));
     return SMPLX_OK;
 }
 
 }  // extern "C"
 
-// world objects: shapes voxelised on the GPU, a registry of named objects on the grid
+// world objects: shapes voxelised on the GPU (shape_meshes.h, mesh_voxelizer.h, octree_voxelizer.h, object_sphere_rows.h
+// over vox_common.h), a registry of named objects on the grid
 #include "world_objects.h"
 
 // the robot body: voxel models of the links outside the planning group, placed under the current link transforms

@@ -11,7 +11,7 @@
 // multiply-add; host and device compile this one source): oct_axis_trips and oct_axis_value run on the device, and the host
 // compiler builds the same source for tests/cpp/octree_host_driver.cpp.
 //
-// Limits (world_objects.h refuses a call beyond them with SMPLX_E_LIMIT before it allocates or launches anything):
+// Limits (octree_voxelizer.h octree_limits refuses a call beyond them with SMPLX_E_LIMIT before it allocates or launches anything):
 // size / res <= OCT_MAX_RATIO per leaf, and the bound on the call's sample points, (2 ceil(size / res) + 1)^3 summed over
 // its leaves (1 for a leaf of size <= res), at most OCT_MAX_POINTS -- the voxeliser's cap on the cells of one call.
 // oct_axis_trips stops at the bound's 2 ceil(size / res) + 1 trips.  The running sum reaches that only where res is

@@ -159,10 +159,7 @@ struct AttachedBodies {
     };
     std::vector<Body> bodies;
     SmplxBodiesDev* d_bodies = nullptr;
-    // work space of the voxeliser for objects attached by shape (world_objects.h object_spheres_run): grows, never
-    // shrinks, like the grid's
-    void* d_vox = nullptr;
-    size_t vox_bytes = 0;
+    WorkSpace vox;                     // of the voxeliser for objects attached by shape (object_sphere_rows.h), like the grid's
     uint64_t epoch = 0;                // attaches + detaches so far
     uint64_t epoch_goal = 0;           // ... when the goal was set: the successor caches belong to that set of bodies
 };

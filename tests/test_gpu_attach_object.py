@@ -59,6 +59,34 @@ def test_sphere_rows_cap_and_radius(probe):
     assert OC.same_bits(got, OC.rows_of(cells, r))
 
 
+def test_the_rows_work_space_across_radii(small_cfg):
+    """A space keeps one work space for these calls: the voxeliser's arrays first, then the sphere rows, and the block only
+    grows (object_sphere_rows.h).  A flat triangle on a new space at a large radius, at a small one and at the large one
+    again: at the small radius the rows (32 bytes a filled voxel) outgrow the voxeliser's seven arrays -- one triangle,
+    one chunk and a mask of one byte per voxel of the vertices' index range, each rounded up to 256 bytes -- so the middle
+    call replaces the block between its two uses, and the last call runs inside a block larger than it needs.  Each
+    result equals the judge's, bit for bit."""
+    import voxelize_ref as V
+    s = OC._shape(V.MESH, (), vertices=np.array([(0.2013, 0.0007, 0.0013), (0.2613, 0.0007, 0.0013), (0.2013, 0.0507, 0.0013)]),
+                  triangles=np.array([(0, 1, 2)]))
+    want = {}
+    for r in (0.025, 0.004):
+        res = r / np.sqrt(2.0)
+        cells, und = V.voxelize_shape(s, (0.0, 0.0, 0.0), res, None, eps=1e-6)
+        assert len(und) == 0 and len(cells) > 0
+        want[r] = OC.rows_of(cells, r)
+        v = np.asarray(s["vertices"])
+        mask = int(np.prod(np.floor(v.max(0) / res) - np.floor(v.min(0) / res) + 3))     # a bound: two voxels to spare an axis
+        assert mask <= 8 * 256                                                           # one chunk
+        voxeliser = 6 * 256 + (mask + 255) // 256 * 256
+        print(f"radius {r}: {len(cells)} rows = {32 * len(cells)} bytes, the voxeliser's arrays at most {voxeliser}")
+        assert (32 * len(cells) > voxeliser) == (r == 0.004)
+    probe = _space(small_cfg, "small")
+    for r in (0.025, 0.004, 0.025):
+        got, first = probe.object_spheres([s], radius=r)
+        assert list(first) == [0, len(want[r])] and OC.same_bits(got, want[r]), r
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. the body's nodes
 # ---------------------------------------------------------------------------------------------------------------------

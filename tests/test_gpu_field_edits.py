@@ -156,6 +156,46 @@ def test_the_16_bit_limit_is_255_cells():
     assert np.array_equal(g.d2(), brute_force(occ, 255))  # and the earlier grid is as it was
 
 
+def test_one_edit_of_more_than_2_to_the_24_points_edits_every_point():
+    """k_occ_points handles one cell a thread, so its launch must cover every listed cell (field.hip occ_points): a grid
+    capped at 65 536 blocks of 256 threads stops after 2^24 points.  One add_points call on a reference-counted 32^3 grid
+    carries 2^24 + 512 points: the first 2^24 cycle through the 4 096 cells of the slab x < 4 (each listed 4 096 times),
+    the last 512 fall into 512 distinct cells with x >= 16.  Counts equal the bincount of the cells and the field the
+    model's on that occupancy; one remove_points call with the same array leaves zero counts and the empty grid's field."""
+    from smpl_amd import capi
+    dims, res, max_dist, dmax = (32, 32, 32), 0.05, 0.2, 4
+    assert fm.dmax_of(res, max_dist) == dmax
+    m = fm.FieldModel(ORIGIN, dims, res)
+    slab = np.argwhere(np.ones((4, 32, 32), bool))                                # 4 096 cells, x < 4
+    tail = np.argwhere(np.ones((8, 8, 8), bool)) + (16, 3, 5)                      # 512 cells, x 16..23
+    unique = np.vstack([slab, tail])
+    world = np.asarray(ORIGIN) + unique.astype(np.float64) * res                   # cell centres
+    assert np.array_equal(m.cells(world), unique)
+    n = 2 ** 24 + 512
+    pts = np.empty((n, 3), np.float64)
+    pts[:2 ** 24].reshape(4096, 4096, 3)[:] = world[:4096]                         # tiled, not looped
+    pts[2 ** 24:] = world[4096:]
+    flat = np.empty(n, np.int64)
+    flat[:2 ** 24].reshape(4096, 4096)[:] = np.ravel_multi_index(slab.T, dims)
+    flat[2 ** 24:] = np.ravel_multi_index(tail.T, dims)
+    want = np.bincount(flat, minlength=32 ** 3).reshape(dims)
+    assert want[:4].min() == want.max() == 4096 and (want == 1).sum() == 512 and want.sum() == n
+
+    g = capi.Grid.empty(ORIGIN, dims, res, max_dist)
+    empty = g.d2()
+    g.set_ref_counted(True)
+    g.add_points(pts)
+    got = g.counts()
+    print(f"counted points: {int(got.sum())} of {n}; cells of the last 512 that are occupied: {int((got[16:] > 0).sum())}")
+    assert np.array_equal(got, want)
+    m.occ = want > 0
+    assert np.array_equal(g.d2(), m.d2(dmax))
+    g.remove_points(pts)
+    assert not g.counts().any()
+    assert np.array_equal(g.d2(), empty)
+    assert np.array_equal(empty, capi.Grid.empty(ORIGIN, dims, res, max_dist).d2())
+
+
 def test_collision_kernels_read_the_edited_field_as_a_host_tiled_upload_of_the_model(small_cfg):
     """The tiled field k_edt_axis<true> writes, judged by the kernels that read it and not by k_untile: after each of a
     windowed add, a remove and an update near the arm, 512 states get the same verdicts and the same lookup tallies from

@@ -190,6 +190,65 @@ def test_put_places_the_states_and_updates_the_field_once(counted):
     _refused(-5, lambda: g.take_body())
 
 
+def _rooted_text():
+    """the body of body_cases under one more link: the joint jr on the new root moves every link at once"""
+    return (C.body_text().replace("link base", "link world\nlink base", 1)
+            + "joint jr revolute world base  0 0 0  0 0 0  0 0 1  -3 3\nvoxels world 0.01\nvalue jr 0.0\n")
+
+
+def test_the_work_space_of_a_put_across_puts():
+    """A put carves the transforms, prefixes and boxes of the states it places out of a work space kept with the grid's
+    record of the body, which only grows (device_mem.h): one state takes three 256-byte pieces, all seven take six.  A
+    grid's first put of a body places every state, whatever moved, so the small put cannot come before it; from there the
+    order is a put that places one state (a leaf joint moved) inside the larger block, a put that places all states (the
+    root joint moved), then take_body -- the record and its work space go -- and a put of the body again.  The cells of
+    every model are the point rule's on the engine's own transforms, and counts and field those of a fresh grid that got
+    the replayed lists, at each step."""
+    text = _rooted_text()
+    body, M = capi.Body(text), B.Body(text)
+    nm = body.nmodels
+    assert nm == NM + 1 and len(body.model_points(nm - 1)) == 0            # the new root's model is empty
+    outside = [m for m in range(nm) if M.outside[m] and len(body.model_points(m)) > 0]
+    assert len(outside) == 7
+
+    def expected():
+        T = body.link_transforms()
+        out = []
+        for m in range(nm):
+            cells, margin = B.place(T[body.model_link(m)], body.model_points(m), C.ORIGIN, C.RES, C.DIMS)
+            assert len(margin) == 0 or margin.min() > 1e-9, m
+            out.append(cells)
+        return out
+
+    g = _grid(True)
+    steps, now = [], {m: [] for m in outside}
+
+    def put_and_check(moved, tag):
+        g.put_body(body)
+        want = expected()
+        for m in outside:
+            assert np.array_equal(g.body_cells(m), want[m]), (tag, m)
+            assert (m in moved) or np.array_equal(want[m], now[m]), (tag, m)
+        for m in moved:
+            steps.append((now[m], want[m]))
+            now[m] = want[m]
+        occ, counts = B.occupancy_after(steps, C.DIMS, True)
+        _same(g, _fresh_from(occ, counts, True), True)
+
+    put_and_check(outside, "first put")
+    l2 = [m for m in outside if body.model_link(m) == M.links.index("l2")]
+    body.set_joint(*C.SECOND_Q)
+    assert [m for m in outside if body.dirty()[m]] == l2 and len(l2) == 1
+    put_and_check(l2, "one state")
+    body.set_joint("jr", 0.0137)
+    assert [m for m in outside if body.dirty()[m]] == outside
+    put_and_check(outside, "all states")
+    g.take_body()
+    _same(g, _grid(True), True)
+    steps, now = [], {m: [] for m in outside}
+    put_and_check(outside, "after take")
+
+
 @pytest.mark.parametrize("counted", [False, True])
 def test_a_world_object_that_overlaps_the_body(counted):
     body = capi.Body(C.body_text())

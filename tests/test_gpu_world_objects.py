@@ -117,6 +117,45 @@ def test_work_distribution_edges(grid, key):
         assert got.min(0).tolist() == [0, 0, want[:, 2].min()] and got[:, 0].max() == W.DIMS[0] - 1
 
 
+def test_the_work_space_across_calls():
+    """The voxelisers keep one work space on the grid that only grows, and the mesh and the octree voxeliser carve the same
+    block differently (device_mem.h).  On one 64^3 grid: a small mesh call, a larger one, an octree (the other carve),
+    the small one again, and the largest (six shapes in one call).  Every list equals the list the same call gives on a
+    fresh grid; then the same order through insert_object / remove_object, with the object's lists, the occupancy (as
+    reference counts) and the field equal to those of a fresh grid that got that one object."""
+    import octree_cases as OC
+    dims = (64, 64, 64)
+
+    def fresh():
+        g = capi.Grid.empty(W.ORIGIN, dims, W.RES, W.MAX_DIST)
+        g.set_ref_counted(True)
+        return g
+
+    calls = [[W.judged("one_triangle")[0]], [W.judged("sphere")[0]], [OC.shape("cloud")], [W.judged("one_triangle")[0]],
+             [W.judged(k)[0] for k in SIX]]
+    g = fresh()
+    sizes = []
+    for k, shapes in enumerate(calls):
+        got, want = g.voxelize(shapes), fresh().voxelize(shapes)
+        sizes.append(sum(len(c) for c in got))
+        assert len(got) == len(want) == len(shapes), k
+        for a, b in zip(got, want):
+            assert len(a) > 0 and np.array_equal(a, b), k
+    print("cells per call:", sizes)
+    assert sizes[0] == sizes[3] < sizes[1] < sizes[4]
+    empty = fresh()
+    for k, shapes in enumerate(calls):
+        g.insert_object("o", shapes)
+        one = fresh()
+        one.insert_object("o", shapes)
+        for s in range(len(shapes)):
+            assert np.array_equal(g.object_cells("o", s), one.object_cells("o", s)), (k, s)
+        _same(g, one, counted=True)
+        assert g.counts().any(), k
+        g.remove_object("o")
+        _same(g, empty, counted=True)
+
+
 # ---- 7. insert / remove / move ---------------------------------------------------------------------------------------
 @pytest.mark.parametrize("counted", [False, True])
 def test_insert_remove_against_fresh_grids(counted):
