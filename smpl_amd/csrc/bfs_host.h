@@ -150,14 +150,14 @@ int run_bfs_multi(smplx_space* const* spaces, int nq)
         G.dist = s->bfs.d_dist; G.lists = s->bfs.d_queue; G.counts = s->bfs.d_counts; G.queued = s->bfs.d_brick_queued;
         G.tag_word = s->hs.bfs.tag_word; G.tag_mask = s->hs.bfs.tag_mask;
         int c[3];
-        const bool in_bounds = bfs_goal_cell(s, s->goal_xyz, c);
+        const bool in_bounds = bfs_goal_cell(s, s->goal.xyz, c);
         for (int a = 0; a < 3; ++a) G.cell[a] = in_bounds ? c[a] : -1;
         G.pad = 0;
     }
     // per pass {sum, largest} of the goals' queue sizes, and one more slot for a pass beyond the history
     const int n_stats = kBfsHistory + 1;
-    if (int e = lead->bfs.b_goals.reserve((size_t)nq)) return e;
-    if (int e = lead->bfs.b_pass_stats.reserve((size_t)2 * n_stats)) return e;
+    if (int e = reserve(lead->bfs.b_goals, (size_t)nq)) return e;
+    if (int e = reserve(lead->bfs.b_pass_stats, (size_t)2 * n_stats)) return e;
     const SmplxBfsGoalDev* d_goals = lead->bfs.b_goals.p;
     int32_t* d_stats = lead->bfs.b_pass_stats.p;
     HIP_TRY(hipMemcpyAsync(lead->bfs.b_goals.p, goals.data(), sizeof(SmplxBfsGoalDev) * nq, hipMemcpyHostToDevice, stream));

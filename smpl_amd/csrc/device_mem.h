@@ -1,5 +1,7 @@
-// smpl_amd/csrc/device_mem.h -- who owns device memory on the construction side (grid_handle.h, field.hip and the headers
-// in its tail): one owning pointer and one work space.  No kernel includes this.
+// smpl_amd/csrc/device_mem.h -- who owns what the host holds on the device, on the construction side (grid_handle.h,
+// field.hip and the headers in its tail) and on the search side (space.h and the headers of engine.hip): one owning
+// pointer, the buffers that only ever grow, one work space, and the owners of a stream and of an event.  Every hipFree,
+// hipHostFree, hipStreamDestroy and hipEventDestroy of the library is in this file.  No kernel includes this.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -18,6 +20,64 @@ struct DevPtr {
     // frees what it holds, then allocates n entries (one where n is 0: a list may be empty)
     hipError_t alloc(size_t n) { reset(); return hipMalloc((void**)&p, (n ? n : 1) * sizeof(T)); }
     operator T*() const { return p; }
+};
+
+// a device buffer that only ever grows: a DevPtr (its `p` is the plain pointer) plus the entries it has room for.
+// reserve(n) does nothing when n fits; else it frees the block, then allocates max(n, 64) entries.  After a failure the
+// buffer is empty (p == nullptr, cap == 0).  The host engine calls it through reserve() of host_core.h, for an SMPLX code.
+template <class T>
+struct DevBuf : DevPtr<T> {
+    size_t cap = 0;
+    hipError_t reserve(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        cap = 0;
+        const size_t want = n > 64 ? n : 64;
+        if (const hipError_t e = this->alloc(want)) { this->p = nullptr; return e; }
+        cap = want;
+        return hipSuccess;
+    }
+};
+
+// its pinned host twin
+template <class T>
+struct PinBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { reset(); }
+    void reset() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+    hipError_t reserve(size_t n)
+    {
+        if (n <= cap) return hipSuccess;
+        reset();
+        const size_t want = n > 64 ? n : 64;
+        if (const hipError_t e = hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault)) { p = nullptr; return e; }
+        cap = want;
+        return hipSuccess;
+    }
+};
+
+// an owning stream or event: move-only, destroyed by its destructor; reads like the raw handle
+template <class H, hipError_t (*Destroy)(H)>
+struct DevHandle {
+    H h = nullptr;
+    DevHandle() = default;
+    DevHandle(DevHandle&& o) noexcept : h(o.h) { o.h = nullptr; }
+    DevHandle& operator=(DevHandle&& o) noexcept { if (this != &o) { reset(); h = o.h; o.h = nullptr; } return *this; }
+    ~DevHandle() { reset(); }
+    void reset() { if (h) (void)Destroy(h); h = nullptr; }
+    operator H() const { return h; }
+};
+
+struct DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
+    hipError_t create() { reset(); return hipStreamCreate(&h); }
+};
+
+struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(unsigned flags = hipEventDefault) { reset(); return hipEventCreateWithFlags(&h, flags); }
 };
 
 // the arrays of one call, carved out of one block that grows and never shrinks: a device allocation costs more than the

@@ -13,11 +13,15 @@ namespace {
 
 int table_alloc(smplx_space* s, size_t cap)
 {
-    if (s->dt.d_table) (void)hipFree(s->dt.d_table);
-    s->dt.d_table = nullptr;
     const int stride = smplx_table_stride(s->N);
-    HIP_TRY(hipMalloc((void**)&s->dt.d_table, cap * (size_t)stride * sizeof(int32_t)));
-    HIP_TRY(hipMemsetAsync(s->dt.d_table, 0, cap * (size_t)stride * sizeof(int32_t), s->stream));
+    // the old table is freed first (the two need not fit side by side): if the new one cannot be had the space has none
+    s->dt.cap = 0;
+    s->hs.table.slots = nullptr;
+    HIP_TRY(s->dt.d_table.alloc(cap * (size_t)stride));
+    if (const hipError_t e = hipMemsetAsync(s->dt.d_table, 0, cap * (size_t)stride * sizeof(int32_t), s->stream)) {
+        s->dt.d_table.reset();
+        return hip_status(e, "table_alloc: hipMemsetAsync");
+    }
     s->dt.cap = cap;
     s->hs.table.slots = s->dt.d_table;
     s->hs.table.mask = (uint32_t)(cap - 1);
@@ -69,8 +73,8 @@ int table_upload(smplx_space* lead, const std::vector<int32_t>& items, DevBuf<in
 {
     if (items.empty()) return SMPLX_OK;
     const int n = (int)(items.size() / ((size_t)lead->N + 2));
-    if (int e = dbuf.reserve(items.size())) return e;
-    if (int e = pbuf.reserve(items.size())) return e;
+    if (int e = reserve(dbuf, items.size())) return e;
+    if (int e = reserve(pbuf, items.size())) return e;
     std::memcpy(pbuf.p, items.data(), items.size() * sizeof(int32_t));
     HIP_TRY(hipMemcpyAsync(dbuf.p, pbuf.p, items.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, stream, lead->d_space, stab, dbuf.p, n, lead->N);

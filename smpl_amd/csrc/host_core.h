@@ -1,6 +1,7 @@
 // smpl_amd/csrc/host_core.h -- what every part of the host engine (engine.hip and the headers it is made of) stands on:
-// the thread's error text behind smplx_last_error(), the HIP_TRY / KLAUNCH early returns, device and pinned buffers that
-// only ever grow, the input guard of the entry points, and the two rounding helpers of every size computation.
+// the thread's error text behind smplx_last_error(), the HIP_TRY / KLAUNCH early returns, the error code of a failed
+// allocation (device_mem.h, which has the owners of everything the host holds on the device), the input guard of the
+// entry points, and the two rounding helpers of every size computation.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +11,7 @@
 #include <string>
 
 #include "../../include/smpl_amd.h"
+#include "device_mem.h"
 #include "specialize.h"
 
 namespace {
@@ -21,6 +23,15 @@ int set_error(int code, const std::string& msg)
     g_error = msg;
     return code;
 }
+
+int hip_status(hipError_t e, const char* what)
+{
+    return e == hipSuccess ? SMPLX_OK : set_error(SMPLX_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// room for n entries in a DevBuf or a PinBuf (device_mem.h), as an SMPLX code
+template <class Buf>
+int reserve(Buf& b, size_t n) { return hip_status(b.reserve(n), "buffer allocation"); }
 
 // input guard of the entry points that take joint values from the caller: a non-finite or absurd value would make the
 // limit folding of KDLRobotModel::checkJointLimits (a -= 2*pi until in range) spin forever on the device
@@ -44,42 +55,6 @@ bool sane_values(const double* q, size_t n)
         hipError_t le_ = smplx::launch((space)->ks.k[smplx::ID], kern, grid, block, lds, stream, __VA_ARGS__);   \
         if (le_ != hipSuccess) return set_error(SMPLX_E_HIP, std::string(#kern) + ": " + hipGetErrorString(le_)); \
     } while (0)
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return SMPLX_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(n, (size_t)64);
-        HIP_TRY(hipMalloc((void**)&p, want * sizeof(T)));
-        cap = want;
-        return SMPLX_OK;
-    }
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
-
-template <class T>
-struct PinBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    int reserve(size_t n)
-    {
-        if (n <= cap) return SMPLX_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = std::max(n, (size_t)64);
-        HIP_TRY(hipHostMalloc((void**)&p, want * sizeof(T), hipHostMallocDefault));
-        cap = want;
-        return SMPLX_OK;
-    }
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-};
 
 inline int blocks_for(long long n, int block) { return (int)((n + block - 1) / block); }
 

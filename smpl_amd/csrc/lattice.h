@@ -10,7 +10,26 @@
 #include <unordered_map>
 #include <vector>
 
+#include "det_math.h"
+#include "device_types.h"
+
 namespace {
+
+// host mirror of ManipLattice::stateToCoord (manip_lattice.cpp:1263-1289) on det_math
+void state_to_coord(const SmplxModelDev& m, const double* q, int32_t* c)
+{
+    for (int v = 0; v < m.nvars; ++v) {
+        const double delta = m.coord_delta[v];
+        if (m.var_type[v] == SMPLX_JT_CONTINUOUS) {
+            const double pos = smplx_normalize_angle_positive(q[v]);
+            int k = (int)((pos + delta * 0.5) / delta);
+            if (k == m.coord_vals[v]) k = 0;
+            c[v] = k;
+        } else {
+            c[v] = (int)(((q[v] - m.var_min[v]) / delta) + 0.5);
+        }
+    }
+}
 
 // coord -> id table: open addressing over the commit-ordered coordinate array.  State ids depend
 // only on insertion order (manip_lattice.cpp:1302-1354), never on the hash function.

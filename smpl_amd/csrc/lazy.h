@@ -20,8 +20,8 @@ namespace {
 // up with a device search that ran on the space
 int lazy_guard(smplx_space* s)
 {
-    if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
-    if (s->grid->epoch != s->grid_epoch)
+    if (!s->goal.set) return set_error(SMPLX_E_STATE, "goal not set");
+    if (s->grid->epoch != s->goal.grid_epoch)
         return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
     if (s->att.epoch != s->att.epoch_goal) return set_error(SMPLX_E_STATE, kBodiesChanged);
     return pull_lattice(s);
@@ -68,12 +68,12 @@ int lazy_rows(smplx_space* s, const double* q, int B, uint8_t* flags, int32_t* c
     LazyHost& Z = s->lazy;
     const size_t BM = (size_t)B * s->M, N = (size_t)s->N;
     int e;
-    if ((e = Z.b_q.reserve((size_t)B * N))) return e;
-    if ((e = Z.b_sq.reserve(BM * N))) return e;
-    if ((e = Z.b_coord.reserve(BM * N))) return e;
-    if ((e = Z.b_h.reserve(BM))) return e;
-    if ((e = Z.b_id.reserve(BM))) return e;
-    if ((e = Z.b_flags.reserve(BM))) return e;
+    if ((e = reserve(Z.b_q, (size_t)B * N))) return e;
+    if ((e = reserve(Z.b_sq, BM * N))) return e;
+    if ((e = reserve(Z.b_coord, BM * N))) return e;
+    if ((e = reserve(Z.b_h, BM))) return e;
+    if ((e = reserve(Z.b_id, BM))) return e;
+    if ((e = reserve(Z.b_flags, BM))) return e;
     HIP_TRY(hipMemsetAsync(Z.b_coord.p, 0, sizeof(int32_t) * BM * N, s->stream));
     HIP_TRY(hipMemsetAsync(Z.b_sq.p, 0, sizeof(double) * BM * N, s->stream));
     HIP_TRY(hipMemcpyAsync(Z.b_q.p, q, sizeof(double) * B * N, hipMemcpyHostToDevice, s->stream));
@@ -94,11 +94,11 @@ int true_cost_items(smplx_space* s, const double* parent_q, const int32_t* child
     LazyHost& Z = s->lazy;
     const size_t N = (size_t)s->N;
     int e;
-    if ((e = Z.b_q.reserve((size_t)n * N))) return e;
-    if ((e = Z.b_sq.reserve((size_t)n * N * SMPLX_TRUE_COST_LANES))) return e;    // the kernel's work_q
-    if ((e = Z.b_coord.reserve((size_t)n * N))) return e;
-    if ((e = Z.b_goal.reserve(n))) return e;
-    if ((e = Z.b_out.reserve((size_t)n * 3))) return e;
+    if ((e = reserve(Z.b_q, (size_t)n * N))) return e;
+    if ((e = reserve(Z.b_sq, (size_t)n * N * SMPLX_TRUE_COST_LANES))) return e;    // the kernel's work_q
+    if ((e = reserve(Z.b_coord, (size_t)n * N))) return e;
+    if ((e = reserve(Z.b_goal, n))) return e;
+    if ((e = reserve(Z.b_out, (size_t)n * 3))) return e;
     HIP_TRY(hipMemcpyAsync(Z.b_q.p, parent_q, sizeof(double) * n * N, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemcpyAsync(Z.b_coord.p, child_coord, sizeof(int32_t) * n * N, hipMemcpyHostToDevice, s->stream));
     if (goal_edge) HIP_TRY(hipMemcpyAsync(Z.b_goal.p, goal_edge, n, hipMemcpyHostToDevice, s->stream));

@@ -90,7 +90,7 @@ int run_group(smplx_space** spaces, Search* S, int nq, char* done, double* t_don
 // Every query sees only its own successor records, in its own sequential order: results are those of a solo run.
 // ---------------------------------------------------------------------------------------------------------------
 struct RingSet : FrontierBatch {
-    hipStream_t stream = nullptr;
+    DevStream stream;
     std::atomic<int> uncollected{0};   // queries of the batch that landed in this set and have not been ingested yet
     std::vector<int> queries;          // the queries of the batch in flight
     bool in_flight = false;
@@ -187,8 +187,8 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     auto submitter = [&]() -> int {
         HIP_TRY(hipSetDevice(device));
         for (RingSet& Bf : sets) {
-            HIP_TRY(hipStreamCreate(&Bf.stream));
-            HIP_TRY(hipEventCreateWithFlags(&Bf.done, hipEventDisableTiming));
+            HIP_TRY(Bf.stream.create());
+            HIP_TRY(Bf.done.create(hipEventDisableTiming));
         }
         long sweeps = 0, states = 0;
         double t_issue = 0;
@@ -299,10 +299,7 @@ int run_pipelined(smplx_space** spaces, Search* S, int nq, int nworkers, char* d
     int rc = submitter();
     if (rc != SMPLX_OK) fail(rc, g_error);
     for (auto& x : th) x.join();
-    for (RingSet& Bf : sets) {
-        if (Bf.stream) { (void)hipStreamSynchronize(Bf.stream); (void)hipStreamDestroy(Bf.stream); }
-        if (Bf.done) (void)hipEventDestroy(Bf.done);
-    }
+    for (RingSet& Bf : sets) if (Bf.stream) (void)hipStreamSynchronize(Bf.stream);   // before `sets` frees its buffers
     if (error.load() != 0) return set_error(error.load(), error_msg);
     return SMPLX_OK;
 }
@@ -332,9 +329,9 @@ int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32
     for (int q = 0; q < nq; ++q) {
         smplx_space* s = spaces[q];
         if (!s) return set_error(SMPLX_E_ARG, "null space");
-        if (!s->goal_set) return set_error(SMPLX_E_STATE, "goal not set");
+        if (!s->goal.set) return set_error(SMPLX_E_STATE, "goal not set");
         if (s->lat.start_id < 0) return set_error(SMPLX_E_STATE, "start not set");
-        if (s->grid->epoch != s->grid_epoch) return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
+        if (s->grid->epoch != s->goal.grid_epoch) return set_error(SMPLX_E_STATE, "the grid was edited after the goal was set: cached successors are stale, set the goal again");
         if (s->att.epoch != s->att.epoch_goal) return set_error(SMPLX_E_STATE, kBodiesChanged);
     }
     // ---- the device-resident search: one persistent workgroup per query, no host round trips.  Taken
@@ -386,7 +383,7 @@ int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32
         if (nq > 1) s->small.pipeline_left = 0;
         const int capB = s->params.batch_states > 0 ? s->params.batch_states : 4096;
         cw[q] = counter_words(capB, s->M);
-        if (int e = s->b_counters.reserve(cw[q])) return e;
+        if (int e = reserve(s->b_counters, cw[q])) return e;
         HIP_TRY(hipMemsetAsync(s->b_counters.p, 0, sizeof(unsigned long long) * cw[q], s->stream));
         base[q] = {s->gpu_batches, s->cache_hits, s->cache_misses, s->committed_evals, s->gpu_evals};
     }
@@ -419,7 +416,7 @@ int replan_multi(smplx_space** spaces, int nq, const smplx_time_params* p, int32
         HIP_TRY(hipSetDevice(spaces[0]->device));
         std::vector<const SmplxSpaceDev*> tab(nq);
         for (int q = 0; q < nq; ++q) tab[q] = spaces[q]->d_space;
-        if (int e = spaces[0]->b_stab.reserve(nq)) return e;
+        if (int e = reserve(spaces[0]->b_stab, nq)) return e;
         HIP_TRY(hipMemcpy(spaces[0]->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
         // one thread sweeps all queries (run_group), or host_threads worker threads own them and this thread is the only
         // GPU submitter (run_pipelined)

@@ -80,15 +80,6 @@ bool search_on_device(const smplx_space* s)
     return search_heap_cache_entries(s, nullptr) > 0;
 }
 
-int search_free(smplx_space* s)
-{
-    DevSearch& D = s->ds;
-    if (D.arena) (void)hipFree(D.arena);
-    if (D.d_hdr) (void)hipFree(D.d_hdr);
-    D = DevSearch();
-    return SMPLX_OK;
-}
-
 // (re)allocate the arena with at least the given capacities, keeping what the device holds
 int search_reserve(smplx_space* s, const SearchCaps& want)
 {
@@ -99,12 +90,12 @@ int search_reserve(smplx_space* s, const SearchCaps& want)
     auto up = [&](int& have, int need) { if (need > have) { have = need; grow = true; } };
     up(c.states, want.states); up(c.heap, want.heap); up(c.incons, want.incons); up(c.log, want.log); up(c.succ, want.succ); up(c.path, want.path);
     if (!D.d_hdr) {
-        HIP_TRY(hipMalloc((void**)&D.d_hdr, sizeof(SmplxSearchDev)));
+        HIP_TRY(D.d_hdr.alloc(1));
         std::memset(&D.h, 0, sizeof(D.h));
     }
     if (grow) {
-        unsigned char* fresh = nullptr;
-        HIP_TRY(hipMalloc((void**)&fresh, search_arena_bytes(c, N)));
+        DevPtr<unsigned char> fresh;   // freed on every early return below
+        HIP_TRY(fresh.alloc(search_arena_bytes(c, N)));
         SmplxSearchDev nh = D.h;
         search_carve(fresh, c, N, nh);
         if (D.arena) {
@@ -121,9 +112,8 @@ int search_reserve(smplx_space* s, const SearchCaps& want)
             HIP_TRY(hipMemcpyAsync(nh.done_cnt, o.done_cnt, ns * sizeof(int32_t), hipMemcpyDeviceToDevice, s->stream));
             if (o.n_succ) HIP_TRY(hipMemcpyAsync(nh.succ, o.succ, (size_t)o.n_succ * sizeof(SmplxSucc), hipMemcpyDeviceToDevice, s->stream));
             HIP_TRY(hipStreamSynchronize(s->stream));
-            (void)hipFree(D.arena);
         }
-        D.arena = fresh;
+        D.arena = std::move(fresh);   // (frees the old arena)
         D.h = nh;
         D.caps = c;
         ++D.grows;
@@ -378,11 +368,11 @@ int search_run_launches(smplx_space** spaces, int nq, const smplx_time_params* p
     {
         std::vector<const SmplxSpaceDev*> tab(nq);
         for (int q = 0; q < nq; ++q) tab[q] = spaces[q]->d_space;
-        if (int e = lead->b_stab.reserve(nq)) return e;
+        if (int e = reserve(lead->b_stab, nq)) return e;
         HIP_TRY(hipMemcpy(lead->b_stab.p, tab.data(), sizeof(void*) * nq, hipMemcpyHostToDevice));
     }
     PinBuf<int32_t>& status = lead->dt.p_ins;      // nq ints the workgroups write when they leave
-    if (int e = status.reserve((size_t)nq)) return e;
+    if (int e = reserve(status, (size_t)nq)) return e;
     size_t lds = 0;
     const int lh = search_heap_cache_entries(lead, &lds);
     const int block = lead->ds.test_no_helper ? smplx_small_block(lead->M) : smplx_search_block(lead->M);

@@ -1,9 +1,11 @@
 // smpl_amd/csrc/space.h -- the records behind the handles of the C-ABI (include/smpl_amd.h).  smplx_space is the handle's
-// own fields (model, grid, stream, goal, scratch, counters) plus one member per concern: the lattice (lattice.h), the
-// device copy of the state table, the BFS buffers, the plain-GetSuccs speculation, the small-batch governor, the
-// step-launch switches, the attached bodies and the device-resident search.  The components are plain structs with
-// public fields; the functions that work on them take the space and live in the header of their concern
-// (bfs_host.h, device_table.h, step.h, search_host.h).  At the end: the two operations that touch several components
+// own fields (stream, model, grid, scratch, counters) plus one member per concern: the goal (goals.h), the lattice
+// (lattice.h), the device copy of the state table, the BFS buffers, the plain-GetSuccs speculation, the small-batch
+// governor, the step-launch switches, the attached bodies, the device-resident search and the lazy pair.  The components
+// are plain structs with public fields; the functions that work on them take the space and live in the header of their
+// concern (goals.h, bfs_host.h, heuristic_host.h, device_table.h, step.h, expand_entry.h, attached_host.h, search_host.h,
+// lazy.h, plan_entry.h).  Every device allocation, stream and event is held by an owner of device_mem.h: deleting the
+// space frees them; only the device image `hs`, which the kernels read, names them by plain pointers.  At the end: the two operations that touch several components
 // at once, a state joining the lattice (new_state) and a query starting over (reset_lattice).
 #pragma once
 
@@ -11,9 +13,11 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
+#include "device_mem.h"
 #include "device_types.h"
 #include "grid_handle.h"
 #include "host_core.h"
@@ -60,7 +64,7 @@ struct FrontierBatch {
     PinBuf<unsigned char> p_out;
     std::vector<int32_t> ins_items;      // K5 inserts of the requesting spaces, tagged with their query slots
     OutView dv, pv;                      // packed outputs: device block, pinned host twin
-    hipEvent_t done = nullptr;           // recorded behind the batch on its stream
+    DevEvent done;                       // recorded behind the batch on its stream
     bool zero_copy = false;              // the batch wrote its results straight into pv (single launch, no copies)
     std::chrono::steady_clock::time_point t_issue;
 };
@@ -68,7 +72,7 @@ struct FrontierBatch {
 // device copy of the state table (K5; SmplxTableDev in hs.table): the states created since the last synchronisation
 // wait in pending_ins as (query slot, id, coord[N]) triples and go up with the next frontier batch (device_table.h)
 struct DeviceTable {
-    int32_t* d_table = nullptr;
+    DevPtr<int32_t> d_table;
     size_t cap = 0, count = 0;
     size_t test_slots = 0;        // test hook: slots of the first table table_ensure allocates (0: the default)
     int64_t regrows = 0;          // times the table was outgrown (load factor above 1/2) and allocated again, every state re-inserted
@@ -79,10 +83,10 @@ struct DeviceTable {
 
 // buffers and bookkeeping of the BFS heuristic's distance field (bfs_host.h)
 struct BfsHost {
-    int32_t* d_dist = nullptr;                  // brick-major distance records (hs.bfs.dist)
-    int32_t* d_queue = nullptr;                 // brick lists of the two passes in flight
-    int32_t* d_counts = nullptr;
-    int32_t* d_brick_queued = nullptr;          // wave-per-brick mode: 2 x nbricks "queued for the next pass" words
+    DevPtr<int32_t> d_dist;                     // brick-major distance records (hs.bfs.dist)
+    DevPtr<int32_t> d_queue;                    // brick lists of the two passes in flight
+    DevPtr<int32_t> d_counts;
+    DevPtr<int32_t> d_brick_queued;             // wave-per-brick mode: 2 x nbricks "queued for the next pass" words
     int bricks[3] = {0, 0, 0};
     int64_t total = 0;                          // cells of the padded grid the API hands out (smplx_bfs_copy)
     int64_t ints = 0;                           // ints of the brick-major records on the device
@@ -140,10 +144,10 @@ struct StepLaunch {
     // on.  A set is all-zero whenever no step is in flight on its stream: k_pipe_finish clears its part behind its last
     // reader, the last block of k_step_block its own.  dirty: a launch sequence on it failed part-way, it is cleared before
     // its next use.
-    struct WorkCounters { hipStream_t stream; int32_t* p; bool dirty; };
+    struct WorkCounters { hipStream_t stream; DevPtr<int32_t> p; bool dirty; };
     std::vector<WorkCounters> work_counters;
     // optional per-kernel timing of expand launches (bench.py roofline): 3 events per launch
-    std::vector<hipEvent_t> prof_events;
+    std::vector<DevEvent> prof_events;
     size_t prof_used = 0;
 };
 
@@ -158,7 +162,7 @@ struct AttachedBodies {
         int first = 0, count = 0;          // its nodes in the device image
     };
     std::vector<Body> bodies;
-    SmplxBodiesDev* d_bodies = nullptr;
+    DevPtr<SmplxBodiesDev> d_bodies;
     WorkSpace vox;                     // of the voxeliser for objects attached by shape (object_sphere_rows.h), like the grid's
     uint64_t epoch = 0;                // attaches + detaches so far
     uint64_t epoch_goal = 0;           // ... when the goal was set: the successor caches belong to that set of bodies
@@ -186,12 +190,23 @@ struct LazyHost {
     int64_t counters[6] = {0, 0, 0, 0, 0, 0};
 };
 
+// the goal as the host holds it (goals.h; the device's record is hs.goal), and the start's position
+struct GoalHost {
+    bool set = false;
+    uint64_t grid_epoch = 0;     // the grid's edit count when the goal was set: the successor caches belong to that field
+    double xyz[3] = {0, 0, 0};
+    double rpy[3] = {0, 0, 0};   // of a pose goal (SMPLX_GOAL_XYZ_RPY), as the caller gave them
+    double rpy_tol = 0;
+    double rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // the goal rotation the Euclidean heuristic measures against (SmplxHeurDev::rot)
+    double start_xyz[3] = {0, 0, 0};   // planning-link position of the start state (getMetricStartDistance)
+};
+
 struct Search;   // the host-driven ARA* (ara_search.h)
 
 // the device-resident ARA* of a query (search_host.h)
 struct DevSearch {
-    unsigned char* arena = nullptr;      // one allocation carved into the buffers of SmplxSearchDev
-    SmplxSearchDev* d_hdr = nullptr;
+    DevPtr<unsigned char> arena;         // one allocation carved into the buffers of SmplxSearchDev
+    DevPtr<SmplxSearchDev> d_hdr;
     SmplxSearchDev h;                    // host copy of the header: pointers, capacities, and the last state read back
     struct Caps { int states = 0, heap = 0, incons = 0, log = 0, succ = 0, path = 0; } caps;
     int dev_states = 0;                  // ids [0, dev_states) exist on the device
@@ -219,8 +234,10 @@ struct smplx_space {
     smplx::HostActions actions;
     smplx_params params;
     SmplxSpaceDev hs;
-    SmplxSpaceDev* d_space = nullptr;
-    hipStream_t stream = nullptr;
+    // before every member that owns device memory, so that it dies after them: members go in reverse order, and every
+    // buffer and event below is freed while the stream still exists.  smplx_space_destroy waits for it first.
+    DevStream stream;
+    DevPtr<SmplxSpaceDev> d_space;
     int device = 0;   // HIP device the handle lives on (worker threads select it explicitly)
     int N = 0, M = 0;
     size_t lds_bytes = 0, blob_bytes = 0;
@@ -229,13 +246,7 @@ struct smplx_space {
     int lds_nroot = 0;   // root-position slots per thread in LDS: none in the per-robot build (they live in registers there)
     smplx::KernelSet ks;       // per-robot kernels (specialize.h), generic ones with SMPLX_SPACE_GENERIC_KERNELS or SMPLX_SPECIALIZE=0
     std::string specialize_note;   // why the per-robot build is absent, if it is
-    bool goal_set = false;
-    uint64_t grid_epoch = 0;         // the grid's edit count when the goal was set: the successor caches belong to that field
-    double goal_xyz[3] = {0, 0, 0};
-    double goal_rpy[3] = {0, 0, 0};   // of a pose goal (SMPLX_GOAL_XYZ_RPY), as the caller gave them
-    double goal_rpy_tol = 0;
-    double goal_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};   // the goal rotation the Euclidean heuristic measures against (SmplxHeurDev::rot)
-    double start_xyz[3] = {0, 0, 0};   // planning-link position of the start state (getMetricStartDistance)
+    GoalHost goal;
     int status = SMPLX_OK;            // sticky: first error of a call that has no way to report one (smplx_space_status)
     std::string status_msg;
     // scratch of the C-ABI entry points
@@ -269,6 +280,8 @@ struct smplx_space {
     DevSearch ds;
     LazyHost lazy;
 };
+static_assert(!std::is_copy_constructible<smplx_space>::value && !std::is_copy_assignable<smplx_space>::value,
+              "a space owns its stream and its device memory");
 
 namespace {
 

@@ -176,12 +176,12 @@ int work_counters_for(smplx_space* s, hipStream_t stream, StepLaunch::WorkCounte
 {
     for (StepLaunch::WorkCounters& w : s->step.work_counters)
         if (w.stream == stream) { *out = &w; return SMPLX_OK; }
-    int32_t* p = nullptr;
-    HIP_TRY(hipMalloc((void**)&p, SMPLX_WORK_COUNTER_BYTES));
+    DevPtr<int32_t> p;
+    HIP_TRY(p.alloc(SMPLX_WORK_COUNTER_BYTES / sizeof(int32_t)));
     hipError_t e = hipMemsetAsync(p, 0, SMPLX_WORK_COUNTER_BYTES, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { (void)hipFree(p); return set_error(SMPLX_E_HIP, std::string("work-list counters: ") + hipGetErrorString(e)); }
-    s->step.work_counters.push_back({stream, p, false});
+    if (int c = hip_status(e, "work-list counters")) return c;
+    s->step.work_counters.push_back({stream, std::move(p), false});
     *out = &s->step.work_counters.back();
     return SMPLX_OK;
 }
@@ -203,7 +203,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
     const int32_t* ins_items = a.k5 && s->dt.d_table ? a.k5->items : nullptr;
     const int n_ins = ins_items ? a.k5->n_items : 0;
     if (s->step.work_list_items > 0) k.capacity = s->step.work_list_items;   // test hook: almost every edge overflows into the deferred pass
-    hipEvent_t* ev = nullptr;
+    DevEvent* ev = nullptr;
     if (s->step.prof_used + 3 <= s->step.prof_events.size()) { ev = &s->step.prof_events[s->step.prof_used]; s->step.prof_used += 3; }
     const int bs = blocks_for(B, SMPLX_BLOCK);
     const int be = blocks_for((long long)B * s->M, SMPLX_BLOCK);
@@ -244,7 +244,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         if (n_ins > 0) {
             hipLaunchKernelGGL(k_table_insert, dim3(blocks_for(n_ins, SMPLX_BLOCK)), dim3(SMPLX_BLOCK), 0, a.stream, s->d_space, a.stab, ins_items, n_ins, s->N);
         }
-        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space) + offsetof(SmplxSpaceDev, model_blob);
+        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space.p) + offsetof(SmplxSpaceDev, model_blob);
         KLAUNCH(s, K_STEP_BLOCK, k_step_block, dim3(be), dim3(SMPLX_STEP_BLOCK), s->step.one_launch_lds, a.stream, s->d_space, a.q, B,
                            a.flags, a.coord, a.sq, a.h, a.cost, a.lookups, a.counters, a.stab, a.state_q, d_id, cmp, wc->p,
                            s->M, s->N, blob, (int)s->blob_bytes);
@@ -287,7 +287,7 @@ int launch_expand(smplx_space* s, const ExpandArgs& a)
         const int bc = blocks_for((long long)B + (long long)B * s->M * 3, SMPLX_BLOCK);
         // the model image (inside the space record) and its size go to the collision blocks as arguments: their copy of
         // it starts beside the shard counters, not behind a load of the header's size field
-        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space) + offsetof(SmplxSpaceDev, model_blob);
+        const unsigned char* blob = reinterpret_cast<const unsigned char*>(s->d_space.p) + offsetof(SmplxSpaceDev, model_blob);
         KLAUNCH(s, K_PIPE_CONFIGS, k_pipe_configs, dim3(bc + be), dim3(SMPLX_BLOCK), s->lds_bytes_valid, a.stream, s->d_space, a.q, B,
                            a.sq, k.edge_w, k.edge_lookups, k.edge_bad, k.state_lookups, k.state_bad, k.work, k.work_count,
                            k.capacity, bc, a.flags, k.succ_coord, a.stab, a.state_q, d_id ? 1 : 0, k.succ_eval, k.succ_goal,
@@ -309,15 +309,15 @@ int reserve_expand(smplx_space* s, int B)
 {
     const size_t BM = (size_t)B * s->M;
     int e;
-    if ((e = s->batch.b_q.reserve((size_t)B * s->N))) return e;
-    if ((e = s->batch.b_work.reserve(expand_work_bytes(B, s->M, s->N)))) return e;
-    if ((e = s->b_flags.reserve(BM))) return e;
-    if ((e = s->b_coord.reserve(BM * s->N))) return e;
-    if ((e = s->b_sq.reserve(BM * s->N))) return e;
-    if ((e = s->b_h.reserve(BM))) return e;
-    if ((e = s->batch.b_cost.reserve(BM))) return e;
-    if ((e = s->batch.b_lookups.reserve(BM))) return e;
-    if ((e = s->b_counters.reserve(counter_words(B, s->M)))) return e;
+    if ((e = reserve(s->batch.b_q, (size_t)B * s->N))) return e;
+    if ((e = reserve(s->batch.b_work, expand_work_bytes(B, s->M, s->N)))) return e;
+    if ((e = reserve(s->b_flags, BM))) return e;
+    if ((e = reserve(s->b_coord, BM * s->N))) return e;
+    if ((e = reserve(s->b_sq, BM * s->N))) return e;
+    if ((e = reserve(s->b_h, BM))) return e;
+    if ((e = reserve(s->batch.b_cost, BM))) return e;
+    if ((e = reserve(s->batch.b_lookups, BM))) return e;
+    if ((e = reserve(s->b_counters, counter_words(B, s->M)))) return e;
     return SMPLX_OK;
 }
 
@@ -429,13 +429,13 @@ int issue_frontier(smplx_space* lead, FrontierBatch& fb, smplx_space* const* spa
     const size_t staged = total * N + (fb.ins_items.size() + 1) / 2;   // doubles: the parents, then the inserts
     const size_t out_bytes = carve_out(nullptr, BM, N).bytes;
     int e;
-    if ((e = fb.b_q.reserve(staged)) || (e = fb.p_q.reserve(staged)) || (e = fb.b_work.reserve(expand_work_bytes(B, M, (int)N))) ||
-        (e = fb.b_cost.reserve(BM)) || (e = fb.b_lookups.reserve(BM)) || (e = fb.b_out.reserve(out_bytes)) ||
-        (e = fb.p_out.reserve(out_bytes)))
+    if ((e = reserve(fb.b_q, staged)) || (e = reserve(fb.p_q, staged)) || (e = reserve(fb.b_work, expand_work_bytes(B, M, (int)N))) ||
+        (e = reserve(fb.b_cost, BM)) || (e = reserve(fb.b_lookups, BM)) || (e = reserve(fb.b_out, out_bytes)) ||
+        (e = reserve(fb.p_out, out_bytes)))
         return e;
-    if (stab && ((e = fb.b_stateq.reserve(total)) || (e = fb.p_stateq.reserve(total)))) return e;
+    if (stab && ((e = reserve(fb.b_stateq, total)) || (e = reserve(fb.p_stateq, total)))) return e;
     // a cross-query batch keeps no tallies: they would mix the queries
-    if (!stab && (e = lead->b_counters.reserve(counter_words(B, M)))) return e;
+    if (!stab && (e = reserve(lead->b_counters, counter_words(B, M)))) return e;
     fb.dv = carve_out(fb.b_out.p, BM, N);
     fb.pv = carve_out(fb.p_out.p, BM, N);
     size_t row = 0;

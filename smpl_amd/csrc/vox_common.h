@@ -34,12 +34,11 @@ double g_vox_kernel_ms = 0.0;
 
 // with the test hook on, the time between begin() and end() is added to g_vox_kernel_ms; end() also reports launch errors
 struct VoxTimer {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~VoxTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    DevEvent a, b;
     hipError_t begin()
     {
         if (!g_vox_timing) return hipSuccess;
-        if (!a) { if (hipError_t e = hipEventCreate(&a)) return e; if (hipError_t e = hipEventCreate(&b)) return e; }
+        if (!a) { if (hipError_t e = a.create()) return e; if (hipError_t e = b.create()) return e; }
         return hipEventRecord(a, 0);
     }
     hipError_t end()
