@@ -19,6 +19,18 @@ namespace {
 
 constexpr int kBfsHistory = 2048;   // passes whose queue sizes are kept behind the counters (d_counts)
 
+// The most passes after which a run can still have a brick queued.  A cell d hops from the goal has its final value after
+// pass d + 1: its neighbour at d - 1 hops got its own in some pass p <= d, by a visit that either held both cells (a visit
+// relaxes its brick to a fixed point) or found that the cell's brick could improve and queued it for pass p + 1, which read
+// the neighbour's final value.  Once every cell is final a visit improves nothing and queues nothing, so the bricks queued by
+// pass dmax + 1 (dmax: the greatest hop count) are the last: nothing is queued after pass dmax + 2.  A path visits no cell
+// twice, so dmax is below the number of cells of the grid.  The count cannot be tied to the bricks alone: a corridor one cell
+// wide can cross the face between two bricks once for each of its rows, and a value crosses one face per visit -- a
+// serpentine of 300 bricks needs over 2 500 passes.  Beyond the bound a run has failed to converge, which the sweep's monotone
+// relaxation rules out; the guard turns a fault of that kind into an error instead of an endless loop.  It is a last resort:
+// at 512^3 the bound is 1.3e8 passes, minutes of launches before the error.
+inline long long bfs_pass_bound(const smplx_grid* g) { return (long long)g->n[0] * g->n[1] * g->n[2] + 2; }
+
 // the cell of a goal position in the space's grid (BFS_3D::run's argument); false: outside the grid (bfs3d.cpp:169-171)
 bool bfs_goal_cell(const smplx_space* s, const double xyz[3], int c[3])
 {
@@ -115,8 +127,7 @@ int run_bfs(smplx_space* s, const double xyz[3])
         if (pending == 0) break;
         if (!dbg) chunk = pending < 256 ? 4 : 16;
         wave_grid = pending < 256 ? std::min(wave_grid_max, 2048) : wave_grid_max;
-        // (a label-correcting brick sweep can legitimately need on the order of nbricks passes on maze-like free space)
-        if (pass > 4 * nbricks + 1024) return set_error(SMPLX_E_HIP, "BFS did not terminate");
+        if ((long long)pass > bfs_pass_bound(s->grid)) return set_error(SMPLX_E_HIP, "BFS did not terminate");
     }
     s->bfs.queue_sizes.assign(cnt.begin() + 3 * kShards * 32, cnt.begin() + 3 * kShards * 32 + std::min(pass, kBfsHistory));
     s->bfs.levels = pass;
@@ -186,6 +197,8 @@ int run_bfs_multi(smplx_space* const* spaces, int nq)
         return std::min(wave_grid_max, std::max(wave_grid_min, 2 * m));
     };
     std::vector<int32_t> stats((size_t)2 * n_stats);
+    long long pass_bound = 0;     // (the spaces have the same bricks per axis, not necessarily the same cells)
+    for (int q = 0; q < nq; ++q) pass_bound = std::max(pass_bound, bfs_pass_bound(spaces[q]->grid));
     int pass = 0;
     while (true) {
         const auto tp0 = std::chrono::steady_clock::now();
@@ -206,8 +219,7 @@ int run_bfs_multi(smplx_space* const* spaces, int nq)
                     1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tp0).count(), visited, nq, (int)stats[(size_t)2 * last + 1]);
         if (visited == 0) break;      // it queued nothing either: every goal's front has died out
         if (!dbg) chunk = visited < 256 ? 4 : 16;
-        // (a label-correcting brick sweep can legitimately need on the order of nbricks passes on maze-like free space)
-        if (pass > 4 * nbricks + 1024) return set_error(SMPLX_E_HIP, "BFS did not terminate");
+        if ((long long)pass > pass_bound) return set_error(SMPLX_E_HIP, "BFS did not terminate");
     }
     // the launch-size hint of each space's next run, single or shared: the per-pass maxima of this one
     std::vector<int32_t> sizes((size_t)std::min(pass, kBfsHistory));

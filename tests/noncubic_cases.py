@@ -213,6 +213,9 @@ def _offsets(shape):
     return [a * dxy + b * dx + c for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1) if (a, b, c) != (0, 0, 0)]
 
 
+neighbour_offsets = _offsets       # for the other case files
+
+
 def deque_flood(dist, start):
     """26-connected flood of the UNREACHED cells of the padded array from flat index `start` (its value is 0 already)"""
     d = dist.reshape(-1).tolist()
