@@ -8,14 +8,20 @@
 //   planning   the third wave is the goal-distance wave of k_pipe_setup (lane-parallel sincos -> the states' rows of sines
 //              and cosines in LDS -> the chain); beside it the edge lanes run pipe_edge_values in registers and, per-robot
 //              build, discretise an edge within limits
-//   gate       one compare with the distance in LDS; per-robot build: the rest of k_pipe_configs' successor role for an
-//              edge that is active and within limits -- the loads of its home slot in the state table issued, chain, goal
-//              test, heuristic, then the table id from the slot that has arrived meanwhile; successor joint values,
-//              waypoint counts and their prefix to LDS
-//   collision  every thread takes items t, t + blockDim.x, ... of n_states + sum(W - 1): the block's states at alpha 0,
-//              then (edge, waypoint) found by a search over the prefix; one item is the fast path of k_pipe_configs.  No
-//              list, hence no capacity, no deferred edge and no whole-edge walk.  Every waypoint is examined, as on the
-//              pipeline: the lookup tally of a colliding edge equals the pipeline's
+//   gate       one compare with the distance in LDS; successor joint values, waypoint counts and their prefix to LDS
+//   successor  per-robot build, edge lanes only, behind the prefix's barrier: the rest of k_pipe_configs' successor role for
+//              an edge that is active and within limits -- the loads of its home slot in the state table issued, chain, goal
+//              test, heuristic, then the table id from the slot that has arrived meanwhile.  Only the verdict reads what it
+//              leaves, so the goal-distance wave does not wait for it: that wave enters the collision phase at once
+//   collision  n_states + sum(W - 1) items: the block's states at alpha 0, then (edge, waypoint) found by a search over the
+//              prefix; one item is the fast path of k_pipe_configs.  Items are dealt in chunks of 64: chunk c goes to wave
+//              NW - 1 - (c mod NW), NW = blockDim.x / 64, and a lane takes its lane's item of each of its wave's chunks.  The
+//              goal-distance wave (wave NW - 1) is dealt first because it starts a successor evaluation ahead of the others:
+//              at NW = 3 it owns chunks 0, 3, ..., so the ragged fourth chunk of a block of 193 .. 256 items runs beside the
+//              edge waves' successor evaluation and first chunk, not behind them on a wave the other two wait for.  One static
+//              rule: no claim counter, and no wave waits for another except at the barriers.  No list, hence no capacity, no
+//              deferred edge and no whole-edge walk.  Every waypoint is examined, as on the pipeline: the lookup tally of a
+//              colliding edge equals the pipeline's (integer adds: their order does not matter)
 //   verdict    edge lanes: k_pipe_finish's verdict, outputs, ballot compaction, tally_block
 // A state whose edges straddle two blocks has its distance and its own check computed by both (same inputs, same
 // instructions, same bits); what is per state in the tallies is counted by the owner of its primitive 0.
@@ -183,29 +189,6 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
 #pragma unroll
                 for (int v = 0; v < CM_NV; ++v) { s_sq[v * BLOCK + t] = sqv[v]; out_q[tid * CM_NV + v] = sqv[v]; }
             }
-#ifndef ABL_NO_SUCC
-            // the rest of the successor role of k_pipe_configs, behind the gate, for an edge that is active and within
-            // limits: the home slot's loads, which travel during the chain, planning-link FK, goal test, heuristic, table id.
-            // (With the chain in front of the gate too, beside the distance chain, every wave pays the seven sincos rounds of
-            // its snap edges, active or not: 31.3 against 30.0 us a step.  Cutting the heuristic into a load here and its cost
-            // in the verdict hid nothing: the compiler waits for the load where the edge lanes' branch rejoins.)
-            if (flags == 0) {
-                constexpr bool SC = CM_PARENT_TRIG && CM_TRIG_PLANNING != 0;
-                const SmplxBfsDev sbfs = Sq->bfs;
-                const TableSlotWords home = table_probe_issue(table, scv, CM_NV);
-                if constexpr (SC) {
-                    double prow[2 * CM_NV], sn[CM_NV], cs[CM_NV];
-#pragma unroll
-                    for (int j = 0; j < 2 * CM_NV; ++j) prow[j] = s_trig[ks * SMPLX_TRIG_ROW + 2 * CM_NV + j];
-                    parent_trig<CM_TRIG_PLANNING, true>(sqv, pqv, prow, sn, cs);
-                    succ_h = successor_goal_h<true>(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal, sn, cs);
-                } else {
-                    succ_h = successor_goal_h(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal);
-                }
-                // the home slot arrived during the chain: the id costs one wait, and more only where the probe walks on
-                succ_id = table_probe_resolve(table, scv, CM_NV, home);
-            }
-#endif
 #else
             flags = pipe_edge_values(M, A, Sq, pi, Q + (int64_t)si * nv, out_q + tid * nv, W);
 #endif
@@ -224,14 +207,46 @@ k_step_block(const SmplxSpaceDev* __restrict__ S, const double* __restrict__ Q, 
         if (lane == 63) s_wsum[wv] = incl;
     }
     __syncthreads();
-    // collision: items [0, n_states) are the block's states (waypoint 0 of every edge), the rest (edge, waypoint)
+#if defined(SMPLX_CONST_MODEL) && !defined(ABL_NO_SUCC)
+    // the rest of the successor role of k_pipe_configs, for an edge that is active and within limits: the home slot's
+    // loads, which travel during the chain, planning-link FK, goal test, heuristic, table id.  It stands behind the item
+    // prefix, not in front of it: no item reads what it leaves (the verdict does), and the goal-distance wave, which has no
+    // edge, is a successor evaluation ahead of the edge waves in the item loop.
+    // (With the chain in front of the gate too, beside the distance chain, every wave pays the seven sincos rounds of
+    // its snap edges, active or not: 31.3 against 30.0 us a step.  Cutting the heuristic into a load here and its cost
+    // in the verdict hid nothing: the compiler waits for the load where the edge lanes' branch rejoins.)
+    if (in_range && flags == 0) {
+        constexpr bool SC = CM_PARENT_TRIG && CM_TRIG_PLANNING != 0;
+        const SmplxBfsDev sbfs = Sq->bfs;
+        const TableSlotWords home = table_probe_issue(table, scv, CM_NV);
+        if constexpr (SC) {
+            double prow[2 * CM_NV], sn[CM_NV], cs[CM_NV];
+#pragma unroll
+            for (int j = 0; j < 2 * CM_NV; ++j) prow[j] = s_trig[ks * SMPLX_TRIG_ROW + 2 * CM_NV + j];
+            parent_trig<CM_TRIG_PLANNING, true>(sqv, pqv, prow, sn, cs);
+            succ_h = successor_goal_h<true>(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal, sn, cs);
+        } else {
+            succ_h = successor_goal_h(M, Sq->goal, sbfs, grid, sqv, scv, succ_goal);
+        }
+        // the home slot arrived during the chain: the id costs one wait, and more only where the probe walks on
+        succ_id = table_probe_resolve(table, scv, CM_NV, home);
+    }
+#endif
+    // collision: items [0, n_states) are the block's states (waypoint 0 of every edge), the rest (edge, waypoint).  Chunk c
+    // holds items [64 c, 64 c + 64) and goes to wave NW - 1 - (c mod NW): lane l of wave w takes items 64 (NW - 1 - w) + l,
+    // + NT, ...  The goal-distance wave is wave NW - 1: it owns chunk 0 (the states, whose rows it wrote itself) and the
+    // chunk behind every NW, so a block of NT + 1 .. NT + 64 items has its ragged last chunk on the wave that started first.
     {
         int wave_first[BLOCK / 64 + 1];
         wave_first[0] = 0;
 #pragma unroll
         for (int k = 0; k < BLOCK / 64; ++k) wave_first[k + 1] = wave_first[k] + s_wsum[k];
+#ifdef ABL_ONE_TURN
+        const int total = min(n_states + wave_first[BLOCK / 64], NT);   // diagnostic: prices the turns behind the first
+#else
         const int total = n_states + wave_first[BLOCK / 64];
-        for (int i = t; i < total; i += NT) {
+#endif
+        for (int i = 64 * (NT / 64 - 1 - wv) + lane; i < total; i += NT) {
             const bool is_state = i < n_states;
             int k = i, edge = 0, wp = 0, Wi = 0;
             if (!is_state) {
