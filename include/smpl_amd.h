@@ -809,6 +809,26 @@ enum {
 int smplx_post_process_path(smplx_space* s, const double* path, int n, int flags, double* out, int cap, int* nout,
                             int64_t* stats);
 
+/* The same for nq paths in one call, in a bounded number of launches: for every k the points of output path k are
+ * byte-identical to what smplx_post_process_path(spaces[k], path k, flags) returns, in every flag combination.
+ * paths: first[nq] points of nvars doubles, back to back; first: nq + 1 offsets in points, first[0] == 0, non-decreasing.
+ * out: room for cap points, may be NULL to ask the sizes; out_first: nq + 1 offsets into out, filled on SMPLX_OK and on
+ * SMPLX_E_LIMIT (out given and out_first[nq] > cap: out is untouched).
+ * A space may appear several times.  The spaces may differ in their attached bodies -- each path is checked with its own
+ * space's -- but share one grid handle, one model image (robot, padding) and one kernel build (SMPLX_SPACE_GENERIC_KERNELS
+ * alike); primitives and heuristic kind do not matter.  Anything else, a null pointer, nq < 0, bad offsets or a value
+ * that is not finite with |q| < 1e6 is SMPLX_E_ARG, and nothing is written.  nq == 0 is SMPLX_OK.
+ * The call needs no goal, is not refused after a grid edit or an attach, and leaves the lattices, the caches and a search
+ * that smplx_replan may resume untouched; it uses the stream of spaces[0] and scratch of its own there.
+ * The shortcut loop of every path runs to its end in one kernel, one workgroup a path (csrc/path_kernels.h k_shortcut); each
+ * interpolation pass checks all waypoints of all paths in one launch.  A workgroup that exceeds the loop's trip bound
+ * (2P + 2 for a path of P points) stops and the call returns SMPLX_E_HIP.
+ * stats (may be NULL): [0] kernel launches, [1] host waits (stream synchronisations), [2] configurations checked on the
+ * device, [3] paths.  [0] and [1] never exceed SMPLX_PP_MULTI_MAX_LAUNCHES, whatever nq and the path lengths are. */
+#define SMPLX_PP_MULTI_MAX_LAUNCHES 3
+int smplx_post_process_paths(smplx_space* const* spaces, int nq, const double* paths, const int32_t* first, int flags, double* out,
+                             int cap, int32_t* out_first, int64_t* stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -980,4 +980,44 @@ inline bool PostProcessPath(GpuPlanningContext* ctx, std::vector<RobotState>& pa
     return true;
 }
 
+// PostProcessPath for many paths in one call (smplx_post_process_paths): paths[k] is processed in ctxs[k], whose spaces
+// share a grid and a robot model (a context may appear several times); every path comes out as PostProcessPath gives it.
+// The shortcut loops run on the device, one workgroup a path, in a number of launches that does not depend on the batch.
+// stats (may be null): the four counters of smplx_post_process_paths.
+inline bool PostProcessPaths(const std::vector<GpuPlanningContext*>& ctxs, std::vector<std::vector<RobotState>>& paths,
+                             bool shortcut_path, bool interpolate_path, bool upstream_limit_test = false, int64_t* stats = nullptr)
+{
+    if (ctxs.size() != paths.size()) return false;
+    const int nq = (int)paths.size();
+    if (nq == 0) return true;
+    const int N = ctxs[0]->nvars();
+    std::vector<smplx_space*> spaces(nq);
+    std::vector<int32_t> first(nq + 1, 0), out_first(nq + 1, 0);
+    for (int k = 0; k < nq; ++k) {
+        if (!ctxs[k]) return false;
+        spaces[k] = ctxs[k]->space();
+        first[k + 1] = first[k] + (int32_t)paths[k].size();
+    }
+    std::vector<double> in((size_t)first[nq] * N + 1);
+    for (int k = 0; k < nq; ++k)
+        for (size_t i = 0; i < paths[k].size(); ++i) {
+            if ((int)paths[k][i].size() != N) return false;
+            std::copy(paths[k][i].begin(), paths[k][i].end(), in.begin() + ((size_t)first[k] + i) * N);
+        }
+    const int flags = (shortcut_path ? SMPLX_PP_SHORTCUT : 0) | (interpolate_path ? SMPLX_PP_INTERPOLATE : 0) |
+                      (upstream_limit_test ? SMPLX_PP_UPSTREAM_LIMITS : 0);
+    if (smplx_post_process_paths(spaces.data(), nq, in.data(), first.data(), flags, nullptr, 0, out_first.data(), nullptr) != SMPLX_OK)
+        return false;
+    std::vector<double> out((size_t)std::max(out_first[nq], 1) * N);
+    if (smplx_post_process_paths(spaces.data(), nq, in.data(), first.data(), flags, out.data(), out_first[nq], out_first.data(), stats) !=
+        SMPLX_OK)
+        return false;
+    for (int k = 0; k < nq; ++k) {
+        paths[k].clear();
+        for (int i = out_first[k]; i < out_first[k + 1]; ++i)
+            paths[k].emplace_back(out.begin() + (size_t)i * N, out.begin() + (size_t)(i + 1) * N);
+    }
+    return true;
+}
+
 }  // namespace smpl_amd

@@ -50,6 +50,7 @@ SYMBOLS = [
     "smplx_set_euclid_weights", "smplx_metric_goal_distance", "smplx_pose_distance", "smplx_joint_distance",
     "smplx_space_heuristic",
     "smplx_attach_object", "smplx_object_spheres",
+    "smplx_post_process_paths",
 ]
 
 # SMPLX_ATTACHED_SPHERE_RADIUS (include/smpl_amd.h): the reference's radius of an attached object's spheres
@@ -212,6 +213,52 @@ def table_probe(nvars, slots, one_home, inserted, queries):
     _chk(lib().smplx_test_table_probe(nvars, slots, int(bool(one_home)), _p(a, _ip), a.shape[0], _p(q, _ip), q.shape[0],
                                       _p(found, _ip), _p(ids, _ip)))
     return found, ids
+
+
+# SMPLX_PP_MULTI_MAX_LAUNCHES (include/smpl_amd.h): the most launches, and the most host waits, of one post_process_paths call
+PP_MULTI_MAX_LAUNCHES = 3
+
+
+def _post_process_paths_fn():
+    f = lib().smplx_post_process_paths
+    f.argtypes = [C.POINTER(C.c_void_p), C.c_int, _dp, _ip, C.c_int, _dp, C.c_int, _ip, C.POINTER(C.c_int64)]
+    return f
+
+
+def post_process_paths(spaces, paths, shortcut=True, interpolate=True, upstream_limits=False):
+    """smplx_post_process_paths: PlannerInterface::postProcessPath of paths[k] in spaces[k], all in one call.
+    Returns (list of arrays, stats)."""
+    nq = len(spaces)
+    assert len(paths) == nq
+    N = spaces[0].N if nq else 1
+    P = [np.ascontiguousarray(p, np.float64).reshape(-1, N) for p in paths]
+    first = np.zeros(nq + 1, np.int32)
+    for k, p in enumerate(P):
+        first[k + 1] = first[k] + p.shape[0]
+    flat = np.ascontiguousarray(np.vstack(P + [np.zeros((1, N))]))     # (never empty: a pointer to pass)
+    flags = (1 if shortcut else 0) | (2 if interpolate else 0) | (4 if upstream_limits else 0)
+    H = (C.c_void_p * max(nq, 1))(*[sp.h for sp in spaces])
+    of = np.zeros(nq + 1, np.int32); st = (C.c_int64 * 4)()
+    f = _post_process_paths_fn()
+    _chk(f(H, nq, _p(flat, _dp), _p(first, _ip), flags, None, 0, _p(of, _ip), st))
+    out = np.zeros((max(int(of[nq]), 1), N))
+    _chk(f(H, nq, _p(flat, _dp), _p(first, _ip), flags, _p(out, _dp), out.shape[0], _p(of, _ip), st))
+    return ([out[of[k]:of[k + 1]].copy() for k in range(nq)],
+            dict(launches=st[0], waits=st[1], configs=st[2], paths=st[3]))
+
+
+def path_waypoints(space, a, b):
+    """Test hook (csrc/test_hooks.h smplx_test_path_waypoints): for the edges a[i] -> b[i], the joint values the lanes of
+    k_shortcut check, in rows sized by smplx_cc_interpolate's counts.  Returns (list of arrays, the device's counts)."""
+    a = _f64(a).reshape(-1, space.N); b = _f64(b).reshape(-1, space.N)
+    n = a.shape[0]
+    first = np.zeros(n + 1, np.int32)
+    for i in range(n):
+        first[i + 1] = first[i] + space.interpolate(a[i], b[i], cap=1)[1]
+    out = np.zeros((max(int(first[n]), 1), space.N)); counts = np.zeros(n, np.int32)
+    lib().smplx_test_path_waypoints.argtypes = [C.c_void_p, _dp, _dp, C.c_int, _ip, _dp, _ip]
+    _chk(lib().smplx_test_path_waypoints(space.h, _p(a, _dp), _p(b, _dp), n, _p(first, _ip), _p(out, _dp), _p(counts, _ip)))
+    return [out[first[i]:first[i + 1]].copy() for i in range(n)], counts
 
 
 # smplx_shape.type (include/smpl_amd.h)

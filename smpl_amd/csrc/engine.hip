@@ -35,6 +35,7 @@
 #include "ara_search.h"
 #include "multi_query.h"
 #include "path_tools.h"
+#include "path_multi.h"
 // the entry points, by concern
 #include "queries.h"
 #include "attached_host.h"

@@ -65,7 +65,8 @@ static inline bool smplx_step_claim_fits(long long blocks)
     X(STATE_VALID, k_state_valid) X(HEURISTIC, k_heuristic) X(SPHERE_POSITIONS, k_sphere_positions) X(SEARCH, k_search) \
     X(ATTACHED_POSITIONS, k_attached_positions) X(PLANNING_POSE, k_planning_pose) X(STEP_BLOCK, k_step_block) \
     X(STATE_CLEARANCE, k_state_clearance) X(EDGE_CLEARANCE, k_edge_clearance) X(LAZY_SUCCS, k_lazy_succs) \
-    X(TRUE_COST, k_true_cost) X(HEURISTIC_CLOSED, k_heuristic_closed)
+    X(TRUE_COST, k_true_cost) X(HEURISTIC_CLOSED, k_heuristic_closed) X(SHORTCUT, k_shortcut) X(PATHS_VALID, k_paths_valid) \
+    X(PATH_WAYPOINTS, k_path_waypoints)
 
 extern "C" {
 __global__ void k_state_prep(const SmplxSpaceDev* S, const double* Q, int B, double* goal_dist,
@@ -131,6 +132,11 @@ __global__ void k_lazy_succs(const SmplxSpaceDev* S, const double* Q, int B, uns
                              int* out_h, int* out_id);
 __global__ void k_true_cost(const SmplxSpaceDev* S, const double* Pq, const int* child_coord, const unsigned char* goal_edge, int n,
                             double* work_q, int* out_cost, int* out_prim, int* out_nmatch);
+__global__ void k_shortcut(const SmplxSpaceDev* const* stab, const double* pts, const int* first, const double* accum, int* keep_all,
+                           int* nkeep, int* err, long long* checked);
+__global__ void k_paths_valid(const SmplxSpaceDev* const* stab, const int* blocks, const double* Q, unsigned char* out);
+__global__ void k_path_waypoints(const SmplxSpaceDev* S, const double* A, const double* B, const int* first, double* out,
+                                 int* out_count);
 __global__ void k_table_insert(const SmplxSpaceDev* S, const SmplxSpaceDev* const* stab, const int* items, int n, int nvars);
 __global__ void k_bfs_metric(SmplxGridDev grid, SmplxBfsDev bfs, const double* xyz, int n, double* out);
 __global__ void k_bfs_init(SmplxGridDev g, int wall_thr, int nbx, int nby, int nbz, int* dist);

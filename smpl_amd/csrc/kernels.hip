@@ -24,6 +24,8 @@
 //   clearance_kernels.h k_state_clearance, k_edge_clearance: the clearance queries of the C-ABI
 //   lazy_kernels.h      k_lazy_succs, k_true_cost: GetLazySuccs and GetTrueCost, an expansion without its checks and the
 //                       checks of one (parent, child) pair
+//   path_kernels.h      k_shortcut, k_paths_valid, k_path_waypoints: post-processing of a batch of paths, the shortcut loop
+//                       one workgroup per path, run to the end on the device
 //   bfs_kernels.h       k_bfs_*: label-correcting 26-connected BFS over 8x8x8 bricks (bfs3d.cpp:507-547)
 //   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query; k_search_table_fill, k_heap_ops, k_table_probe_ops
 //
@@ -52,5 +54,6 @@
 #include "clearance.h"
 #include "clearance_kernels.h"
 #include "lazy_kernels.h"
+#include "path_kernels.h"
 #include "bfs_kernels.h"
 #include "search_kernel.h"

@@ -1,6 +1,6 @@
 // smpl_amd/csrc/plan_entry.h -- the lattice and planning entry points of the C-ABI: the start state, GetSuccs and its
 // lazy pair (lazy.h), the reads of the state table, smplx_plan / smplx_replan and their multi-query forms
-// (multi_query.h), the expansion log, path post-processing (path_tools.h), and the counters and test hooks of the
+// (multi_query.h), the expansion log, path post-processing (path_tools.h; a batch of paths: path_multi.h), and the counters and test hooks of the
 // device-resident search (search_host.h, test_hooks.h).
 #pragma once
 
@@ -296,6 +296,51 @@ int smplx_post_process_path(smplx_space* s, const double* path, int n, int flags
         if (np > cap) return set_error(SMPLX_E_LIMIT, "output path does not fit");
         std::memcpy(out, p.data(), sizeof(double) * p.size());
     }
+    return SMPLX_OK;
+}
+
+int smplx_post_process_paths(smplx_space* const* spaces, int nq, const double* paths, const int32_t* first, int flags, double* out,
+                             int cap, int32_t* out_first, int64_t* stats)
+{
+    if (nq < 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (nq == 0) {
+        if (out_first) out_first[0] = 0;
+        if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
+        return SMPLX_OK;
+    }
+    if (!spaces || !first || !out_first || (out && cap < 0)) return set_error(SMPLX_E_ARG, "bad argument");
+    long long total = 0;
+    if (!smplx_path_multi::check_offsets(first, nq, &total)) return set_error(SMPLX_E_ARG, "first: nq + 1 offsets, first[0] == 0, non-decreasing");
+    if (total > 0 && !paths) return set_error(SMPLX_E_ARG, "bad argument");
+    for (int k = 0; k < nq; ++k) {
+        if (!spaces[k]) return set_error(SMPLX_E_ARG, "null space");
+        if (!same_grid_and_robot(spaces[0], spaces[k])) return set_error(SMPLX_E_ARG, "the spaces of one call share a grid, a robot model and a kernel build");
+    }
+    if (total > 0 && !sane_values(paths, (size_t)total * spaces[0]->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    return post_process_paths(spaces, nq, paths, first, flags, out, cap, out_first, stats);
+}
+
+int smplx_test_path_waypoints(smplx_space* s, const double* a, const double* b, int n, const int32_t* first, double* out, int32_t* counts)
+{
+    if (!s || !a || !b || !first || !out || !counts || n <= 0) return set_error(SMPLX_E_ARG, "bad argument");
+    if (!smplx_path_multi::check_offsets(first, n, nullptr)) return set_error(SMPLX_E_ARG, "bad offsets");
+    if (!sane_values(a, (size_t)n * s->N) || !sane_values(b, (size_t)n * s->N)) return set_error(SMPLX_E_ARG, "joint values must be finite (|q| < 1e6)");
+    DevBuf<double> d_a, d_b, d_out;
+    DevBuf<int32_t> d_first, d_counts;
+    const size_t rows = (size_t)first[n];
+    int e;
+    if ((e = reserve(d_a, (size_t)n * s->N)) || (e = reserve(d_b, (size_t)n * s->N)) || (e = reserve(d_out, rows * s->N)) ||
+        (e = reserve(d_first, (size_t)n + 1)) || (e = reserve(d_counts, (size_t)n))) return e;
+    HIP_TRY(hipMemcpyAsync(d_a.p, a, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_b.p, b, sizeof(double) * n * s->N, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemcpyAsync(d_first.p, first, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(d_out.p, 0, sizeof(double) * (rows ? rows : 1) * s->N, s->stream));
+    KLAUNCH(s, K_PATH_WAYPOINTS, k_path_waypoints, dim3((unsigned)n), dim3(SMPLX_BLOCK), s->lds_bytes, s->stream, s->d_space, d_a.p, d_b.p,
+            d_first.p, d_out.p, d_counts.p);
+    HIP_TRY(hipGetLastError());
+    if (rows) HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * rows * s->N, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(counts, d_counts.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
     return SMPLX_OK;
 }
 

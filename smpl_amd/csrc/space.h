@@ -190,6 +190,16 @@ struct LazyHost {
     int64_t counters[6] = {0, 0, 0, 0, 0, 0};
 };
 
+// scratch of smplx_post_process_paths (path_multi.h), held by the call's leading space: its own buffers, like the
+// clearance queries', so that the call touches nothing a search or a frontier batch may hold between calls
+struct PathMultiHost {
+    DevBuf<const SmplxSpaceDev*> b_stab;   // per path: its space's device image
+    DevBuf<double> b_rows;                 // the rows of a pass; the points and accumulated costs of the shortcut stage
+    DevBuf<unsigned char> b_valid;
+    DevBuf<int32_t> b_ints;                // the block table of a pass; offsets, keep lists, counts and error words of the shortcut stage
+    DevBuf<long long> b_checked;
+};
+
 // the goal as the host holds it (goals.h; the device's record is hs.goal), and the start's position
 struct GoalHost {
     bool set = false;
@@ -279,6 +289,7 @@ struct smplx_space {
     AttachedBodies att;
     DevSearch ds;
     LazyHost lazy;
+    PathMultiHost pm;
 };
 static_assert(!std::is_copy_constructible<smplx_space>::value && !std::is_copy_assignable<smplx_space>::value,
               "a space owns its stream and its device memory");

@@ -77,6 +77,12 @@ int smplx_test_goal_rotation(const smplx_space* s, double R[9]);
  * build is compiled against (specialize.h kClosedFormDefine appended).  Returns the size needed, including the NUL. */
 int smplx_test_const_header(const smplx_model* m, int closed_form, char* out, int cap);
 
+/* The joint values the lanes of k_shortcut (path_kernels.h) check on the edges a[i] -> b[i], i < n: one block an edge, the
+ * waypoints dealt to its lanes as in the kernel, each written as stage_config staged it.  first: n + 1 row offsets into
+ * out (the caller's waypoint counts, smplx_cc_interpolate's); counts[i] = the device's count.  An edge writes no more rows
+ * than the caller gave it; rows it does not write stay 0. */
+int smplx_test_path_waypoints(smplx_space* s, const double* a, const double* b, int n, const int32_t* first, double* out, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif
