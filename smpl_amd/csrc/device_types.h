@@ -265,7 +265,7 @@ struct SmplxSpaceDev {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Device-resident ARA* (kernels: search_kernel.h, host side: engine.hip).  One persistent workgroup owns one
+// Device-resident ARA* (kernels: search_kernel.h with search_heap.h and search_table.h, host side: search_host.h).  One persistent workgroup owns one
 // query: OPEN (the reference's intrusive binary heap, intrusive_heap.hpp:346-395), INCONS, the state table, the search
 // states and the committed successor lists all live in HBM (the top of the heap in LDS while the kernel runs); the host
 // only launches, grows buffers when the kernel asks, and reads results.

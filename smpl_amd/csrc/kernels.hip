@@ -27,7 +27,9 @@
 //   path_kernels.h      k_shortcut, k_paths_valid, k_path_waypoints: post-processing of a batch of paths, the shortcut loop
 //                       one workgroup per path, run to the end on the device
 //   bfs_kernels.h       k_bfs_*: label-correcting 26-connected BFS over 8x8x8 bricks (bfs3d.cpp:507-547)
-//   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query; k_search_table_fill, k_heap_ops, k_table_probe_ops
+//   search_kernel.h     k_search: device-resident ARA*, one persistent workgroup per query, and the pieces of its step; it
+//                       includes search_heap.h (OPEN: the wave-parallel binary heap, k_heap_ops) and search_table.h (the
+//                       state table as the search's workgroup probes and fills it, k_search_table_fill, k_table_probe_ops)
 //
 // No MFMA: the path is integer/byte gathers from the voxel grid plus a short serial FK chain in fp64.
 // The sphere trees are staged in LDS; per-thread scratch (tree-root positions, saved link transforms,

@@ -114,8 +114,8 @@ __device__ __forceinline__ int closed_form_h(const ModelLds* __restrict__ M, con
 }
 
 // BfsHeuristic::getMetricGoalDistance (bfs_heuristic.cpp:129-138) of the state with joint values q: the gate of its
-// primitives.  The one definition for every path; goal_distance_of_h (search_kernel.h) recovers the same value from a
-// state's heuristic and must keep the same distance for an unreachable cell.
+// primitives.  The one definition for every path; goal_distance_of_h (search_kernel.h, for round_prepare) recovers the same
+// value from a state's heuristic and must keep the same distance for an unreachable cell.
 __device__ __forceinline__ double metric_goal_distance(const ModelLds* __restrict__ M, const SmplxGridDev& grid, const SmplxBfsDev& bfs,
                                                        const double* __restrict__ q)
 {

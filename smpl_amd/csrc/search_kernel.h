@@ -1,4 +1,9 @@
 // smpl_amd/csrc/search_kernel.h -- device-resident ARA* (SURVEY row N2), included at the end of kernels.hip.
+// Owns: the search state's load / store (sstate_*), SearchRegs with search_regs_load / search_regs_store, BookRegs and
+// BookOut with book_out_store / book_out_load, goal_distance_of_h, and the pieces of a step of k_search, each stated once:
+// round_prepare (an evaluation round for a parent state), search_book_table with book_find_pairs (getOrCreateState's table
+// side), open_improve_wave (the OPEN / INCONS operation of an improved successor); k_search itself.  OPEN is
+// search_heap.h (the pop: heap_pop_wave, a new epsilon: heap_rekey_block), the state table search_table.h.
 //
 //   k_search      one persistent workgroup per query: pop -> expand on the lanes -> getOrCreateState -> push / decrease.
 //                 Follows smpl/src/search/arastar.cpp:107-215 (replan), 486-527 (improvePath), 531-568 (expand),
@@ -14,15 +19,9 @@
 //                   sequential program keeps in variables lives in its registers (uniform over the lanes), per-successor data
 //                   in the lane of the primitive, and a value another lane holds is read with v_readlane -- a single lane
 //                   walking LDS-resident structures costs a ~100-cycle round trip per step, which is what round 3 first
-//                   measured (13 us of relaxation per expansion).
-//                   The sifts of the heap are wave-parallel and exact: sift-up reads ALL ancestors of the slot at once
-//                   (lane j: index >> j), a ballot finds the level the sequential loop would stop at, the ancestors below it
-//                   move down in one scatter; sift-down fetches the five levels under the pivot at once (62 lanes) and
-//                   resolves the path in registers.
+//                   measured (13 us of relaxation per expansion).  (The wave-parallel sifts of the heap: search_heap.h.)
 //   the other waves check configurations: one waypoint of one edge per lane (expand_config_lane), between the two barriers
 //                   of a step.
-// The first `lh` entries of the heap array live in LDS while the kernel runs, the rest in HBM; the HBM-resident ancestors of
-// the slots a relaxation's pushes will take are fetched into LDS in one round trip before it (written through by every sift).
 //
 // A launch runs at most `max_steps` expansions and then stores its state in the query's SmplxSearchDev, so that the host
 // sees progress, can stop a search, and can enlarge buffers (SMPLX_SS_GROW) between launches.
@@ -32,245 +31,12 @@
 #pragma once
 
 #include "small_batch.h"   // ExpandLds, expand_state_block's lane functions, SMPLX_WAVE_SYNC
+#include "search_heap.h"
+#include "search_table.h"
 
-#define SMPLX_AC_LEVELS 16
-#define SMPLX_AC_SLOTS 128
 #define SMPLX_INFINITECOST 1000000000u     // SBPL INFINITECOST
 
 enum { SA_EVAL = 0, SA_SKIP = 1, SA_REORDER = 2, SA_EXIT = 3 };
-
-// what the waves of the block share
-struct SearchLds {
-    int action;                            // the round, published before its first barrier
-    int buf;                               // ... and the ExpandLds it works on
-    int seq;                               // ... and its number
-    int helper_gave_up;                    // the helper wave's wait for `go` ran out (never seen; turns into SMPLX_SS_ERROR)
-    int go;                                // = seq once the state table holds everything committed before this round's state was
-                                           //   popped: the helper wave may probe it (the search wave sets it before it joins the round's end)
-    double reorder_eps;
-    int reorder_size, reorder_dups;
-    // ancestors of the slots the pushes of a relaxation will take, as far as they lie in HBM: level j (1 = parents) holds
-    // heap indices ac_lo[j] .. ac_hi[j] at ac_val[ac_base[j] ...]
-    int ac_nlev;
-    int ac_lo[SMPLX_AC_LEVELS + 1], ac_hi[SMPLX_AC_LEVELS + 1], ac_base[SMPLX_AC_LEVELS + 1];
-    unsigned long long ac_val[SMPLX_AC_SLOTS];
-};
-
-// a heap entry as one 64-bit word (the layout of SmplxHeapEntry: f in the low half, id in the high half): LDS and HBM
-// copies are single loads / stores
-typedef unsigned long long hent_t;
-#define HENT_ABSENT (~0ull)
-__device__ __forceinline__ unsigned int hent_f(hent_t e) { return (unsigned int)e; }
-__device__ __forceinline__ int hent_id(hent_t e) { return (int)(e >> 32); }
-__device__ __forceinline__ hent_t hent_make(unsigned int f, int id) { return (hent_t)f | ((hent_t)(unsigned int)id << 32); }
-
-// what the helper wave leaves for the search wave at the end of a round: lane = primitive
-struct BookOut {
-    int limits_ok[64], wcount[64], h[64], is_goal[64];
-    unsigned int hash[64], free_slot[64];
-    int pr_id[64], dup_of[64], clash[64];
-    int ss[8][64];                         // the successor's search state as stored (sstate_load's two 16-byte words)
-};
-
-struct HeapRef {
-    LDS_AS hent_t* lds;                    // entries [0, lh)
-    SMPLX_GLOBAL_AS hent_t* hbm;           // entries [lh, ...)
-    SMPLX_GLOBAL_AS SmplxSState* st;
-    int lh;
-};
-
-__device__ __forceinline__ hent_t hget(const HeapRef& H, int i)
-{
-    if (i < H.lh) return H.lds[i];
-    return H.hbm[i];
-}
-// the entry alone (the state's heap_index is not touched)
-__device__ __forceinline__ void hput(const HeapRef& H, int i, hent_t e)
-{
-    if (i < H.lh) H.lds[i] = e;
-    else H.hbm[i] = e;
-}
-// place an entry and record its position in the state (intrusive_heap.hpp: m_data[i] = e; e->m_heap_index = i)
-__device__ __forceinline__ void hset(const HeapRef& H, int i, hent_t e)
-{
-    hput(H, i, e);
-    H.st[hent_id(e)].heap_index = i;
-}
-
-// ---- the sequential forms (one thread): the reference's loops as they stand.  Used by the level-parallel make() and as the
-// specification of the wave-parallel forms below ----
-
-// intrusive_heap.hpp:346-377; size = number of elements (the reference's m_data.size() - 1)
-__device__ __forceinline__ void heap_percolate_down(const HeapRef& H, int pivot, int size)
-{
-    if (pivot > size) return;
-    int left = pivot << 1, right = left + 1;
-    const hent_t tmp = hget(H, pivot);
-    while (left <= size) {
-        hent_t es = hget(H, left);
-        int s = left;
-        if (right <= size) {
-            const hent_t er = hget(H, right);
-            if (!(hent_f(es) < hent_f(er))) { es = er; s = right; }
-        }
-        if (hent_f(es) < hent_f(tmp)) {
-            hset(H, pivot, es);
-            pivot = s;
-        } else break;
-        left = pivot << 1; right = left + 1;
-    }
-    hset(H, pivot, tmp);
-}
-
-// intrusive_heap.hpp:208-213 make(): percolate_down(i) for i = size/2 .. 1, by ALL threads of the block.  Nodes of one depth
-// own disjoint subtrees, so a depth is sifted by all threads at once, deepest first -- the result is the sequential
-// loop's.  With the same element twice in the array (`duplicates`) two sifts could race on its heap_index: then thread 0
-// runs the loop alone.  Ends with a barrier.
-__device__ __forceinline__ void heap_make_block(const HeapRef& H, int size, bool duplicates)
-{
-    const int t = threadIdx.x;
-    if (duplicates) {
-        if (t == 0) for (int i = size >> 1; i >= 1; --i) heap_percolate_down(H, i, size);
-        __syncthreads();
-        return;
-    }
-    int top_depth = 0;
-    while ((2 << top_depth) <= (size >> 1)) ++top_depth;      // depth of node size/2
-    for (int d = top_depth; d >= 0; --d) {
-        const int first = 1 << d;
-        int lastn = (2 << d) - 1;
-        if (lastn > (size >> 1)) lastn = size >> 1;
-        for (int i = first + t; i <= lastn; i += blockDim.x) heap_percolate_down(H, i, size);
-        __syncthreads();
-    }
-}
-
-// ---- wave-level helpers: every lane of the wave is active and `lane_index` arguments are uniform ----
-__device__ __forceinline__ int wave_rl(int v, int lane_index) { return __builtin_amdgcn_readlane(v, lane_index); }
-__device__ __forceinline__ unsigned int wave_rlu(unsigned int v, int lane_index) { return (unsigned int)__builtin_amdgcn_readlane((int)v, lane_index); }
-__device__ __forceinline__ hent_t wave_rl64(hent_t v, int lane_index)
-{
-    const unsigned int lo = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)v, lane_index);
-    const unsigned int hi = (unsigned int)__builtin_amdgcn_readlane((int)(unsigned int)(v >> 32), lane_index);
-    return (hent_t)lo | ((hent_t)hi << 32);
-}
-
-// a write to the HBM part of the heap also refreshes the ancestor cache where it holds that index
-__device__ __forceinline__ void ac_update(SearchLds& W, int i, hent_t e)
-{
-    const int nlev = W.ac_nlev;
-    for (int j = 1; j <= nlev; ++j)
-        if (i >= W.ac_lo[j] && i <= W.ac_hi[j]) { W.ac_val[W.ac_base[j] + i - W.ac_lo[j]] = e; return; }
-}
-__device__ __forceinline__ void hset_ac(const HeapRef& H, SearchLds& W, int i, hent_t e)
-{
-    if (i < H.lh) H.lds[i] = e;
-    else { H.hbm[i] = e; ac_update(W, i, e); }
-    H.st[hent_id(e)].heap_index = i;
-}
-
-// percolate_up by the whole wave (intrusive_heap.hpp:379-395): entry e sifts up from slot `start` (a push: the new last slot;
-// decrease: the entry's slot).  Lane j reads the ancestor start >> j; the sequential loop compares every ancestor IN ITS
-// ORIGINAL PLACE with e and stops at the first that is smaller, so a ballot finds that level; the ancestors below it move
-// down one level each, e takes the freed slot.  `cached` = the ancestor cache covers the walk (a push of the relaxation it
-// was built for): HBM-resident ancestors are read from LDS.
-__device__ __forceinline__ void heap_sift_up_wave(const HeapRef& H, SearchLds& W, int lane, int start, hent_t e, bool cached)
-{
-    const int j = lane;
-    const int idx = j < 31 ? (start >> j) : 0;
-    const bool anc = j >= 1 && idx >= 1;
-    hent_t ent = 0;
-    if (anc) {
-        if (idx < H.lh) ent = H.lds[idx];
-        else if (cached && j <= W.ac_nlev && idx >= W.ac_lo[j] && idx <= W.ac_hi[j]) ent = W.ac_val[W.ac_base[j] + idx - W.ac_lo[j]];
-        else ent = H.hbm[idx];
-    }
-    const unsigned long long m_anc = __ballot(anc), m_stop = __ballot(anc && hent_f(ent) < hent_f(e));
-    const int jstop = m_stop ? __ffsll((long long)m_stop) - 1 : __popcll(m_anc) + 1;   // ancestors are lanes 1 .. popc(m_anc)
-    if (!cached) {
-        if (anc && j < jstop) hset_ac(H, W, start >> (j - 1), ent);
-        if (j == 0) hset_ac(H, W, start >> (jstop - 1), e);
-        return;
-    }
-    // a walk the cache was built for: a write to level l of the walk can only concern the cache's level l (level 0, the new
-    // slots themselves, is not cached)
-    const bool mover = anc && j < jstop;
-    if (mover || j == 0) {
-        const int l = mover ? j - 1 : jstop - 1;
-        const int dst = start >> l;
-        const hent_t v = mover ? ent : e;
-        if (dst < H.lh) H.lds[dst] = v;
-        else {
-            H.hbm[dst] = v;
-            if (l >= 1 && l <= W.ac_nlev && dst >= W.ac_lo[l] && dst <= W.ac_hi[l]) W.ac_val[W.ac_base[l] + dst - W.ac_lo[l]] = v;
-        }
-        H.st[hent_id(v)].heap_index = dst;
-    }
-}
-
-// percolate_down by the whole wave (intrusive_heap.hpp:346-377): entry tmp sifts down from `pivot`.  Lanes 0 .. 61 fetch the
-// five levels under the pivot at once; the path is resolved in registers (the loop reads every child in its original place:
-// moves only ever write to slots ABOVE what is read next); the chosen entries move up in one scatter.
-__device__ __forceinline__ void heap_sift_down_wave(const HeapRef& H, int lane, int pivot, int size, hent_t tmp)
-{
-    const int lv = 31 - __clz(lane + 2);                    // level below the pivot: 1 .. 5 for lanes 0 .. 61
-    const int off = lane + 2 - (1 << lv);
-    while (true) {
-        if ((pivot << 1) > size) break;
-        const int idx = (pivot << lv) + off;
-        hent_t ent = HENT_ABSENT;
-        if (lane < 62 && idx <= size) ent = hget(H, idx);
-        int c = 0, depth = 0;
-        unsigned long long chosen = 0;
-        bool stopped = false;
-#pragma unroll
-        for (int l = 1; l <= 5; ++l) {
-            if (stopped) continue;
-            const int li = (1 << l) - 2 + 2 * c;
-            const hent_t el = wave_rl64(ent, li), er = wave_rl64(ent, li + 1);
-            if (el == HENT_ABSENT) { stopped = true; continue; }
-            const bool right = er != HENT_ABSENT && !(hent_f(el) < hent_f(er));
-            const hent_t es = right ? er : el;
-            if (!(hent_f(es) < hent_f(tmp))) { stopped = true; continue; }
-            chosen |= 1ull << (li + (right ? 1 : 0));
-            c = 2 * c + (right ? 1 : 0);
-            depth = l;
-        }
-        if ((chosen >> lane) & 1ull) hset(H, idx >> 1, ent);
-        pivot = (pivot << depth) + c;
-        if (stopped) break;
-        // the next round reads below what this one moved: nothing it reads was written
-    }
-    if (lane == 0) hset(H, pivot, tmp);
-}
-
-// ARAStar::computeKey (arastar.cpp:579-582)
-__device__ __forceinline__ unsigned int search_key(double eps, unsigned int g, unsigned int h)
-{
-    return g + (unsigned int)(long long)(eps * (double)h);
-}
-
-// Every OPEN entry of state `id` takes the state's new f (whole wave).  Only needed once a state has been pushed while
-// already in OPEN (the reference appends a state to INCONS once per improvement, arastar.cpp:563-565, and pushes every
-// INCONS entry, :180-184): its heap then holds the same element twice, and both see an f change because both point to it.
-__device__ __forceinline__ void heap_refresh_duplicates_wave(const HeapRef& H, SearchLds& W, int lane, int size, int id, unsigned int f)
-{
-    for (int i = 1 + lane; i <= size; i += 64) {
-        const hent_t e = hget(H, i);
-        if (hent_id(e) == id && hent_f(e) != f) {
-            const hent_t ne = hent_make(f, id);
-            if (i < H.lh) H.lds[i] = ne; else { H.hbm[i] = ne; ac_update(W, i, ne); }
-        }
-    }
-}
-
-__device__ __forceinline__ unsigned int coord_hash_lds(const LDS_AS int* c, int n)
-{
-    unsigned int h = 2166136261u;
-    for (int i = 0; i < n; ++i) h = (h ^ (unsigned int)c[i]) * 16777619u;
-    h ^= h >> 15; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
 
 // ARAStar::reinitSearchState (arastar.cpp:613-627) on a copy of the state; h stays (GetGoalHeuristic of a state is fixed
 // for a goal).  A state that was not touched in this call is not in OPEN: OPEN is emptied when a call starts.
@@ -284,6 +50,14 @@ __device__ __forceinline__ void sstate_reinit(SmplxSState& s, int call_number)
     s.bp = -1;
     s.heap_index = 0;
     s.flags = 0;
+}
+
+// the search state of a lane that has no successor (yet)
+__device__ __forceinline__ SmplxSState sstate_blank()
+{
+    SmplxSState s;
+    s.g = s.h = s.f = s.eg = 0; s.bp = -1; s.heap_index = 0; s.iteration_closed = 0; s.call_number = 0; s.flags = 0;
+    return s;
 }
 
 typedef table_int4 sk_int4;   // (lattice_steps.h)
@@ -310,68 +84,6 @@ __device__ __forceinline__ SmplxSState sstate_load(const SMPLX_GLOBAL_AS SmplxSS
     return s;
 }
 
-// One probe sequence of the state table with plain 16-byte loads.  Only the workgroup that owns the query writes its table
-// while the kernel runs, so what it reads is current.  table_probe_start issues the loads of the home slot (the caller
-// puts the planning-link FK between the two, for the loads to travel behind); table_probe_finish looks at them and walks on
-// if it has to.
-struct TableProbe { int id; unsigned int free_slot; };
-// (SMPLX_TABLE_WORDS, the 16-byte words of a slot: lattice_steps.h)
-// (table_slot_load and table_slot_match, the slot's loader and its compare, are shared with the step kernels: lattice_steps.h)
-typedef TableSlotWords TableProbeLoads;
-__device__ __forceinline__ TableProbeLoads table_probe_start(const SmplxTableDev& T, int nv, unsigned int hash)
-{
-    TableProbeLoads r;
-    r.slot = hash & T.mask;
-    table_slot_load(T, r.slot, nv, r.w);
-    return r;
-}
-__device__ __forceinline__ TableProbe table_probe_finish(const SmplxTableDev& T, TableProbeLoads& ld, const LDS_AS int* c, int nv)
-{
-    TableProbe r;
-    while (true) {
-        if (ld.w[0].x == 0) { r.id = -1; r.free_slot = ld.slot; return r; }
-        if (ld.w[0].x > 0 && table_slot_match(ld.w, c, nv)) { r.id = ld.w[0].x - 1; r.free_slot = 0; return r; }
-        ld.slot = (ld.slot + 1) & T.mask;
-        table_slot_load(T, ld.slot, nv, ld.w);
-    }
-}
-__device__ __forceinline__ void table_store_own(const SmplxTableDev& T, unsigned int slot, const LDS_AS int* c, int nv, int id)
-{
-    SMPLX_GLOBAL_AS int* sl = as_global(T.slots) + (size_t)slot * T.stride;
-    for (int v = 0; v < nv; ++v) sl[1 + v] = c[v];
-    sl[0] = id + 1;
-}
-
-// Ancestors of the slots n + 1 .. n + cnt (where a relaxation's pushes go) that lie beyond the LDS part of the heap: one
-// round trip, all lanes of the search wave.  Returns whether every such ancestor fits the cache.
-__device__ __forceinline__ bool ancestor_cache_fill(const HeapRef& H, SearchLds& W, int lane, int n, int cnt)
-{
-    int nlev = 0, total = 0;
-    int my_idx[2] = {-1, -1};
-    bool complete = true;
-    for (int j = 1; j <= SMPLX_AC_LEVELS; ++j) {
-        int lo = (n + 1) >> j, hi = (n + cnt) >> j;
-        if (hi > n) hi = n;
-        if (hi < H.lh || cnt == 0) break;
-        if (lo < H.lh) lo = H.lh;
-        const int len = hi - lo + 1;
-        if (total + len > SMPLX_AC_SLOTS || j == SMPLX_AC_LEVELS) { complete = false; break; }
-        if (lane == 0) { W.ac_lo[j] = lo; W.ac_hi[j] = hi; W.ac_base[j] = total; }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            const int e = lane + 64 * r - total;
-            if (e >= 0 && e < len) my_idx[r] = lo + e;
-        }
-        total += len;
-        nlev = j;
-    }
-    if (lane == 0) W.ac_nlev = nlev;
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-        if (my_idx[r] >= 0) W.ac_val[lane + 64 * r] = H.hbm[my_idx[r]];
-    return complete;
-}
-
 // the search's variables: registers of the search wave, the same value in every lane
 struct SearchRegs {
     double curr_eps, satisfied_eps;
@@ -381,6 +93,30 @@ struct SearchRegs {
     unsigned int goal_f;
     long long committed_evals, gpu_evals, lookups;
 };
+// ... as a launch finds them in the query's header, with `max_steps` expansions to go
+__device__ __forceinline__ SearchRegs search_regs_load(const SmplxSearchDev* P, int max_steps)
+{
+    SearchRegs R;
+    R.curr_eps = P->curr_eps; R.satisfied_eps = P->satisfied_eps;
+    R.heap_size = P->heap_size; R.nstates = P->nstates; R.n_incons = P->n_incons; R.n_log = P->n_log; R.n_succ = P->n_succ;
+    R.iteration = P->iteration; R.call_number = P->call_number; R.phase = P->phase; R.num = P->num;
+    R.expand_count = P->expand_count; R.expand_count_init = P->expand_count_init; R.err = P->err;
+    R.dup_pushes = P->dup_pushes; R.goal_f = P->goal_f;
+    R.committed_evals = P->committed_evals; R.gpu_evals = P->gpu_evals; R.lookups = P->lookups;
+    R.status = SMPLX_SS_RUNNING; R.grow_what = 0; R.steps_left = max_steps;
+    return R;
+}
+// ... and as it leaves them there for the host and the next launch (one lane)
+__device__ __forceinline__ void search_regs_store(SmplxSearchDev* Pd, const SearchRegs& R)
+{
+    Pd->curr_eps = R.curr_eps; Pd->satisfied_eps = R.satisfied_eps;
+    Pd->heap_size = R.heap_size; Pd->nstates = R.nstates; Pd->n_incons = R.n_incons; Pd->n_log = R.n_log; Pd->n_succ = R.n_succ;
+    Pd->iteration = R.iteration; Pd->call_number = R.call_number; Pd->phase = R.phase; Pd->num = R.num;
+    Pd->expand_count = R.expand_count; Pd->expand_count_init = R.expand_count_init; Pd->err = R.err;
+    Pd->dup_pushes = R.dup_pushes; Pd->goal_f = R.goal_f;
+    Pd->status = R.status; Pd->grow_what = R.grow_what;
+    Pd->committed_evals = R.committed_evals; Pd->gpu_evals = R.gpu_evals; Pd->lookups = R.lookups;
+}
 
 // getMetricGoalDistance recovered from a state's heuristic h = cost_per_cell * BFS distance (bfs_heuristic.cpp:129-138 /
 // 355-366: both read the BFS cell of the same planning-link position); the caller knows that the product is invertible.
@@ -388,6 +124,78 @@ struct SearchRegs {
 __device__ __forceinline__ double goal_distance_of_h(int h, int cpc, const SmplxGridDev& grid)
 {
     return h == 32767 ? (double)0x7FFFFFFF * grid.res : (double)(h / cpc) * grid.res;
+}
+
+// An evaluation round is got ready for a parent state in Y, by the whole search wave (lane v < nv brings the parent's joint
+// value `parent_q`): the parent, the verdict words cleared, the goal distance -- from the state's heuristic `h` where
+// `gd_from_h` says that it follows from it, else by lane 0 (metric_goal_distance) and a broadcast --, then per primitive
+// whether it has an action here and the successor's joint values (manip_lattice.cpp:254-270).  Returns the lane's
+// "primitive `lane` has a successor to evaluate", which Y.lookups tells the other waves.  No block barrier: opening the
+// round (W.action / W.buf / W.seq and barrier A) is the caller's.
+// In two halves, because the round of the popped state stages its parent ahead of the pop (the load of the joint values
+// travels beside the sift-down) and does the rest behind it: round_stage, then round_gate; round_prepare is both.
+// round_gate ends with the stores of Y.lookups and Y.goal_dist.  Where the popped state's round follows a wrong guess they
+// now land ahead of the barrier that ends the guessed round (they used to follow it): Y is the buffer the guessed round
+// does not use, and nobody reads it before barrier A of its own round, as for the top of OPEN's round further down.
+__device__ __forceinline__ void round_stage(ExpandLds& Y, int lane, int nv, int nprims, double parent_q)
+{
+    if (lane < nv) Y.parent[lane] = parent_q;
+    if (lane < nprims) { Y.edge_bad[lane] = 0; Y.edge_lk[lane] = 0; }
+    if (lane == 0) { Y.state_bad = 0; Y.state_lookups = 0; }
+}
+__device__ __forceinline__ bool round_gate(const ModelLds* __restrict__ M, const SmplxActionsDev& A, const SmplxGoalDev& G,
+                                              const SmplxGridDev& grid, const SmplxBfsDev& bfs, bool gd_from_h, ExpandLds& Y,
+                                              int lane, int nprims, int h)
+{
+    SMPLX_WAVE_SYNC();                               // Y.parent is complete
+    double gd;
+    if (gd_from_h) gd = goal_distance_of_h(h, bfs.cost_per_cell, grid);
+    else {
+        double g1 = 0.0;
+        if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, Y.parent);
+        gd = wave_rl_f64(g1, 0);
+    }
+    const bool in = lane < nprims;
+    const bool act = in && mprim_active(A, gd, A.type[lane]) && successor_values(M, A, G, lane, Y.parent, Y.sq[lane]);
+    if (in) Y.lookups[lane] = act ? 1 : 0;
+    if (lane == 0) Y.goal_dist = gd;
+    return act;
+}
+__device__ __forceinline__ bool round_prepare(const ModelLds* __restrict__ M, const SmplxActionsDev& A, const SmplxGoalDev& G,
+                                              const SmplxGridDev& grid, const SmplxBfsDev& bfs, bool gd_from_h, ExpandLds& Y,
+                                              int lane, int nv, int nprims, double parent_q, int h)
+{
+    round_stage(Y, lane, nv, nprims, parent_q);
+    return round_gate(M, A, G, grid, bfs, gd_from_h, Y, lane, nprims, h);
+}
+
+// Pairs among the successors of one expansion for which `member` holds (successors whose coordinate the table does not
+// know), by the whole wave: dup_of = the lowest earlier member with the lane's coordinate (that primitive creates the state),
+// else -1; clash = an earlier member that is nobody's duplicate ended its probe at the lane's empty slot.
+__device__ __forceinline__ void book_find_pairs(const ExpandLds& X, int lane, int nv, bool member, unsigned int hash,
+                                                unsigned int free_slot, int& dup_of, bool& clash)
+{
+    dup_of = -1;
+    clash = false;
+    unsigned long long members = __ballot(member);
+    while (members) {                                    // uniform
+        const int j = __ffsll((long long)members) - 1;
+        members &= members - 1;
+        const unsigned int hj = wave_rlu(hash, j);
+        if (j < lane && member && dup_of < 0 && hj == hash) {
+            bool same = true;
+            for (int v = 0; v < nv; ++v) same = same && X.coord[j][v] == X.coord[lane][v];
+            if (same) dup_of = j;
+        }
+    }
+    const bool mine = member && dup_of < 0;
+    members = __ballot(mine);
+    while (members) {
+        const int j = __ffsll((long long)members) - 1;
+        members &= members - 1;
+        const unsigned int fj = wave_rlu(free_slot, j);
+        if (j < lane && mine && fj == free_slot) clash = true;
+    }
 }
 
 // getOrCreateState's table side (manip_lattice.cpp:1302-1354) for the successors of one expansion, by a whole wave (lane =
@@ -401,7 +209,7 @@ __device__ __forceinline__ void search_book_table(const ModelLds* __restrict__ M
                                                   const SmplxGoalDev& G, const SmplxTableDev& table, SMPLX_GLOBAL_AS SmplxSState* st,
                                                   ExpandLds& X, int lane, int nv, bool act, BookLane& b, BookRegs& o, SmplxSState& ss)
 {
-    o.hash = 0; o.pr.id = -1; o.pr.free_slot = 0; o.dup_of = -1; o.clash = false;
+    o.hash = 0; o.pr.id = -1; o.pr.free_slot = 0;
     if (act && b.limits_ok) {
         // getHashEntry (manip_lattice.cpp:1302-1316): the home slot's loads travel behind the planning-link FK; a coordinate the
         // table knows has its search state requested at once (it lands behind the waypoint lanes)
@@ -411,29 +219,63 @@ __device__ __forceinline__ void search_book_table(const ModelLds* __restrict__ M
         o.pr = table_probe_finish(table, ld, (const LDS_AS int*)X.coord[lane], nv);
         if (o.pr.id >= 0 && (!WithGoalFK || !b.is_goal)) ss = sstate_load(&st[o.pr.id]);   // (a goal successor takes the goal's state)
     }
-    const bool c_unknown = act && b.limits_ok && o.pr.id < 0;
-    {
-        unsigned long long members = __ballot(c_unknown);
-        while (members) {                                // uniform
-            const int j = __ffsll((long long)members) - 1;
-            members &= members - 1;
-            const unsigned int hj = wave_rlu(o.hash, j);
-            if (j < lane && c_unknown && o.dup_of < 0 && hj == o.hash) {
-                bool same = true;
-                for (int v = 0; v < nv; ++v) same = same && X.coord[j][v] == X.coord[lane][v];
-                if (same) o.dup_of = j;
-            }
-        }
+    book_find_pairs(X, lane, nv, act && b.limits_ok && o.pr.id < 0, o.hash, o.pr.free_slot, o.dup_of, o.clash);
+}
+
+// what the helper wave leaves for the search wave at the end of a round: lane = primitive
+struct BookOut {
+    int limits_ok[64], wcount[64], h[64], is_goal[64];
+    unsigned int hash[64], free_slot[64];
+    int pr_id[64], dup_of[64], clash[64];
+    int ss[8][64];                         // the successor's search state as stored (sstate_load's two 16-byte words)
+};
+__device__ __forceinline__ void book_out_store(BookOut& Bo, int p, const BookLane& b, const BookRegs& o, const SmplxSState& ss)
+{
+    Bo.limits_ok[p] = b.limits_ok ? 1 : 0; Bo.wcount[p] = b.W; Bo.h[p] = b.h; Bo.is_goal[p] = b.is_goal;
+    Bo.hash[p] = o.hash; Bo.free_slot[p] = o.pr.free_slot; Bo.pr_id[p] = o.pr.id; Bo.dup_of[p] = o.dup_of; Bo.clash[p] = o.clash ? 1 : 0;
+    Bo.ss[0][p] = (int)ss.g; Bo.ss[1][p] = (int)ss.h; Bo.ss[2][p] = (int)ss.f; Bo.ss[3][p] = (int)ss.eg;
+    Bo.ss[4][p] = ss.bp; Bo.ss[5][p] = ss.heap_index;
+    Bo.ss[6][p] = (int)((unsigned int)ss.iteration_closed | ((unsigned int)ss.call_number << 16)); Bo.ss[7][p] = (int)ss.flags;
+}
+__device__ __forceinline__ void book_out_load(const BookOut& Bo, int p, BookLane& b, BookRegs& o, SmplxSState& ss)
+{
+    b.limits_ok = Bo.limits_ok[p] != 0; b.W = Bo.wcount[p]; b.h = Bo.h[p]; b.is_goal = Bo.is_goal[p];
+    o.hash = Bo.hash[p]; o.pr.free_slot = Bo.free_slot[p]; o.pr.id = Bo.pr_id[p];
+    o.dup_of = Bo.dup_of[p]; o.clash = Bo.clash[p] != 0;
+    ss.g = (unsigned int)Bo.ss[0][p]; ss.h = (unsigned int)Bo.ss[1][p]; ss.f = (unsigned int)Bo.ss[2][p];
+    ss.eg = (unsigned int)Bo.ss[3][p]; ss.bp = Bo.ss[4][p]; ss.heap_index = Bo.ss[5][p];
+    const unsigned int itc = (unsigned int)Bo.ss[6][p];
+    ss.iteration_closed = (unsigned short)(itc & 0xFFFFu); ss.call_number = (unsigned short)(itc >> 16);
+    ss.flags = (unsigned int)Bo.ss[7][p];
+}
+
+// The OPEN / INCONS operation of a successor whose g has just improved (arastar.cpp:555-566), by the whole wave with
+// uniform arguments: state `id` with the new key f, its `flags`, whether it had been reached before in this call (only
+// then can it be in OPEN) and whether it is closed in this iteration.  Not closed: its position is read where the sifts
+// keep it current, behind a fence that lets earlier sifts' stores land; it sifts up from there (decrease), or it is pushed
+// with the ancestor cache (`ac_complete`: the cache holds every HBM-resident ancestor the pushes read; the fence stands in
+// where it does not).  Closed: appended to INCONS.
+__device__ __forceinline__ void open_improve_wave(const HeapRef& H, SearchLds& W, SearchRegs& R, const SmplxSearchDev* P, int lane, int id,
+                                                  unsigned int f, unsigned int flags, bool reached_before, bool closed_now, bool ac_complete)
+{
+    if (closed_now) {
+        if (lane == 0) as_global(P->incons)[R.n_incons] = id;      // (never marked: arastar.cpp:563-565)
+        ++R.n_incons;
+        return;
     }
-    {
-        const bool mine = c_unknown && o.dup_of < 0;
-        unsigned long long members = __ballot(mine);
-        while (members) {
-            const int j = __ffsll((long long)members) - 1;
-            members &= members - 1;
-            const unsigned int fj = wave_rlu(o.pr.free_slot, j);
-            if (j < lane && mine && fj == o.pr.free_slot) o.clash = true;
-        }
+    if (id == 0) R.goal_f = f;
+    // a state reached for the first time in this call is not in OPEN
+    int hi = 0;
+    if (reached_before || !ac_complete) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // earlier sifts' stores have landed
+    if (reached_before) hi = as_global(P->st)[id].heap_index;
+    const hent_t e = hent_make(f, id);
+    if (hi != 0) {
+        if (flags & 1u) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, f);
+        heap_sift_up_wave(H, W, lane, hi, e, false);
+    } else {
+        if ((flags & 1u) && R.dup_pushes > 0) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, f);
+        ++R.heap_size;
+        heap_sift_up_wave(H, W, lane, R.heap_size, e, true);
     }
 }
 
@@ -542,17 +384,16 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     }
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                     BookRegs o;
-                    SmplxSState ss;
-                    ss.g = ss.h = ss.f = ss.eg = 0; ss.bp = -1; ss.heap_index = 0; ss.iteration_closed = 0; ss.call_number = 0; ss.flags = 0;
+                    SmplxSState ss = sstate_blank();
                     search_book_table<false>(M, grid, bfs, G, table, as_global(P->st), Xr, p, nv, act, r, o, ss);
-                    Bo.limits_ok[p] = r.limits_ok ? 1 : 0; Bo.wcount[p] = r.W; Bo.h[p] = r.h; Bo.is_goal[p] = r.is_goal;
-                    Bo.hash[p] = o.hash; Bo.free_slot[p] = o.pr.free_slot; Bo.pr_id[p] = o.pr.id; Bo.dup_of[p] = o.dup_of; Bo.clash[p] = o.clash ? 1 : 0;
-                    Bo.ss[0][p] = (int)ss.g; Bo.ss[1][p] = (int)ss.h; Bo.ss[2][p] = (int)ss.f; Bo.ss[3][p] = (int)ss.eg;
-                    Bo.ss[4][p] = ss.bp; Bo.ss[5][p] = ss.heap_index;
-                    Bo.ss[6][p] = (int)((unsigned int)ss.iteration_closed | ((unsigned int)ss.call_number << 16)); Bo.ss[7][p] = (int)ss.flags;
+                    book_out_store(Bo, p, r, o, ss);
                 }
             }
             if (action == SA_REORDER) {
+                // heap_rekey_block (search_heap.h), which the search wave calls at the same moment with the same size, epsilon
+                // and duplicates (it runs that function's barriers against the ones below), written out: called here,
+                // the per-robot build of scenes.mixed_kinds_robot() needs 16 bytes of scratch and two VGPR spills more
+                // (profiles/search_kernel_pieces_ab.txt).  The two must stay the same loop and the same barriers.
                 const int size = W.reorder_size;
                 const double eps = W.reorder_eps;
                 for (int i = 1 + t; i <= size; i += blockDim.x) {     // f of every OPEN entry under the new epsilon (arastar.cpp:571-577)
@@ -571,14 +412,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
         // =============================== the search wave ===============================
         const int lane = t - book0;
         const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-        SearchRegs R;
-        R.curr_eps = P->curr_eps; R.satisfied_eps = P->satisfied_eps;
-        R.heap_size = P->heap_size; R.nstates = P->nstates; R.n_incons = P->n_incons; R.n_log = P->n_log; R.n_succ = P->n_succ;
-        R.iteration = P->iteration; R.call_number = P->call_number; R.phase = P->phase; R.num = P->num;
-        R.expand_count = P->expand_count; R.expand_count_init = P->expand_count_init; R.err = P->err;
-        R.dup_pushes = P->dup_pushes; R.goal_f = P->goal_f;
-        R.committed_evals = P->committed_evals; R.gpu_evals = P->gpu_evals; R.lookups = P->lookups;
-        R.status = SMPLX_SS_RUNNING; R.grow_what = 0; R.steps_left = max_steps;
+        SearchRegs R = search_regs_load(P, max_steps);
         long long ticks[8];
         for (int k = 0; k < 8; ++k) ticks[k] = P->ticks[k];
         long long tick = (long long)wall_clock64();
@@ -711,18 +545,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                 R.n_incons = 0;
                 if (lane == 0) { W.action = SA_REORDER; W.reorder_size = R.heap_size; W.reorder_eps = R.curr_eps; W.reorder_dups = R.dup_pushes; }
                 __syncthreads();                                   // A
-                {
-                    const int size = R.heap_size;
-                    for (int i = 1 + t; i <= size; i += blockDim.x) {
-                        const int eid = hent_id(hget(H, i));
-                        SMPLX_GLOBAL_AS SmplxSState* ss = &as_global(P->st)[eid];
-                        const unsigned int f = search_key(R.curr_eps, ss->g, ss->h);
-                        ss->f = f;
-                        hput(H, i, hent_make(f, eid));
-                    }
-                    __syncthreads();
-                    heap_make_block(H, size, R.dup_pushes > 0);
-                }
+                heap_rekey_block(H, as_global(P->st), R.heap_size, R.curr_eps, R.dup_pushes > 0);
                 __syncthreads();                                   // B
                 R.goal_f = as_global(P->st)[0].f;      // (the goal state is re-initialised when a call starts: its f is this call's)
                 R.phase = 2;
@@ -743,14 +566,8 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
             const bool use_spec = pend == m && off < 0;                         // (only states never expanded are guessed)
             const int cur = use_spec ? pbuf : (pend >= 0 ? pbuf ^ 1 : 0);
             ExpandLds& X = Xb[cur];
-            if (!use_spec) {
-                if (lane < nv) X.parent[lane] = as_global(P->q)[(size_t)m * nv + lane];
-                if (lane < nprims) { X.edge_bad[lane] = 0; X.edge_lk[lane] = 0; }
-                if (lane == 0) { X.state_bad = 0; X.state_lookups = 0; }
-            }
-            if (lane == 0) as_global(P->st)[m].heap_index = 0;
-            --R.heap_size;
-            if (R.heap_size >= 1) heap_sift_down_wave(H, lane, 1, R.heap_size, last);
+            if (!use_spec) round_stage(X, lane, nv, nprims, lane < nv ? as_global(P->q)[(size_t)m * nv + lane] : 0.0);
+            heap_pop_wave(H, lane, m, R.heap_size, last);
             // the new top of OPEN is what the NEXT pop returns unless this step puts something above it: its joint values and
             // heuristic are requested now and looked at when the guess is made (below), a whole evaluation later
             int top_id = -1, top_off = 0;
@@ -777,8 +594,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
             bool valid = false;
             bool ac_complete = true;     // the ancestor cache holds every HBM-resident ancestor the pushes will read
             int sid = -1, cost = 0, cnt = 0, evals = 0;
-            SmplxSState ss;                                          // the successor's search state
-            ss.g = ss.h = ss.f = ss.eg = 0; ss.bp = -1; ss.heap_index = 0; ss.iteration_closed = 0; ss.call_number = 0; ss.flags = 0;
+            SmplxSState ss = sstate_blank();                         // the successor's search state
 
             if (off < 0) {
                 // ---- GetSuccs loop body (manip_lattice.cpp:254-305): successors' joint values, then the waypoint lanes ----
@@ -790,22 +606,10 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     pend = -1;
                     ++spec_hits;
                 } else {
-                    SMPLX_WAVE_SYNC();                               // X.parent is complete
-                    double gd;
-                    if (gd_from_h) {
-                        const int hh = (int)sm.h;
-                        gd = goal_distance_of_h(hh, cpc, grid);
-                    } else {
-                        double g1 = 0.0;
-                        if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, X.parent);
-                        const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
-                        gd = __longlong_as_double((long long)bits);
-                    }
-                    act = in && mprim_active(A, gd, A.type[lane]) && successor_values(M, A, G, lane, X.parent, X.sq[lane]);
+                    act = round_gate(M, A, G, grid, bfs, gd_from_h, X, lane, nprims, (int)sm.h);
                     if (pend >= 0) { __syncthreads(); pend = -1; }   // B of the round that guessed wrong
-                    if (in) X.lookups[lane] = act ? 1 : 0;
                     ++round_seq;
-                    if (lane == 0) { X.goal_dist = gd; W.action = SA_EVAL; W.buf = cur; W.seq = round_seq; W.go = round_seq; }
+                    if (lane == 0) { W.action = SA_EVAL; W.buf = cur; W.seq = round_seq; W.go = round_seq; }
                     __syncthreads();                                 // A
                 }
                 BookLane b;
@@ -824,39 +628,13 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                 const int nxt = cur ^ 1;
                 bool top_ready = false, top_act = false;
                 if (top_id > 0 && top_off < 0 && top_f < R.goal_f && R.steps_left > 0) {
-                    ExpandLds& Y = Xb[nxt];
-                    if (lane < nv) Y.parent[lane] = top_q;
-                    if (lane < nprims) { Y.edge_bad[lane] = 0; Y.edge_lk[lane] = 0; }
-                    if (lane == 0) { Y.state_bad = 0; Y.state_lookups = 0; }
-                    SMPLX_WAVE_SYNC();                               // Y.parent is complete
-                    double gd2;
-                    if (gd_from_h) {
-                        const int hh = (int)top_h;
-                        gd2 = goal_distance_of_h(hh, cpc, grid);
-                    } else {
-                        double g1 = 0.0;
-                        if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, Y.parent);
-                        const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
-                        gd2 = __longlong_as_double((long long)bits);
-                    }
-                    top_act = in && mprim_active(A, gd2, A.type[lane]) && successor_values(M, A, G, lane, Y.parent, Y.sq[lane]);
-                    if (in) Y.lookups[lane] = top_act ? 1 : 0;
-                    if (lane == 0) Y.goal_dist = gd2;
+                    top_act = round_prepare(M, A, G, grid, bfs, gd_from_h, Xb[nxt], lane, nv, nprims, top_q, (int)top_h);
                     top_ready = true;
                 }
                 __syncthreads();                                     // B: the waypoint verdicts have landed
                 SK_TICK(2);
                 if (has_helper && W.helper_gave_up) R.steps_left = 0;      // leave at the next selection; the status says why (below)
-                if (has_helper && in) {
-                    b.limits_ok = Bo.limits_ok[lane] != 0; b.W = Bo.wcount[lane]; b.h = Bo.h[lane]; b.is_goal = Bo.is_goal[lane];
-                    bk.hash = Bo.hash[lane]; bk.pr.free_slot = Bo.free_slot[lane]; bk.pr.id = Bo.pr_id[lane];
-                    bk.dup_of = Bo.dup_of[lane]; bk.clash = Bo.clash[lane] != 0;
-                    ss.g = (unsigned int)Bo.ss[0][lane]; ss.h = (unsigned int)Bo.ss[1][lane]; ss.f = (unsigned int)Bo.ss[2][lane];
-                    ss.eg = (unsigned int)Bo.ss[3][lane]; ss.bp = Bo.ss[4][lane]; ss.heap_index = Bo.ss[5][lane];
-                    const unsigned int itc = (unsigned int)Bo.ss[6][lane];
-                    ss.iteration_closed = (unsigned short)(itc & 0xFFFFu); ss.call_number = (unsigned short)(itc >> 16);
-                    ss.flags = (unsigned int)Bo.ss[7][lane];
-                }
+                if (has_helper && in) book_out_load(Bo, lane, b, bk, ss);
                 const bool cand = act && b.limits_ok;
                 unsigned int hash = bk.hash;
                 TableProbe pr = bk.pr;
@@ -887,7 +665,9 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                 if (!unknown) dup_of = -1;
                 {
                     // a candidate that was to create the state for a later one turned out to collide (rare): the pairs again,
-                    // among the valid successors only
+                    // among the valid successors only.  This is book_find_pairs(X, lane, nv, unknown, hash, pr.free_slot, dup_of,
+                    // clash) written out: called here, the generic build needs 16 bytes of scratch and seven VGPR spills
+                    // more (profiles/search_kernel_pieces_ab.txt).  The two must stay the same loops.
                     const bool root_valid = __shfl((int)valid, dup_of >= 0 ? dup_of : lane) != 0;
                     if (__ballot(unknown && dup_of >= 0 && !root_valid)) {
                         dup_of = -1;
@@ -968,25 +748,12 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     const bool guess_succ = fbest != 0xFFFFFFFFu && fbest < top_f && fbest < R.goal_f;
                     const bool guess_top = !guess_succ && top_id > 0 && top_off < 0 && top_f < R.goal_f;
                     if ((guess_succ || guess_top) && R.steps_left > 0) {
-                        ExpandLds& Y = Xb[nxt];
-                        if (lane < nv) Y.parent[lane] = guess_succ ? X.sq[jbest][lane] : top_q;
-                        if (lane < nprims) { Y.edge_bad[lane] = 0; Y.edge_lk[lane] = 0; }
-                        if (lane == 0) { Y.state_bad = 0; Y.state_lookups = 0; }
-                        SMPLX_WAVE_SYNC();                           // Y.parent is complete
-                        double gd2;
-                        if (gd_from_h) {
-                            const int hh = guess_succ ? wave_rl((int)ss.h, jbest) : (int)top_h;
-                            gd2 = goal_distance_of_h(hh, cpc, grid);
-                        } else {
-                            double g1 = 0.0;
-                            if (lane == 0) g1 = metric_goal_distance(M, grid, bfs, Y.parent);
-                            const unsigned long long bits = wave_rl64((unsigned long long)__double_as_longlong(g1), 0);
-                            gd2 = __longlong_as_double((long long)bits);
-                        }
-                        p_act = in && mprim_active(A, gd2, A.type[lane]) && successor_values(M, A, G, lane, Y.parent, Y.sq[lane]);
-                        if (in) Y.lookups[lane] = p_act ? 1 : 0;
+                        double guess_q = top_q;
+                        if (guess_succ && lane < nv) guess_q = X.sq[jbest][lane];
+                        const int guess_h = guess_succ ? wave_rl((int)ss.h, jbest) : (int)top_h;
+                        p_act = round_prepare(M, A, G, grid, bfs, gd_from_h, Xb[nxt], lane, nv, nprims, guess_q, guess_h);
                         ++round_seq;
-                        if (lane == 0) { Y.goal_dist = gd2; W.action = SA_EVAL; W.buf = nxt; W.seq = round_seq; }
+                        if (lane == 0) { W.action = SA_EVAL; W.buf = nxt; W.seq = round_seq; }
                         __syncthreads();                             // A of the guessed round
                         pend = guess_succ ? wave_rl(sid, jbest) : top_id;
                         pbuf = nxt;
@@ -1065,28 +832,8 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                 while (rest) {
                     const int j = __ffsll((long long)rest) - 1;
                     rest &= rest - 1;
-                    const int id = wave_rl(sid, j);
-                    if (wave_rl((int)closed_now, j) == 0) {
-                        const unsigned int fj = wave_rlu(f, j);
-                        const unsigned int flags_j = wave_rlu(ss.flags, j);
-                        const bool reached_j = wave_rl((int)reached_before, j) != 0;
-                        if (id == 0) R.goal_f = fj;
-                        int hi = 0;
-                        if (reached_j || !ac_complete) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // earlier sifts' stores have landed
-                        if (reached_j) hi = as_global(P->st)[id].heap_index;
-                        const hent_t e = hent_make(fj, id);
-                        if (hi != 0) {
-                            if (flags_j & 1u) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, fj);
-                            heap_sift_up_wave(H, W, lane, hi, e, false);
-                        } else {
-                            if ((flags_j & 1u) && R.dup_pushes > 0) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, fj);
-                            ++R.heap_size;
-                            heap_sift_up_wave(H, W, lane, R.heap_size, e, true);
-                        }
-                    } else {
-                        if (lane == 0) as_global(P->incons)[R.n_incons] = id;      // (never marked: arastar.cpp:563-565)
-                        ++R.n_incons;
-                    }
+                    open_improve_wave(H, W, R, P, lane, wave_rl(sid, j), wave_rlu(f, j), wave_rlu(ss.flags, j),
+                                      wave_rl((int)reached_before, j) != 0, wave_rl((int)closed_now, j) != 0, ac_complete);
                 }
             } else {
                 unsigned long long rest = m_succ;
@@ -1109,30 +856,14 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
                     }
                     const int new_cost = (int)(eg + (unsigned int)cj);
                     if (!((unsigned int)new_cost < g_r)) continue;
-                    const bool reached_before = g_r != SMPLX_INFINITECOST;
                     if (lane == r) { ss.g = (unsigned int)new_cost; ss.bp = m; dirty = true; }
-                    if ((itc_r & 0xFFFFu) != ((unsigned int)R.iteration & 0xFFFFu)) {
-                        const unsigned int f = search_key(R.curr_eps, (unsigned int)new_cost, h_r);
+                    const bool closed_now = (itc_r & 0xFFFFu) == ((unsigned int)R.iteration & 0xFFFFu);
+                    unsigned int f = 0;
+                    if (!closed_now) {
+                        f = search_key(R.curr_eps, (unsigned int)new_cost, h_r);
                         if (lane == r) ss.f = f;
-                        if (id == 0) R.goal_f = f;
-                        // a state reached for the first time in this call is not in OPEN; otherwise its position is read where
-                        // the sifts keep it current
-                        int hi = 0;
-                        if (reached_before || !ac_complete) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // earlier sifts' stores have landed
-                        if (reached_before) hi = as_global(P->st)[id].heap_index;
-                        const hent_t e = hent_make(f, id);
-                        if (hi != 0) {
-                            if (flags_r & 1u) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, f);
-                            heap_sift_up_wave(H, W, lane, hi, e, false);
-                        } else {
-                            if ((flags_r & 1u) && R.dup_pushes > 0) heap_refresh_duplicates_wave(H, W, lane, R.heap_size, id, f);
-                            ++R.heap_size;
-                            heap_sift_up_wave(H, W, lane, R.heap_size, e, true);
-                        }
-                    } else {
-                        if (lane == 0) as_global(P->incons)[R.n_incons] = id;      // (never marked: arastar.cpp:563-565)
-                        ++R.n_incons;
                     }
+                    open_improve_wave(H, W, R, P, lane, id, f, flags_r, g_r != SMPLX_INFINITECOST, closed_now, ac_complete);
                 }
             }
             if (dirty && valid && alias < 0) sstate_store(&as_global(P->st)[sid], ss, false);
@@ -1173,13 +904,7 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
             }
             if (W.helper_gave_up) R.status = SMPLX_SS_ERROR;
             Pd->solved = solved; Pd->cost = cost; Pd->n_path = n_path;
-            Pd->curr_eps = R.curr_eps; Pd->satisfied_eps = R.satisfied_eps;
-            Pd->heap_size = R.heap_size; Pd->nstates = R.nstates; Pd->n_incons = R.n_incons; Pd->n_log = R.n_log; Pd->n_succ = R.n_succ;
-            Pd->iteration = R.iteration; Pd->call_number = R.call_number; Pd->phase = R.phase; Pd->num = R.num;
-            Pd->expand_count = R.expand_count; Pd->expand_count_init = R.expand_count_init; Pd->err = R.err;
-            Pd->dup_pushes = R.dup_pushes; Pd->goal_f = R.goal_f;
-            Pd->status = R.status; Pd->grow_what = R.grow_what;
-            Pd->committed_evals = R.committed_evals; Pd->gpu_evals = R.gpu_evals; Pd->lookups = R.lookups;
+            search_regs_store(Pd, R);
             Pd->t_start = t_start;
             SK_TICK(6);
             ticks[7] += (spec_issued << 32) + spec_hits;            // rounds opened on a guess | guesses the next pop confirmed
@@ -1193,122 +918,5 @@ k_search(const SmplxSpaceDev* const* __restrict__ stab, int max_steps, int lh, i
     {
         const int n = W.reorder_size + 1 < lh ? W.reorder_size + 1 : lh;
         for (int i = t; i < n; i += blockDim.x) H.hbm[i] = H.lds[i];
-    }
-}
-
-// getOrCreateState for states the device table does not hold yet (the start state the host created; every state after
-// the table was enlarged): inserts ids [first, n) of the query's coordinate array
-extern "C" __global__ void __launch_bounds__(256)
-k_search_table_fill(const SmplxSpaceDev* __restrict__ Sq, const int* __restrict__ coord, int first, int n, int nvars)
-{
-    const SmplxTableDev T = Sq->table;
-    for (int id = first + blockIdx.x * blockDim.x + threadIdx.x; id < n; id += gridDim.x * blockDim.x) {
-        if (id == 0) continue;      // the goal id has no coordinate (manip_lattice.cpp:122)
-        const int* c = coord + (size_t)id * nvars;
-        unsigned int k = smplx_coord_hash(c, nvars) & T.mask;
-        while (true) {
-            SMPLX_GLOBAL_AS int* sl = as_global(T.slots) + (size_t)k * T.stride;
-            if (atomicCAS((int*)&sl[0], 0, -(id + 1)) == 0) {
-                for (int v = 0; v < nvars; ++v) sl[1 + v] = c[v];
-                __threadfence();
-                __atomic_store_n(&sl[0], id + 1, __ATOMIC_RELAXED);
-                break;
-            }
-            k = (k + 1) & T.mask;
-        }
-    }
-}
-
-// Parity-test kernel (test_hooks.h): the state-table probe of k_search (table_probe_start / table_probe_finish /
-// table_store_own) on a table of the caller's size.  insert = 1: one lane takes the n coordinates in turn, probes, and stores
-// coordinate i under id i where the probe found none (out[i] = what the probe found, -1 for a new coordinate); insert = 0:
-// every lane looks its share of the n coordinates up (out[i] = id or -1).  one_home: every coordinate's probe starts at
-// slot 0 instead of its hash, so that a lookup walks over every state inserted before the one it looks for.
-extern "C" __global__ void __launch_bounds__(64)
-k_table_probe_ops(SmplxTableDev T, const int* __restrict__ coords, int n, int nv, int one_home, int insert, int* __restrict__ out)
-{
-    __shared__ int cbuf[64][SMPLX_MAX_VARS];
-    const int lane = threadIdx.x;
-    if (insert && lane != 0) return;
-    for (int i = lane; i < n; i += insert ? 1 : 64) {
-        for (int v = 0; v < nv; ++v) cbuf[lane][v] = coords[(size_t)i * nv + v];
-        const LDS_AS int* c = (const LDS_AS int*)cbuf[lane];
-        const unsigned int hash = one_home ? 0u : coord_hash_lds(c, nv);
-        TableProbeLoads ld = table_probe_start(T, nv, hash);
-        const TableProbe pr = table_probe_finish(T, ld, c, nv);
-        out[i] = pr.id;
-        if (insert && pr.id < 0) {
-            table_store_own(T, pr.free_slot, c, nv, i);
-            __threadfence();
-        }
-    }
-}
-
-// Parity-test kernel (test_hooks.h): the heap primitives of k_search driven by an op sequence in the language of
-// oracle/heap_ref_driver.cpp -- 0 push(priority), 1 pop, 2 / 5 decrease / increase(element << 20 | priority), 3 erase(element),
-// 4 re-prioritise everything and make() -- so that they can be compared with the reference's own intrusive_heap
-// (tests/golden/heap_ref.json).  Element e is state e; the first `lh` heap entries live in LDS, the rest in HBM.  One wave:
-// push / decrease run the wave-parallel sift-up, pop / increase / erase the wave-parallel sift-down, make() the level-parallel
-// form -- the code paths of the search.
-extern "C" __global__ void __launch_bounds__(64)
-k_heap_ops(const int* __restrict__ ops, int nops, int lh, unsigned long long* __restrict__ heap_hbm, SmplxSState* __restrict__ st,
-           int* __restrict__ top_after)
-{
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ SearchLds W;
-    HeapRef H;
-    H.lds = (LDS_AS hent_t*)smem;
-    H.hbm = as_global(heap_hbm);
-    H.st = as_global(st);
-    H.lh = lh;
-    const int lane = threadIdx.x;
-    if (lane == 0) W.ac_nlev = 0;
-    __syncthreads();
-    int nelem = 0, size = 0;
-    for (int i = 0; i < nops; ++i) {
-        const int code = ops[2 * i], key = ops[2 * i + 1];
-        if (code == 0) {
-            if (lane == 0) { st[nelem].f = (unsigned int)key; st[nelem].heap_index = 0; }
-            ++size;
-            heap_sift_up_wave(H, W, lane, size, hent_make((unsigned int)key, nelem), false);
-            ++nelem;
-        } else if (code == 1) {
-            if (size > 0) {
-                const hent_t top = hget(H, 1), last = hget(H, size);
-                if (lane == 0) st[hent_id(top)].heap_index = 0;
-                --size;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                if (size >= 1) heap_sift_down_wave(H, lane, 1, size, last);
-            }
-        } else if (code == 2 || code == 5) {
-            const int e = key >> 20, p = key & 0xFFFFF;
-            const int hi = e < nelem ? st[e].heap_index : 0;
-            if (hi != 0) {
-                if (lane == 0) st[e].f = (unsigned int)p;
-                if (code == 2) heap_sift_up_wave(H, W, lane, hi, hent_make((unsigned int)p, e), false);
-                else heap_sift_down_wave(H, lane, hi, size, hent_make((unsigned int)p, e));
-            }
-        } else if (code == 3) {
-            const int pos = key < nelem ? st[key].heap_index : 0;
-            if (pos != 0) {                                      // intrusive_heap.hpp:197-206
-                const hent_t last = hget(H, size);
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                if (lane == 0) { hset(H, pos, last); st[key].heap_index = 0; }
-                --size;
-                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-                if (pos <= size) heap_sift_down_wave(H, lane, pos, size, last);
-            }
-        } else if (code == 4) {
-            for (int k = 1 + lane; k <= size; k += 64) {
-                const int e = hent_id(hget(H, k));
-                const unsigned int p = (st[e].f * 7919u + 13u) % 1000u;
-                st[e].f = p;
-                hput(H, k, hent_make(p, e));
-            }
-            __syncthreads();
-            heap_make_block(H, size, false);
-        }
-        __syncthreads();      // (one wave: orders what the lanes stored with what the next op reads)
-        if (lane == 0) top_after[i] = size > 0 ? hent_id(hget(H, 1)) : -1;
     }
 }

@@ -1,6 +1,7 @@
 // smpl_amd/csrc/small_batch.h -- one block per state: small frontier batches, and the pieces k_search is built from.
 // Owns: ExpandLds, the lane functions (expand_config_lane, expand_book_*, expand_verdict), SMPLX_WAVE_SYNC,
-// expand_state_block and k_small_batch.  search_kernel.h uses expand_state_block and the lane functions.
+// expand_state_block and k_small_batch.  search_kernel.h builds the rounds of k_search from the lane functions (round_prepare,
+// search_book_table there).
 // Restates: manip_lattice.cpp:254-305 (the GetSuccs loop body, in lane-sized pieces).
 #pragma once
 

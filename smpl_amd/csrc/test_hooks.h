@@ -31,12 +31,13 @@ long long smplx_test_one_launch_steps(const smplx_space* s);
  * is in flight on it, 0 if not; an error (negative) if no step has run on the stream. */
 int smplx_test_step_counters_zero(smplx_space* s, void* stream);
 
-/* The heap primitives of the device-resident search (search_kernel.h) driven by an op sequence in the language of
- * oracle/heap_ref_driver.cpp (pairs code, key; see k_heap_ops): top_after[i] = element at the top after op i, -1 when empty.
+/* The heap primitives of the device-resident search (search_heap.h; pop is the search's own heap_pop_wave) driven by an op
+ * sequence in the language of oracle/heap_ref_driver.cpp (pairs code, key; see k_heap_ops): top_after[i] = element at the top
+ * after op i, -1 when empty.
  * lds_entries = how many leading heap entries live in LDS (the rest in HBM), 1 .. 4096. */
 int smplx_test_heap_ops(const int32_t* ops, int nops, int lds_entries, int32_t* top_after);
 
-/* The state-table probe of the device-resident search (search_kernel.h table_probe_start / table_probe_finish /
+/* The state-table probe of the device-resident search (search_table.h table_probe_start / table_probe_finish /
  * table_store_own, see k_table_probe_ops) on an empty table of `slots` slots (a power of two, more than n_inserted) for
  * coordinates of nvars ints: `inserted` go in one after the other, coordinate i under id i (found_at_insert[i] = what the
  * probe found before the store: -1 unless the coordinate was there already), then every row of `queries` is looked up

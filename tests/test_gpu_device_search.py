@@ -162,6 +162,76 @@ def test_device_search_through_epsilon_steps(small_cfg, monkeypatch, helper_wave
     _check_against_oracle(o, s, eo, go)
     assert go["solved"] == 1 and go["satisfied_eps"] <= 3.0 and go["cost"] > 0      # at least two epsilon steps finished
     assert go["expansions"] > go["expansions_init"] > 0
+    # No state of this search is improved twice while it is closed in one iteration (the plain loop of arastar_loop.py finds
+    # none either), so INCONS never brings OPEN an element it already holds.  The counter exists on the device only; 0 is
+    # what it read before k_search was built from pieces (profiles/search_kernel_pieces_ab.txt) and pins that the INCONS /
+    # OPEN / heap_index handling makes no duplicates of its own.
+    dup_pushes = s.search_counters()["dup_pushes"]
+    print("dup_pushes", dup_pushes)
+    assert dup_pushes == 0
+
+
+def _branch_case(name, helper_wave, generic=False, capacity=0):
+    """the device search of a case of search_branch_cases.py: (oracle, its result, the events, the space, its result)"""
+    import search_branch_cases as sb
+    from smpl_amd import capi
+    _need_gpu()
+    o, sid, eo, ev = sb.case_truth(name)
+    cfg = sb.case_config(name)
+    s = capi.Space.from_config(cfg, batch_states=256, generic_kernels=generic)
+    s.set_search_helper(helper_wave)
+    if capacity:
+        s.set_search_capacity(capacity)
+    s.set_goal_joint(cfg.goal, sb.case_goal_tol(name, cfg))
+    assert s.set_start(cfg.start) == sid
+    go = s.plan(*sb.EPS, True, True, *sb.case_bounds(name))
+    print(name, "helper" if helper_wave else "inline", "generic" if generic else "per-robot", ev, s.search_counters())
+    return o, eo, ev, s, go
+
+
+@pytest.mark.parametrize("helper_wave", [True, False], ids=["helper", "inline"])
+def test_two_goal_successors_of_one_expansion(monkeypatch, helper_wave):
+    """A joint goal wide enough for a state to have two primitives inside it: both successors are the goal's entry, so the
+    expansion is relaxed by the loop in primitive order and the second one meets what the first stored.  That the search
+    has such an expansion is the oracle's word (search_branch_cases.py); the search itself is the oracle's."""
+    monkeypatch.setenv("SMPLX_SEARCH", "device")
+    o, eo, ev, s, go = _branch_case("goal_pair", helper_wave)
+    assert ev["two_goal"] >= 1
+    _check_against_oracle(o, s, eo, go)
+    assert go["solved"] == 1 and go["satisfied_eps"] == 1.0
+
+
+@pytest.mark.parametrize("helper_wave", [True, False], ids=["helper", "inline"])
+def test_one_primitive_row_listed_twice(monkeypatch, helper_wave):
+    """The two-joint chain with a primitive row listed twice: the copies land in one cell, so among the new states of an
+    expansion two share a coordinate (the lower primitive creates the state, the other takes its id) and two probes find
+    the same known state; either way two successors name one state.  Stopped after 300 expansions."""
+    monkeypatch.setenv("SMPLX_SEARCH", "device")
+    o, eo, ev, s, go = _branch_case("twin_rows", helper_wave, generic=True)
+    assert ev["alias_new"] >= 1 and ev["alias_old"] >= 1
+    _check_against_oracle(o, s, eo, go)
+    for i in range(1, o.num_states()):
+        assert np.array_equal(o.get_state(i)[1], s.get_state(i)[1]), i
+
+
+@pytest.mark.parametrize("generic", [False, True], ids=["per-robot", "generic"])
+@pytest.mark.parametrize("helper_wave", [True, False], ids=["helper", "inline"])
+def test_two_new_states_probe_to_one_empty_slot(monkeypatch, helper_wave, generic):
+    """config_small stopped after 110 expansions, in the smallest state table the search does not outgrow (2048 slots for
+    about a thousand states): by the table model of search_branch_cases.py some expansions create two states whose probes
+    end at the same empty slot, and the later one has to probe again behind the other.  The model holds because the device
+    kept its first table, of the model's size; a state stored in the wrong slot would be created a second time, which
+    the state count, the log and the coordinates of every state would show."""
+    import search_branch_cases as sb
+    monkeypatch.setenv("SMPLX_SEARCH", "device")
+    o, _, _, ev = sb.case_truth("clash")
+    o, eo, ev, s, go = _branch_case("clash", helper_wave, generic=generic, capacity=sb.clash_capacity(ev, o.M))
+    assert ev["clash"] >= 1 and ev["unlisted"] == 0
+    _check_against_oracle(o, s, eo, go)
+    sc = s.search_counters()
+    assert sc["table_allocs"] == 1 and s.table_slots() == ev["table_slots"]
+    for i in range(1, o.num_states()):
+        assert np.array_equal(o.get_state(i)[1], s.get_state(i)[1]), i
 
 
 def test_device_search_outgrows_its_buffers(small_cfg, monkeypatch):

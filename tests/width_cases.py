@@ -38,7 +38,7 @@ LEADS = 3                               # links whose spheres are checked agains
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# the layout formulas, restated (device_types.h, kernels.h, search_kernel.h, search_host.h)
+# the layout formulas, restated (device_types.h, kernels.h, search_kernel.h, search_table.h, search_host.h)
 # ----------------------------------------------------------------------------------------------------------------------
 
 def table_stride(nv):
